@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoise-step latent-frames/sec on 32x16x16 latent clips (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one VqVideoDiffusionModel.forward over a batch of synthetic random-token clips (config 4:
 B = 8 clips per GPU, 32x16x16 latents, codebook 1024, dim 256, dim_head 128, extents 3,3,3, depth 4, mlp 256),
 bf16 operands / fp32 accumulation, inputs resident in HBM.  Clips are independent: every rank runs its own
 batch, no data-path collective ("weak" scaling).  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline step only.  --full adds the figures that take runs of their own: per-kernel
+rooflines, the other precisions, windows, widths and configurations, the sampler, the frame encoder, the training
+steps and the CPU baseline.  --dump-outputs DIR writes the logits of the last timed step (rank 0) as DIR/logits.npy.
 """
 import argparse
 import json
@@ -177,13 +181,21 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-cone', action='store_true', help='skip the secondary last-frame-cone figure (cleaner kernel traces)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the encoder token check')
+    ap.add_argument('--no-cone', action='store_true', help='with --full: skip the secondary last-frame-cone figure (cleaner kernel traces)')
     ap.add_argument('--eager', action='store_true', help='replay the Python launch path instead of the hipGraph')
-    ap.add_argument('--train-steps', type=int, default=30, help='timed full training steps reported as train_step (0 = skip)')
+    ap.add_argument('--train-steps', type=int, default=30,
+                    help='with --full: timed full training steps reported as train_step (0 = skip)')
     ap.add_argument('--secondary-timeout', type=int, default=420,
-                    help='n_gpus > 1: seconds after which a hung secondary figure is abandoned and the headline line printed (0 = never)')
+                    help='with --full, n_gpus > 1: seconds after which a hung secondary figure is abandoned and the headline line printed (0 = never)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, the secondary figures: kernel rooflines, other precisions / sizes / configurations, '
+                         'sampler, frame encoder, training steps, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the last timed step\'s logits [B, H, W, C] (rank 0) as DIR/logits.npy, float32')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # Plain `python bench.py --gpus N`: start the N ranks ourselves, as fresh child processes of torch.distributed.run, BEFORE
@@ -307,6 +319,49 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(y).all()
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the last frame's logits (fp32, 8 MB at config 4)
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, 'logits.npy'), y.float().cpu().numpy())
+        log(f'logits {tuple(y.shape)} written to {a.dump_outputs}')
+
+    frames = cfg['B'] * cfg['S'] * world * a.steps
+    ms_per_step = elapsed / a.steps * 1e3
+    elt = 2 if dtype == torch.bfloat16 else 4
+    step_bytes, attn_bytes = algorithmic_bytes(cfg, elt)
+    N = cfg['B'] * cfg['S'] * cfg['H'] * cfg['W']
+    out = {
+        'metric': 'denoise-step latent-frames/sec (forward, 32x16x16 latent clips)',
+        'value': frames / elapsed, 'unit': 'latent-frames/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
+        'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': a.dtype, 'data': 'synthetic random tokens, random-init weights (seed 42)',
+        'config': {'workload': 'BASELINE.json configs[3] per GPU: VqVideoDiffusionModel.forward, B=8 clips/GPU of '
+                               '32x16x16 latents, codebook 1024, dim 256, dim_head 128, heads 1, extents 3,3,3, '
+                               'depth 4, mlp 256',
+                   'clips_per_gpu': cfg['B'], 'latent_shape': [cfg['S'], cfg['H'], cfg['W']], 'codebook': cfg['C'],
+                   'parallelism': f'clips sharded over {world} rank(s), no data-path collective'},
+        'rccl_ranks': ranks_seen if backend in (None, 'nccl') else 0,
+        'dist_backend': {None: None, 'nccl': 'nccl (RCCL)'}.get(backend, f'{backend} (REHEARSAL: ranks share cards, not an RCCL/xGMI figure)'),
+        'devices_visible': ndev,
+        'launch_mode': 'eager' if a.eager else 'hipGraph replay (1 graph = 1 forward step)',
+        'clip_streams': wcfg.get_clip_streams(),
+        'sclk_mhz_after_timed_region': sclk_mhz,
+        'step_roofline': {'algorithmic_bytes_per_step': step_bytes,
+                          'achieved_GBs': step_bytes / (ms_per_step * 1e-3) / 1e9,
+                          'frac_of_8TBs': step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          # SURVEY 8(d): both denominators -- the 8.0 TB/s specification and the 6.29 TB/s a float4 copy measures
+                          'frac_of_measured_copy_6.29TBs': step_bytes / (ms_per_step * 1e-3) / 1e9 / 6290.0},
+    }
+    if not a.full:
+        # a plain run ends with the headline: everything below takes runs of its own
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            sys.stdout.flush()
+            sys.stderr.flush()
+            os._exit(0)                    # as at the end of a --full run: no hand-made teardown of the communicator
+        return
 
     # Per-launch durations of the two kernels that carry the step (the fused per-token layer kernel and the local-3D
     # attention forward), measured live with HIP events on the launch stream (torch's current stream);
@@ -360,11 +415,6 @@ def main():
         attn_ms = time_kernel(run_attn, reps)
         fused_ms = time_kernel(run_fused, reps) if use_fused else None
 
-    frames = cfg['B'] * cfg['S'] * world * a.steps
-    ms_per_step = elapsed / a.steps * 1e3
-    elt = 2 if dtype == torch.bfloat16 else 4
-    step_bytes, attn_bytes = algorithmic_bytes(cfg, elt)
-    N = cfg['B'] * cfg['S'] * cfg['H'] * cfg['W']
     attn_gbs = attn_bytes / (attn_ms * 1e-3) / 1e9
     attn_roof = {'bound': 'hbm', 'kernel': 'attn_fwd_row16_kernel (local 3D attention forward)', 'achieved': attn_gbs,
                  'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': attn_gbs / HBM_PEAK_GBS, 'traffic': None,
@@ -430,30 +480,8 @@ def main():
     # head + tail launches (the one timed here), the embedding + tail launch and the last layer's head-only launch, which take
     # ~0.6 and ~0.7 of a head + tail launch (profiles/r03/headline_by_grid.csv: 30 and 36 us beside 48-52); attention: depth times.
     dominant_fused = fused_roof is not None and fused_ms * (cfg['depth'] - 1 + 1.3) > attn_ms * cfg['depth']
-    out = {
-        'metric': 'denoise-step latent-frames/sec (forward, 32x16x16 latent clips)',
-        'value': frames / elapsed, 'unit': 'latent-frames/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
-        'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': a.dtype, 'data': 'synthetic random tokens, random-init weights (seed 42)',
-        'config': {'workload': 'BASELINE.json configs[3] per GPU: VqVideoDiffusionModel.forward, B=8 clips/GPU of '
-                               '32x16x16 latents, codebook 1024, dim 256, dim_head 128, heads 1, extents 3,3,3, '
-                               'depth 4, mlp 256',
-                   'clips_per_gpu': cfg['B'], 'latent_shape': [cfg['S'], cfg['H'], cfg['W']], 'codebook': cfg['C'],
-                   'parallelism': f'clips sharded over {world} rank(s), no data-path collective'},
-        'rccl_ranks': ranks_seen if backend in (None, 'nccl') else 0,
-        'dist_backend': {None: None, 'nccl': 'nccl (RCCL)'}.get(backend, f'{backend} (REHEARSAL: ranks share cards, not an RCCL/xGMI figure)'),
-        'devices_visible': ndev,
-        'roofline': fused_roof if dominant_fused else attn_roof,
-        'roofline_other': attn_roof if dominant_fused else fused_roof,
-        'launch_mode': 'eager' if a.eager else 'hipGraph replay (1 graph = 1 forward step)',
-        'clip_streams': wcfg.get_clip_streams(),
-        'sclk_mhz_after_timed_region': sclk_mhz,
-        'step_roofline': {'algorithmic_bytes_per_step': step_bytes,
-                          'achieved_GBs': step_bytes / (ms_per_step * 1e-3) / 1e9,
-                          'frac_of_8TBs': step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                          # SURVEY 8(d): both denominators -- the 8.0 TB/s specification and the 6.29 TB/s a float4 copy measures
-                          'frac_of_measured_copy_6.29TBs': step_bytes / (ms_per_step * 1e-3) / 1e9 / 6290.0},
-    }
+    out['roofline'] = fused_roof if dominant_fused else attn_roof
+    out['roofline_other'] = attn_roof if dominant_fused else fused_roof
     gc.collect()
     # The secondary figures below must never cost the headline line: whatever one of them raises (every rank runs the same
     # code on the same shapes, so a failure is the same on all ranks and no rank is left waiting in a collective) is recorded

@@ -58,9 +58,11 @@ def test_transformer_tiny():
     assert rel(oden.denoiser_forward(sd, g['z'], ext, heads), g['logits']) < 2e-6
     # shorter clip than the position table (reference test(), local_3d_attention.py:168-171)
     assert rel(oden.denoiser_forward(sd, g['z_short'], ext, heads), g['logits_short']) < 2e-6
-    # batch chunking is exact (clips are independent)
-    assert torch.equal(oden.denoiser_forward(sd, g['z'], ext, heads, batch_chunk=1),
-                       oden.denoiser_forward(sd, g['z'], ext, heads))
+    # batch chunking only splits the clips (they are independent): the reference's logits, and the whole batch's up to the
+    # last bits a CPU GEMM may round differently at another row count (MKL's AVX2 kernels do, 6.5e-8 here; its AVX-512 ones do not)
+    chunked = oden.denoiser_forward(sd, g['z'], ext, heads, batch_chunk=1)
+    assert rel(chunked, g['logits']) < 2e-6
+    assert rel(chunked, oden.denoiser_forward(sd, g['z'], ext, heads)) < 1e-6
 
 
 def test_transformer_identity_out():
