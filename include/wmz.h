@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define WMZ_VERSION 113
+#define WMZ_VERSION 114
 
 enum { WMZ_F32 = 0, WMZ_BF16 = 1,
        WMZ_F16 = 2 /* IEEE half activations / MFMA operands: the PRECISE fused inference mode (wmz_local3d_attn_fwd* on the
@@ -108,17 +108,11 @@ int wmz_linear_fwd_blocked(const void* A, long lda, int rows_per_block, long blo
                            const float* bias, void* C, long ldc, int M, int N, int K, int out_f32, int dtype, void* stream);
 
 /* Weight / bias gradient of the family above: dW[N,K] += dC[M,N]^T . A'[M,K], dbias[N] += colsum(dC), where
- * A' = A, LayerNorm(A) (ln_* non-NULL; mean/rstd from wmz_layernorm_stats) or GELU(A) (gelu_in).  dW / dbias are fp32
- * and ACCUMULATED with float atomics (split over M): zero them first, or pass .grad buffers to accumulate. */
-int wmz_linear_wgrad(const void* dC, long ldc, const void* A, long lda, float* dW, float* dbias, int M, int N, int K,
-                     const float* ln_gamma, const float* ln_beta, const float* ln_mean, const float* ln_rstd,
-                     int gelu_in, int dtype, void* stream);
-
-/* The same with a two-stage reduction instead of float atomics: the slices of M leave their 128 x 128 partial tiles in
- * `workspace` (fp32, at least wmz_linear_wgrad_workspace_floats(M, N, K, dtype) floats, contents undefined afterwards) and
- * a second launch adds their sum to dW / dbias (overwrite != 0: stores it instead) -- deterministic summation order, no
- * same-address atomics.  The caller owns the workspace (the library never allocates); one workspace can serve every wgrad
- * on a stream. */
+ * A' = A, LayerNorm(A) (ln_* non-NULL; mean/rstd from wmz_layernorm_stats) or GELU(A) (gelu_in); dW / dbias fp32.  Two-stage
+ * reduction: the slices of M leave their 128 x 128 partial tiles in `workspace` (fp32, at least
+ * wmz_linear_wgrad_workspace_floats(M, N, K, dtype) floats, contents undefined afterwards) and a second launch adds their sum
+ * to dW / dbias (overwrite != 0: stores it instead) -- deterministic summation order, no same-address atomics.  The caller
+ * owns the workspace (the library never allocates); one workspace can serve every wgrad on a stream. */
 long wmz_linear_wgrad_workspace_floats(int M, int N, int K, int dtype);
 int wmz_linear_wgrad_ws(const void* dC, long ldc, const void* A, long lda, float* dW, float* dbias, int M, int N, int K,
                         const float* ln_gamma, const float* ln_beta, const float* ln_mean, const float* ln_rstd,
@@ -385,12 +379,9 @@ int wmz_operands_refresh(const void* const* src0, const void* const* src1, const
 /* The conv encoder / decoder's GEMM operands from nn.Conv2d's fp32 weights [Co, Ci, KH, KW] (kk = KH*KW), every layer in one
  * launch (n <= 48 entries): mode 0 = the forward / weight-gradient layout [Co, kk * Ci8] (tap-major, channels fastest,
  * zero-padded to a multiple of 8), mode 1 = the data-gradient layout [Ci8, kk * Co8] with the taps flipped
- * (autoencoder.py:_w_op / _wT_op); dst in `dtype`. */
-int wmz_conv_operands_refresh(const void* const* weight, void* const* dst, const int* co, const int* ci, const int* kk,
-                              const int* mode, int n, int dtype, void* stream);
-/* The same with, per entry, an optional fragment-order destination instead of the row-major one (bf16): pack[i] = 1: the weight
- * stream of wmz_conv3x3_direct_fwd for that operand (what wmz_conv3x3_direct_pack makes of it), 2: wmz_conv_point_fwd's
- * (wmz_conv_point_pack), 0: row-major as above; pack == NULL: all row-major. */
+ * (autoencoder.py:_w_op / _wT_op); dst in `dtype`.  Per entry, an optional fragment-order destination instead of the row-major
+ * one (bf16): pack[i] = 1: the weight stream of wmz_conv3x3_direct_fwd_strided for that operand (what wmz_conv3x3_direct_pack
+ * makes of it), 2: wmz_conv_point_fwd_bn's (wmz_conv_point_pack), 0: row-major as above; pack == NULL: all row-major. */
 int wmz_conv_operands_refresh_packed(const void* const* weight, void* const* dst, const int* co, const int* ci, const int* kk,
                                      const int* mode, const int* pack, int n, int dtype, void* stream);
 
@@ -415,7 +406,7 @@ int wmz_fused_pack_table(const void* block_rows, int nblk, long total8, const vo
                          void* stream);
 
 /* Training forward on the same kernels (replaces the five per-op GEMM launches per layer of the training forward).
- * Besides the inference outputs they write what the backward (wmz_linear_wgrad, wmz_layernorm_bwd, wmz_local3d_attn_bwd
+ * Besides the inference outputs they write what the backward (wmz_linear_wgrad_ws, wmz_layernorm_bwd, wmz_local3d_attn_bwd
  * ..) reads, row-major: x1_out [ntok, D] = the feed-forward block's input (x + to_out(o)), x_out_rowmajor [ntok, D] = a
  * row-major copy of x_out when x_out itself is tiled (NULL otherwise), and kv_out as ONE [ntok, 2I] buffer (k | v column
  * halves).  z_tiled_out (optional, needs the head and ntok % 32 == 0): the feed-forward pre-activation W1 LN(x1) + b1 as
@@ -423,7 +414,7 @@ int wmz_fused_pack_table(const void* block_rows, int nblk, long total8, const vo
  * exported, the per-op backward recomputes it with one LayerNorm-GEMM.
  * ln_ff_stats / ln_attn_stats (optional, fp32 [2, ntok]: means then reciprocal standard deviations): the statistics of the
  * two LayerNorms the kernel applies -- in front of the feed-forward, and in front of the next layer's k | v -- for the
- * backward (wmz_linear_wgrad's LayerNorm prologue, wmz_linear_fwd_stats), which otherwise spends a pass per LayerNorm. */
+ * backward (wmz_linear_wgrad_ws's LayerNorm prologue, wmz_linear_fwd_stats), which otherwise spends a pass per LayerNorm. */
 int wmz_layer_fused_fwd_train(const void* o, const void* x, void* x_out, void* x_out_rowmajor, void* x1_out, void* q_out,
                               void* kv_out, float* ln_ff_stats, float* ln_attn_stats, void* z_tiled_out, const void* wpack,
                               const float* vec, int ntok, int D, int I, int M, int has_head, int has_tail, int xflags,
@@ -454,7 +445,7 @@ int wmz_embed_qkv_fused_fwd_train(const int64_t* z, const float* emb, const floa
  * from zero_row (D bf16 zeros) -- no [ntok, D] tensor of zeros is written or read.  0 / 0 / NULL: dy is [ntok, D].
  * wpack: the TRANSPOSED weight streams of wmz_layer_fused_bwd_pack (wpack_ff: 163 840 + 32 768 bf16, wpack_qkv: 98 304 +
  * 32 768 bf16; the LayerNorm gammas are folded in).  Replaces wmz_linear_fwd x5 (dgrad / recompute) and wmz_layernorm_bwd
- * x2 per layer; the weight gradients stay wmz_linear_wgrad calls on the operands written here, computed against the
+ * x2 per layer; the weight gradients stay wmz_linear_wgrad_ws / _batch calls on the operands written here, computed against the
  * NORMALISED inputs, and wmz_ln_affine_grads turns such a raw gradient G[N, K] = dC^T xhat and s[N] = column sums of dC
  * (ntok must be a multiple of 32 for both kernels) into the parameter gradients: dW += G diag(gamma) + s beta^T, dbias[n - bias_from] += s[n] (n >= bias_from; NULL: no
  * bias), dgamma[k] += sum_n W[n,k] G[n,k], dbeta[k] += sum_n W[n,k] s[n]  (all fp32, accumulating). */
@@ -484,33 +475,27 @@ int wmz_ln_affine_grads_batch(int n, const float* const* G, const float* const* 
  * (wmz_bn_finalize) sums the replicas -- thousands of workgroups adding into ONE row is a chain of same-address atomics that
  * complete ~15 ns apart, 60-120 us behind a 70-200 us convolution. */
 #define WMZ_STAT_REPLICAS 8
-int wmz_conv2d_nhwc_fwd(const void* x, const void* w, void* out, const float* bias, const float* scale,
-                        const float* shift, const void* residual, float* stat_sum, float* stat_sq, int B, int Hi, int Wi,
-                        int Cin, int Cout, int KH, int KW, int stride, int pad, int leaky, float slope, int dtype,
-                        void* stream);
-/* The same with an INPUT prologue for 1x1 convolutions (KH = KW = 1, pad = 0): the A operand is LeakyReLU(x * in_scale[c]
- * + in_shift[c]) (slope in_slope), applied while the slab is staged -- the training-mode BatchNorm + activation in front
- * of the conv (autoencoder.py:21-25 Residual: conv3x3 -> BN -> LeakyReLU -> conv1x1) without a pass of its own. */
+/* in_scale / in_shift (optional, both or neither; 1x1 convolutions only: KH = KW = 1, pad = 0): an INPUT prologue -- the A
+ * operand is LeakyReLU(x * in_scale[c] + in_shift[c]) (slope in_slope), applied while the slab is staged: the training-mode
+ * BatchNorm + activation in front of the conv (autoencoder.py:21-25 Residual: conv3x3 -> BN -> LeakyReLU -> conv1x1) without
+ * a pass of its own. */
 int wmz_conv2d_nhwc_fwd_pre(const void* x, const void* w, void* out, const float* bias, const float* scale,
                             const float* shift, const void* residual, float* stat_sum, float* stat_sq,
                             const float* in_scale, const float* in_shift, float in_slope, int B, int Hi, int Wi, int Cin,
                             int Cout, int KH, int KW, int stride, int pad, int leaky, float slope, int dtype, void* stream);
-/* Direct 3x3 / stride 1 / pad 1 convolution in bf16 (csrc/conv_direct.hip; autoencoder.py:8-10 conv3x3 inside Residual :18-42,
- * UpscaleResidual :89-131 and the decoder's first / last convolutions :134-152): the same result as wmz_conv2d_nhwc_fwd on
- * these shapes (same k order, same epilogue arithmetic) with the haloed input patch and the weight stream staged by LDS-DMA.
- * wpack: the GEMM operand [Cout, 9 * Cin] re-ordered by wmz_conv3x3_direct_pack (wmz_conv3x3_direct_pack_elems(Cin, Cout) bf16
- * elements).  Shapes: wmz_conv3x3_direct_supported(H, W, Cin, Cout) != 0 -- Cin % 64 == 0, Cout % 8 == 0 and <= 128, W a
- * multiple of 32 with H % 8 == 0, or W = 16 with H % 16 == 0. */
+/* Direct 3x3 / pad 1 convolution in bf16 (csrc/conv_direct.hip; autoencoder.py:8-10 conv3x3 inside Residual :18-42,
+ * UpscaleResidual :89-131 and the decoder's first / last convolutions :134-152; at stride 2 the first convolution of the
+ * down-sampling Residual :27-33): the same result as wmz_conv2d_nhwc_fwd_pre on these shapes (same k order, same epilogue
+ * arithmetic) with the haloed input patch staged in LDS by DMA.  wpack: the GEMM operand [Cout, 9 * Cin] re-ordered by
+ * wmz_conv3x3_direct_pack (wmz_conv3x3_direct_pack_elems(Cin, Cout) bf16 elements), the same stream at both strides.  H, W: the
+ * INPUT plane.  Shapes: wmz_conv3x3_direct_supported_strided(H, W, Cin, Cout, stride) != 0 -- Cin = 64 or 128 and
+ *   stride 1: Cout % 8 == 0 and <= 128, W a multiple of 32 with H % 8 == 0, or W = 16 with H % 16 == 0;
+ *   stride 2: Cout = 128, H and W even, the output H / 2 x W / 2 in planes of 8 k x 16 m pixels (LeakyReLU slope in [0, 1]).
+ * wmz_conv3x3_direct_supported(H, W, Cin, Cout): the stride-1 answer alone. */
+int wmz_conv3x3_direct_supported_strided(int H, int W, int Cin, int Cout, int stride);
 int wmz_conv3x3_direct_supported(int H, int W, int Cin, int Cout);
 long wmz_conv3x3_direct_pack_elems(int Cin, int Cout);
 int wmz_conv3x3_direct_pack(const void* w_op, void* wpack, int Cin, int Cout, void* stream);
-int wmz_conv3x3_direct_fwd(const void* x, const void* wpack, void* out, const float* bias, const float* scale,
-                           const float* shift, const void* residual, float* stat_sum, float* stat_sq, int B, int H, int W,
-                           int Cin, int Cout, int leaky, float slope, void* stream);
-/* The same at stride 2 (pad 1; autoencoder.py:27-33, the first convolution of the down-sampling Residual): H, W the (even) INPUT
- * plane, the output H / 2 x W / 2; Cout = 128, output planes of 8 k x 16 m pixels; same packed weight stream.  stride == 1 is
- * wmz_conv3x3_direct_fwd. */
-int wmz_conv3x3_direct_supported_strided(int H, int W, int Cin, int Cout, int stride);
 int wmz_conv3x3_direct_fwd_strided(const void* x, const void* wpack, void* out, const float* bias, const float* scale,
                                    const float* shift, const void* residual, float* stat_sum, float* stat_sq, int B, int H, int W,
                                    int Cin, int Cout, int stride, int leaky, float slope, void* stream);
@@ -523,9 +508,6 @@ int wmz_conv3x3_direct_fwd_strided(const void* x, const void* wpack, void* out, 
 int wmz_conv_point_supported(int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad);
 long wmz_conv_point_pack_elems(int K, int Cout);
 int wmz_conv_point_pack(const void* w_op, void* wpack, int K, int Cout, void* stream);
-int wmz_conv_point_fwd(const void* x, const void* wpack, void* out, const float* bias, const float* scale, const float* shift,
-                       float* stat_sum, float* stat_sq, const float* in_scale, const float* in_shift, float in_slope, int B, int Hi,
-                       int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad, int leaky, float slope, void* stream);
 /* A training-mode nn.BatchNorm2d (autoencoder.py:21-25) handed to the kernel that APPLIES it as its raw batch statistics: that kernel
  * does what wmz_bn_finalize does -- same arithmetic -- while it sets up its per-channel constants, and one of its workgroups moves the
  * running statistics (momentum, unbiased variance), increments *num_batches_tracked and writes the optional outputs (scale / shift /
@@ -540,7 +522,8 @@ typedef struct wmz_bn_stats {
   float* mean; float* rstd;                         /* out [C], both or neither */
   double count, momentum, eps;
 } wmz_bn_stats;
-/* wmz_conv_point_fwd with the input prologue's BatchNorm given as raw statistics (in_bn; then in_scale = in_shift = NULL). */
+/* The input prologue (optional, 1x1 convolutions of <= 128 channels) is wmz_conv2d_nhwc_fwd_pre's, its BatchNorm given either as
+ * in_scale / in_shift or as raw statistics (in_bn; then in_scale = in_shift = NULL).  LeakyReLU slope in [0, 1]. */
 int wmz_conv_point_fwd_bn(const void* x, const void* wpack, void* out, const float* bias, const float* scale, const float* shift,
                           float* stat_sum, float* stat_sq, const float* in_scale, const float* in_shift, const wmz_bn_stats* in_bn,
                           float in_slope, int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad, int leaky,
@@ -574,11 +557,9 @@ int wmz_dilate_nhwc(const void* dy, void* dz, int B, int Ho, int Wo, int C, int 
 int wmz_bilinear2x_nhwc(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 
 /* ---- backward of the conv path (VQ-AE training, train_vqae.py:125-192; the reference gets these from autograd) ----
- * data gradient: wmz_conv2d_nhwc_fwd on the (zero-dilated for stride 2) output gradient with flipped, transposed weights.
- * weight gradient: dW[Cout, KH*KW*Cin] += dy^T . im2col(x) (implicit), dbias[Cout] += colsum(dy); fp32, accumulated. */
-int wmz_conv2d_nhwc_wgrad(const void* x, const void* dy, float* dW, float* dbias, int B, int Hi, int Wi, int Cin, int Cout,
-                          int KH, int KW, int stride, int pad, int dtype, void* stream);
-/* ... by the two-stage reduction of wmz_linear_wgrad_ws (caller-owned workspace of at least
+ * data gradient: wmz_conv2d_nhwc_fwd_pre on the (zero-dilated for stride 2) output gradient with flipped, transposed weights.
+ * weight gradient: dW[Cout, KH*KW*Cin] += dy^T . im2col(x) (implicit), dbias[Cout] += colsum(dy); fp32, by the two-stage
+ * reduction of wmz_linear_wgrad_ws (caller-owned workspace of at least
  * wmz_conv2d_nhwc_wgrad_workspace_floats(...) floats; deterministic, no float atomics; overwrite != 0: dW / dbias are stored,
  * not accumulated -- no zero fill needed).  conv_layout_co > 0: dW is nn.Conv2d's own weight (gradient) tensor
  * [conv_layout_co, conv_layout_ci, KH, KW] -- the channel padding of the operands cropped, the taps transposed -- and dbias has
@@ -598,26 +579,25 @@ int wmz_conv2d_nhwc_wgrad_batch(int n, const void* const* x, const void* const* 
                                 const int* conv_layout_ci, float* workspace, long workspace_floats, int dtype, void* stream);
 int wmz_conv2d_nhwc_wgrad_is_direct(int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad, int dtype);
 /* training-mode BatchNorm + LeakyReLU backward, pass 1: g = dy * act'(y) (optional g_out), sum_g[C] += g,
- * sum_gx[C] += g * (x - mean) * rstd;  pass 2: dx = gamma*rstd*(g - sum_g/M - xhat*sum_gx/M)  (dgamma = sum_gx, dbeta = sum_g). */
+ * sum_gx[C] += g * (x - mean) * rstd;  pass 2: dx = gamma*rstd*(g - sum_g/M - xhat*sum_gx/M) (+ add)  (dgamma = sum_gx,
+ * dbeta = sum_g).  add (optional, [M, C] in the activations' dtype): the gradient x receives from its other consumer -- a
+ * residual block's skip path (autoencoder.py:35-42, :119-131) -- summed by this pass instead of one of its own (the reference's
+ * autograd runs an add kernel there). */
 int wmz_bn_act_bwd_reduce(const void* x, const void* y, const void* dy, const float* mean, const float* rstd, void* g_out,
                           float* sum_g, float* sum_gx, long M, int C, int leaky, float slope, int dtype, void* stream);
-int wmz_bn_bwd_apply(const void* x, const void* g, const float* mean, const float* rstd, const float* gamma,
-                     const float* sum_g, const float* sum_gx, void* dx, long M, int C, int dtype, void* stream);
+int wmz_bn_bwd_apply_add(const void* x, const void* g, const float* mean, const float* rstd, const float* gamma,
+                         const float* sum_g, const float* sum_gx, const void* add, void* dx, long M, int C, int dtype,
+                         void* stream);
 /* Both of the above for y = LeakyReLU(BatchNorm_train(x)) WITHOUT a skip input (autoencoder.py:21-25 Residual's first
  * normalisation, :100-118 UpscaleResidual's two): the LeakyReLU mask is recomputed from x and the forward's (scale, shift) -- the
  * sign of fmaf(x, scale, shift), what wmz_affine_act_nhwc evaluated -- so the stored output is not read and g = dy * act'(y) is not
  * written: 5 tensor passes instead of 7.  dy: the gradient behind the activation; sum_g / sum_gx: fp32 [C], ZERO on entry,
- * receive dbeta / dgamma; dx = dL/dx.  Shapes: wmz_bn_leaky_bwd_supported(C, dtype) != 0 (the 16-byte kernels). */
+ * receive dbeta / dgamma; dx = dL/dx; add as wmz_bn_bwd_apply_add's.  Shapes: wmz_bn_leaky_bwd_supported(C, dtype) != 0 (the
+ * 16-byte kernels). */
 int wmz_bn_leaky_bwd_supported(int C, int dtype);
 int wmz_bn_leaky_bwd(const void* x, const void* dy, const float* scale, const float* shift, const float* mean,
                      const float* rstd, const float* gamma, float* sum_g, float* sum_gx, const void* add, void* dx, long M, int C,
                      float slope, int dtype, void* stream);
-/* wmz_bn_bwd_apply with dx += add (optional, [M, C] in the activations' dtype): the gradient x receives from its other consumer --
- * a residual block's skip path (autoencoder.py:35-42, :119-131) -- summed by this pass instead of one of its own (the reference's
- * autograd runs an add kernel there); wmz_bn_leaky_bwd's `add` is the same. */
-int wmz_bn_bwd_apply_add(const void* x, const void* g, const float* mean, const float* rstd, const float* gamma,
-                         const float* sum_g, const float* sum_gx, const void* add, void* dx, long M, int C, int dtype,
-                         void* stream);
 /* adjoint of wmz_bilinear2x_nhwc (gather form, deterministic): dy [B,2H,2W,C] -> dx [B,H,W,C]. */
 int wmz_bilinear2x_nhwc_bwd(const void* dy, void* dx, int B, int H, int W, int C, int dtype, void* stream);
 

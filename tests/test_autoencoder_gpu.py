@@ -528,9 +528,9 @@ def test_training_elementwise_kernels_vector_and_scalar_forms(wmz, C, dtype):
 @pytest.mark.gpu
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 def test_conv_operands_bulk_refresh_equals_the_tensor_op_builds(wmz, dtype):
-    """_cast.ConvOperands (wmz_conv_operands_refresh: every conv layer's forward and data-gradient GEMM operands by one launch)
-    == autoencoder._w_op / _wT_op's permute / pad / flip / cast builds, bit for bit, incl. channel counts that are not multiples
-    of 8 (the RGB input, an odd width) and 1x1 / 3x3 / 4x4 taps; afterwards the cache serves them without a rebuild."""
+    """_cast.ConvOperands (wmz_conv_operands_refresh_packed: every conv layer's forward and data-gradient GEMM operands by one
+    launch) == autoencoder._w_op / _wT_op's permute / pad / flip / cast builds, bit for bit, incl. channel counts that are not
+    multiples of 8 (the RGB input, an odd width) and 1x1 / 3x3 / 4x4 taps; afterwards the cache serves them without a rebuild."""
     from world_modelz_amd import _cast, autoencoder
     torch.manual_seed(3)
     convs = [torch.nn.Conv2d(3, 32, 4, 2, 1), torch.nn.Conv2d(32, 20, 3, 1, 1), torch.nn.Conv2d(20, 64, 1), torch.nn.Conv2d(64, 3, 3, 1, 1)]

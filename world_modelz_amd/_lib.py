@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('WMZ_LIB_PATH') or os.path.join(_HERE, 'libwmz_hip.so')    # override: kernel A/B builds (tools/)
 
 WMZ_F32, WMZ_BF16, WMZ_F16 = 0, 1, 2
-EXPECTED_VERSION = 113      # include/wmz.h WMZ_VERSION: bumped with every ABI change; lib() refuses another build
+EXPECTED_VERSION = 114      # include/wmz.h WMZ_VERSION: bumped with every ABI change; lib() refuses another build
 WMZ_LIN_GELU = 1
 WMZ_LIN_GELU_IN = 2
 WMZ_LIN_DGELU = 4
@@ -28,8 +28,6 @@ SIGNATURES = {
     'wmz_debug_attn_knobs': [c_int, c_int],
     'wmz_debug_linear_knobs': [c_int],
     'wmz_local3d_attn_bwd': [c_void_p] * 10 + [c_int] * 9 + [c_long] * 8 + [c_int, c_void_p],
-    'wmz_linear_wgrad': [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
-                        + [c_int, c_int, c_void_p],
     'wmz_linear_wgrad_workspace_floats': [c_int, c_int, c_int, c_int],      # returns long (restype set in lib())
     'wmz_linear_wgrad_ws': [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
                            + [c_int, c_int, c_void_p, c_long, c_int, c_void_p],
@@ -59,7 +57,6 @@ SIGNATURES = {
     'wmz_debug_stamp': [c_void_p, c_int, c_void_p],
     'wmz_layer_fused_fwd': [c_void_p] * 7 + [c_int] * 6 + [c_float, c_void_p],
     'wmz_operands_refresh': [c_void_p] * 7 + [c_int, c_void_p],
-    'wmz_conv_operands_refresh': [c_void_p] * 6 + [c_int, c_int, c_void_p],
     'wmz_conv_operands_refresh_packed': [c_void_p] * 7 + [c_int, c_int, c_void_p],
     'wmz_layer_fused_pack': [c_void_p] * 16 + [c_int] * 3 + [c_void_p],
     'wmz_layer_fused_fwd_train': [c_void_p] * 12 + [c_int] * 7 + [c_float, c_void_p],
@@ -80,18 +77,15 @@ SIGNATURES = {
     'wmz_chain_qkv_bwd': [c_void_p] * 7 + [c_long] + [c_int] * 2 + [c_void_p],
     'wmz_local3d_attn_fwd_planes': [c_void_p] * 5 + [c_int] * 9 + [c_long] * 4 + [c_int, c_int, c_int, c_void_p],
     'wmz_embed_qkv_fused_fwd': [c_void_p] * 10 + [c_int] * 8 + [c_float, c_void_p],
-    'wmz_conv2d_nhwc_fwd': [c_void_p] * 9 + [c_int] * 10 + [c_float, c_int, c_void_p],
     'wmz_conv2d_nhwc_fwd_pre': [c_void_p] * 11 + [c_float] + [c_int] * 10 + [c_float, c_int, c_void_p],
     'wmz_conv3x3_direct_supported': [c_int] * 4,
     'wmz_conv3x3_direct_pack_elems': [c_int, c_int],                       # returns long
     'wmz_conv3x3_direct_pack': [c_void_p, c_void_p, c_int, c_int, c_void_p],
-    'wmz_conv3x3_direct_fwd': [c_void_p] * 9 + [c_int] * 6 + [c_float, c_void_p],
     'wmz_conv3x3_direct_supported_strided': [c_int] * 5,
     'wmz_conv3x3_direct_fwd_strided': [c_void_p] * 9 + [c_int] * 7 + [c_float, c_void_p],
     'wmz_conv_point_supported': [c_int] * 9,
     'wmz_conv_point_pack_elems': [c_int, c_int],                           # returns long
     'wmz_conv_point_pack': [c_void_p, c_void_p, c_int, c_int, c_void_p],
-    'wmz_conv_point_fwd': [c_void_p] * 10 + [c_float] + [c_int] * 10 + [c_float, c_void_p],
     'wmz_conv_point_fwd_bn': [c_void_p] * 11 + [c_float] + [c_int] * 10 + [c_float, c_void_p],      # (.., in_shift, const wmz_bn_stats*, in_slope, ..)
     'wmz_affine_act_bn_supported': [c_int, c_int],
     'wmz_dilate_nhwc': [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p],
@@ -102,11 +96,9 @@ SIGNATURES = {
     'wmz_channel_stats_nhwc': [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p],
     'wmz_bn_finalize': [c_void_p, c_void_p, c_double] + [c_void_p] * 4 + [c_double, c_double, c_int] + [c_void_p] * 4
                        + [c_int, c_void_p, c_void_p],
-    'wmz_conv2d_nhwc_wgrad': [c_void_p] * 4 + [c_int] * 10 + [c_void_p],
     'wmz_conv2d_nhwc_wgrad_workspace_floats': [c_int] * 10,                # returns long
     'wmz_conv2d_nhwc_wgrad_ws': [c_void_p] * 4 + [c_int] * 12 + [c_void_p, c_long, c_int, c_void_p],
     'wmz_bn_act_bwd_reduce': [c_void_p] * 8 + [c_long, c_int, c_int, c_float, c_int, c_void_p],
-    'wmz_bn_bwd_apply': [c_void_p] * 8 + [c_long, c_int, c_int, c_void_p],
     'wmz_bn_leaky_bwd_supported': [c_int, c_int],
     'wmz_bn_leaky_bwd': [c_void_p] * 11 + [c_long, c_int, c_float, c_int, c_void_p],
     'wmz_bn_bwd_apply_add': [c_void_p] * 9 + [c_long, c_int, c_int, c_void_p],

@@ -343,14 +343,14 @@ extern "C" int wmz_conv_point_fwd_bn(const void* x, const void* wpack, void* out
                                      float* stat_sum, float* stat_sq, const float* in_scale, const float* in_shift,
                                      const wmz_bn_stats* in_bn, float in_slope, int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW,
                                      int stride, int pad, int leaky, float slope, void* stream) {
-  WMZ_REQUIRE(x && wpack && out, "wmz_conv_point_fwd: null tensor");
-  WMZ_REQUIRE(wmz_conv_point_supported(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad), "wmz_conv_point_fwd: unsupported shape (wmz_conv_point_supported)");
-  WMZ_REQUIRE((stat_sum == nullptr) == (stat_sq == nullptr), "wmz_conv_point_fwd: stat_sum and stat_sq go together");
-  WMZ_REQUIRE((scale == nullptr) == (shift == nullptr), "wmz_conv_point_fwd: scale and shift go together");
-  WMZ_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "wmz_conv_point_fwd: in_scale and in_shift go together");
+  WMZ_REQUIRE(x && wpack && out, "wmz_conv_point_fwd_bn: null tensor");
+  WMZ_REQUIRE(wmz_conv_point_supported(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad), "wmz_conv_point_fwd_bn: unsupported shape (wmz_conv_point_supported)");
+  WMZ_REQUIRE((stat_sum == nullptr) == (stat_sq == nullptr), "wmz_conv_point_fwd_bn: stat_sum and stat_sq go together");
+  WMZ_REQUIRE((scale == nullptr) == (shift == nullptr), "wmz_conv_point_fwd_bn: scale and shift go together");
+  WMZ_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "wmz_conv_point_fwd_bn: in_scale and in_shift go together");
   WMZ_REQUIRE(bn_stats_ok(in_bn) && (in_bn == nullptr || in_scale == nullptr), "wmz_conv_point_fwd_bn: incomplete wmz_bn_stats (or both prologue forms given)");
-  WMZ_REQUIRE((in_scale == nullptr && in_bn == nullptr) || (KH == 1 && KW == 1 && pad == 0 && Cin <= 128), "wmz_conv_point_fwd: the input prologue is built for 1x1 convolutions of <= 128 channels");
-  WMZ_REQUIRE(slope >= 0.f && slope <= 1.f, "wmz_conv_point_fwd: LeakyReLU slope in [0, 1] expected");
+  WMZ_REQUIRE((in_scale == nullptr && in_bn == nullptr) || (KH == 1 && KW == 1 && pad == 0 && Cin <= 128), "wmz_conv_point_fwd_bn: the input prologue is built for 1x1 convolutions of <= 128 channels");
+  WMZ_REQUIRE(slope >= 0.f && slope <= 1.f, "wmz_conv_point_fwd_bn: LeakyReLU slope in [0, 1] expected");
   PointParams P;
   P.x = (const bf16_t*)x; P.wpack = (const bf16_t*)wpack; P.out = (bf16_t*)out;
   P.bias = bias; P.scale = scale; P.shift = shift; P.stat_sum = stat_sum; P.stat_sq = stat_sq;
@@ -385,16 +385,8 @@ extern "C" int wmz_conv_point_fwd_bn(const void* x, const void* wpack, void* out
     if (padded) hipLaunchKernelGGL((convp_kernel<4, 1, true>), dim3(grid), dim3(256), lds_bytes, st, P);
     else hipLaunchKernelGGL((convp_kernel<4, 1, false>), dim3(grid), dim3(256), lds_bytes, st, P);
   }
-  WMZ_LAUNCH_CHECK("wmz_conv_point_fwd");
+  WMZ_LAUNCH_CHECK("wmz_conv_point_fwd_bn");
   return WMZ_OK;
-}
-
-extern "C" int wmz_conv_point_fwd(const void* x, const void* wpack, void* out, const float* bias, const float* scale, const float* shift,
-                                  float* stat_sum, float* stat_sq, const float* in_scale, const float* in_shift, float in_slope, int B,
-                                  int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad, int leaky, float slope,
-                                  void* stream) {
-  return wmz_conv_point_fwd_bn(x, wpack, out, bias, scale, shift, stat_sum, stat_sq, in_scale, in_shift, nullptr, in_slope, B, Hi, Wi, Cin,
-                               Cout, KH, KW, stride, pad, leaky, slope, stream);
 }
 
 extern "C" int wmz_nchw_to_nhwc8(const void* x, void* y, int B, int C, int H, int W, int in_dtype, int out_dtype, void* stream) {

@@ -1,5 +1,6 @@
 // Backward pieces of the nn.Linear / PreNorm-LayerNorm family (the reference gets these from autograd):
-//   wmz_linear_wgrad    dW[N,K] += dC[M,N]^T . A'[M,K],  dbias[N] += colsum(dC)      A' = A | LN(A) | GELU(A)
+//   wmz_linear_wgrad_ws / _batch / _batch_ln
+//                       dW[N,K] += dC[M,N]^T . A'[M,K],  dbias[N] += colsum(dC)      A' = A | LN(A) | GELU(A)
 //   wmz_layernorm_stats mean / rstd per row
 //   wmz_layernorm_bwd   dx = LN'(x)^T dyhat (+ skip gradient),  dgamma, dbeta
 // (the data gradient dA' = dC . W is wmz_linear_fwd on the transposed weight, optionally x gelu'(z).)
@@ -41,9 +42,9 @@ template <> __device__ __forceinline__ i32x4 pack_chunk<bf16_t>(const float* f) 
 }
 
 // ------------------------------------------------------------------------------------------------ wgrad
-// Output tile 128 (n) x 128 (k') per workgroup, reduction over a slice of M in steps of 32 rows.  Both operands are
-// "m-major" in memory, so both tiles are staged row = m and read as TRANSPOSED fragments (8 consecutive m of one column):
-// bf16 through ds_read_b64_tr_b16 from a 64-byte-granule swizzled image, fp32 as scalar reads.
+// Output tile 128 (n) x 128 (k') per workgroup, reduction over a slice of M.  Both operands are "m-major" in memory, so both
+// tiles are staged row = m and read as TRANSPOSED fragments (8 consecutive m of one column): bf16 through ds_read_b64_tr_b16
+// from a 64-byte-granule swizzled image, fp32 as scalar reads.
 struct WgParams {
   const void* dC; long ldc;
   const void* A; long lda;
@@ -69,7 +70,7 @@ struct RedProb {
 };
 struct RedBatch { RedProb p[WG_MAXB]; int n; };
 
-constexpr int WG_BN = 128, WG_BK = 128, WG_MS = 32;
+constexpr int WG_BN = 128, WG_BK = 128;
 
 template <typename T> __device__ __forceinline__ int wswz(int r) { return sizeof(T) == 2 ? ((r & 3) << 6) : 0; }
 
@@ -92,135 +93,12 @@ __device__ __forceinline__ void wg_col_frag(Frag8<T>& f, const char* img, int m0
   }
 }
 
-template <typename T, int PRO>   // PRO: 0 raw A, 1 LN(A) from mean/rstd/gamma/beta, 2 GELU(A), 3 implicit im2col of NHWC x
-__global__ __launch_bounds__(NT, 2) void wgrad_kernel(WgParams P) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  constexpr int ROWB = WG_BN * (int)sizeof(T);
-  constexpr int CPR = ROWB / 16;                       // chunks per tile row: 16 (bf16) / 32 (f32)
-  constexpr int PER_T = WG_MS * CPR / NT;              // chunks per thread per tile: 2 / 4
-  __shared__ __attribute__((aligned(16))) char Cs[WG_MS * ROWB];
-  __shared__ __attribute__((aligned(16))) char As[WG_MS * ROWB];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);          // the tiles of one slice of M share an XCD: its L2 serves the operands' re-reads
-  const int bk = bid % P.nbk; bid /= P.nbk;
-  const int bn = bid % P.nbn; bid /= P.nbn;
-  const int split = bid;
-  const int n0 = bn * WG_BN, k0 = bk * WG_BK;
-  const int m_begin = split * P.rows_per_wg, m_end = min(P.M, m_begin + P.rows_per_wg);
-  const T* dC = reinterpret_cast<const T*>(P.dC);
-  const T* A = reinterpret_cast<const T*>(P.A);
-
-  i32x4 rc[PER_T], ra[PER_T];
-  auto fetch = [&](int m0) {
-#pragma unroll
-    for (int it = 0; it < PER_T; ++it) {
-      const int idx = tid + it * NT;
-      const int r = idx / CPR, c = idx - r * CPR;
-      const int m = m0 + r;
-      rc[it] = (i32x4)(0);
-      ra[it] = (i32x4)(0);
-      if (m < m_end) {
-        if (n0 + c * EPC < P.N) rc[it] = *reinterpret_cast<const i32x4*>(dC + (long)m * P.ldc + n0 + c * EPC);
-        if constexpr (PRO == 3) {
-          const int k = k0 + c * EPC;
-          if (k < P.K) {
-            const int tap = k / P.Cin, ci = k - tap * P.Cin;
-            const int kh = tap / P.KW, kw = tap - kh * P.KW;
-            const int wo = m % P.Wo, t = m / P.Wo;
-            const int ho = t % P.Ho, b = t / P.Ho;
-            const int hi = ho * P.cstride - P.cpad + kh, wi = wo * P.cstride - P.cpad + kw;
-            if (hi >= 0 && hi < P.Hi && wi >= 0 && wi < P.Wi)
-              ra[it] = *reinterpret_cast<const i32x4*>(A + (((long)b * P.Hi + hi) * P.Wi + wi) * P.Cin + ci);
-          }
-        } else if (k0 + c * EPC < P.K) {
-          i32x4 v = *reinterpret_cast<const i32x4*>(A + (long)m * P.lda + k0 + c * EPC);
-          if constexpr (PRO == 1 || PRO == 2) {
-            float f[EPC];
-            unpack_chunk<T>(v, f);
-            if constexpr (PRO == 1) {
-              const float mu = P.mean[m], rs = P.rstd[m];
-#pragma unroll
-              for (int e = 0; e < EPC; ++e) f[e] = (f[e] - mu) * rs * P.gamma[k0 + c * EPC + e] + P.beta[k0 + c * EPC + e];
-            } else {
-#pragma unroll
-              for (int e = 0; e < EPC; ++e) f[e] = gelu_erf(f[e]);
-            }
-            v = pack_chunk<T>(f);
-          }
-          ra[it] = v;
-        }
-      }
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x16)(0.f);
-  float bsum = 0.f;                                    // threads 0..127 of the bk == 0 workgroups: column sums of dC
-  const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
-
-  if (m_begin < m_end) fetch(m_begin);
-  for (int m0 = m_begin; m0 < m_end; m0 += WG_MS) {
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < PER_T; ++it) {
-      const int idx = tid + it * NT;
-      const int r = idx / CPR, c = idx - r * CPR;
-      const int off = r * ROWB + ((c << 4) ^ wswz<T>(r));
-      *reinterpret_cast<i32x4*>(Cs + off) = rc[it];
-      *reinterpret_cast<i32x4*>(As + off) = ra[it];
-    }
-    __syncthreads();
-    if (m0 + WG_MS < m_end) fetch(m0 + WG_MS);
-    if (P.dbias != nullptr && bk == 0 && tid < WG_BN) {
-#pragma unroll 8
-      for (int r = 0; r < WG_MS; ++r) {
-        const char* p = Cs + r * ROWB + ((tid * (int)sizeof(T)) ^ wswz<T>(r));
-        bsum += Elem<T>::to_f32(*reinterpret_cast<const T*>(p));
-      }
-    }
-#pragma unroll
-    for (int ms = 0; ms < WG_MS; ms += 16) {
-      Frag8<T> cf[2], af[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        wg_col_frag<T>(cf[i], Cs, ms, wn + 32 * i, lane);
-        wg_col_frag<T>(af[i], As, ms, wk + 32 * i, lane);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) mma32(acc[i][j], cf[i], af[j]);
-    }
-  }
-
-  // D: row (n) = (reg&3) + 8*(reg>>2) + 4*(lane>>5), col (k') = lane&31
-  const int l31 = lane & 31, hh = lane >> 5;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int kc = k0 + wk + 32 * j + l31;
-      if (kc >= P.K) continue;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int n = n0 + wn + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        if (n < P.N) atomicAdd(P.dW + (long)n * P.K + kc, acc[i][j][reg]);
-      }
-    }
-  if (P.dbias != nullptr && bk == 0 && tid < WG_BN && n0 + tid < P.N) atomicAdd(P.dbias + n0 + tid, bsum);
-}
-
-
-// ---- wgrad, version 2: the same 128 x 128 output tile and operand handling, but
+// ---- wgrad2_kernel:
 //   * slabs of 64 rows (bf16; 32 for fp32) in a DOUBLE-buffered LDS image: one barrier per slab and 16 MFMAs per wave
-//     between two barriers (version 1: two barriers around 8 MFMAs);
-//   * the slices of M do not meet in float atomics (version 1: 64 KB of same-address atomics per workgroup, all at the end,
-//     serialised memory-side) but in a workspace [split][N][K] (+ [split][N] for the bias) that wgrad_reduce_kernel sums
-//     into dW / dbias: two-stage reduction, deterministic summation order.
+//     between two barriers;
+//   * the slices of M do not meet in float atomics (64 KB of same-address atomics per workgroup, all at the end, serialised
+//     memory-side) but in a workspace [split][N][K] (+ [split][N] for the bias) that wgrad_reduce_kernel sums into
+//     dW / dbias: two-stage reduction, deterministic summation order.
 template <typename T> struct W2 { static constexpr int MS = sizeof(T) == 2 ? 64 : 32; };
 
 template <typename T, int PRO>
@@ -429,7 +307,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgBatch B, float* __restr
 // to cross a ~1.5 us round trip -- the ablations added up, 88 us of streaming + 92 us of multiply = 181 us at dim 384).  LDS reads
 // are inline asm with hand-counted waits (hipcc drains the DMA ring in front of every LDS read it can see); fragments of the
 // next 16-row step are read while the MFMAs of this one run, across slab boundaries too.  The partial tiles go through the same
-// workspace layout and reduction kernel as version 2's.
+// workspace layout and reduction kernel as wgrad2_kernel's.
 constexpr int W3_NT = 512, W3_T = 256, W3_MS = 64, W3_ROWB = W3_T * 2;
 constexpr int W3_SL = 32, W3_SIMG = W3_SL * W3_ROWB, W3_BUF = 2 * W3_SIMG;     // 16 KB per operand image, 32 KB per ring buffer
 #ifndef WMZ_W3_NBUF
@@ -1025,40 +903,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_small_kernel(const float* __
 
 }  // namespace
 
-extern "C" int wmz_linear_wgrad(const void* dC, long ldc, const void* A, long lda, float* dW, float* dbias, int M, int N,
-                                int K, const float* ln_gamma, const float* ln_beta, const float* ln_mean,
-                                const float* ln_rstd, int gelu_in, int dtype, void* stream) {
-  WMZ_REQUIRE(dC && A && dW, "wmz_linear_wgrad: null tensor");
-  WMZ_REQUIRE(M > 0 && N > 0 && K > 0, "wmz_linear_wgrad: bad shape");
-  WMZ_REQUIRE(N % 8 == 0 && K % 8 == 0 && ldc % 8 == 0 && lda % 8 == 0, "wmz_linear_wgrad: N, K and row strides must be multiples of 8");
-  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_linear_wgrad: bad dtype %d", dtype);
-  const bool ln = ln_gamma != nullptr;
-  WMZ_REQUIRE(!ln || (ln_beta && ln_mean && ln_rstd), "wmz_linear_wgrad: LayerNorm prologue needs gamma, beta, mean, rstd");
-  WMZ_REQUIRE(!(ln && gelu_in), "wmz_linear_wgrad: LayerNorm and GELU prologues are exclusive");
-  WgParams P;
-  P.dC = dC; P.ldc = ldc; P.A = A; P.lda = lda; P.dW = dW; P.dbias = dbias; P.M = M; P.N = N; P.K = K;
-  P.gamma = ln_gamma; P.beta = ln_beta; P.mean = ln_mean; P.rstd = ln_rstd; P.gelu_in = gelu_in;
-  P.Hi = P.Wi = P.Cin = P.Ho = P.Wo = P.KW = P.cstride = P.cpad = 0;
-  P.nbn = wmz_cdiv(N, WG_BN); P.nbk = wmz_cdiv(K, WG_BK); P.nsplit = 0; P.direct = 0;
-  const int tiles = P.nbn * P.nbk;
-  constexpr int wg_target = 256;             // ~one workgroup per CU (measured optimum)
-  int split = wmz_cdiv(wg_target, tiles);    // ~one workgroup per CU: every extra split is another 64 KB of float atomics
-  const int max_split = wmz_cdiv(M, 4 * WG_MS);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  P.rows_per_wg = wmz_cdiv(wmz_cdiv(M, split), WG_MS) * WG_MS;
-  split = wmz_cdiv(M, P.rows_per_wg);
-  dim3 grid((unsigned)(tiles * split)), block(NT);
-  hipStream_t st = (hipStream_t)stream;
-  const int pro = ln ? 1 : (gelu_in ? 2 : 0);
-#define WMZ_WG(T, PRO) hipLaunchKernelGGL((wgrad_kernel<T, PRO>), grid, block, 0, st, P)
-  if (dtype == WMZ_BF16) { if (pro == 1) WMZ_WG(bf16_t, 1); else if (pro == 2) WMZ_WG(bf16_t, 2); else WMZ_WG(bf16_t, 0); }
-  else { if (pro == 1) WMZ_WG(float, 1); else if (pro == 2) WMZ_WG(float, 2); else WMZ_WG(float, 0); }
-#undef WMZ_WG
-  WMZ_LAUNCH_CHECK("wmz_linear_wgrad");
-  return WMZ_OK;
-}
-
 // slices of M for a wgrad of these sizes (shared by the launch and by the workspace query)
 // target of workgroups per problem (set by the entry points around their own launches; host-side, single stream of calls):
 // a batch of n problems fills the chip together, and every slice a problem does NOT have is 2 x N x K x 4 bytes of partial
@@ -1241,7 +1085,7 @@ static int wgrad_batch_plain(int n, const void* const* dC, const long* ldc, cons
       WMZ_LAUNCH_CHECK("wmz_linear_wgrad_batch");
       return WMZ_OK;
     }
-    // (workspace sized for version 2's slicing only: fall through to it -- rebuild the tables)
+    // (workspace sized for wgrad2_kernel's slicing only: fall through to it -- rebuild the tables)
     off = 0;
     for (int i = 0; i < n; ++i) {
       const int tiled = a_tiled != nullptr && a_tiled[i] != 0;
@@ -1349,39 +1193,9 @@ extern "C" int wmz_linear_wgrad_batch_ln(int n, const void* const* dC, const lon
   return WMZ_OK;
 }
 
-extern "C" int wmz_conv2d_nhwc_wgrad(const void* x, const void* dy, float* dW, float* dbias, int B, int Hi, int Wi, int Cin,
-                                     int Cout, int KH, int KW, int stride, int pad, int dtype, void* stream) {
-  WMZ_REQUIRE(x && dy && dW, "wmz_conv2d_nhwc_wgrad: null tensor");
-  WMZ_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0, "wmz_conv2d_nhwc_wgrad: bad shape");
-  WMZ_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "wmz_conv2d_nhwc_wgrad: Cin and Cout must be multiples of 8 (zero-pad)");
-  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_conv2d_nhwc_wgrad: bad dtype %d", dtype);
-  WgParams P;
-  P.Hi = Hi; P.Wi = Wi; P.Cin = Cin; P.KW = KW; P.cstride = stride; P.cpad = pad;
-  P.Ho = (Hi + 2 * pad - KH) / stride + 1;
-  P.Wo = (Wi + 2 * pad - KW) / stride + 1;
-  WMZ_REQUIRE(P.Ho > 0 && P.Wo > 0, "wmz_conv2d_nhwc_wgrad: empty output");
-  P.dC = dy; P.ldc = Cout; P.A = x; P.lda = 0; P.dW = dW; P.dbias = dbias;
-  P.M = B * P.Ho * P.Wo; P.N = Cout; P.K = KH * KW * Cin;
-  P.gamma = P.beta = P.mean = P.rstd = nullptr; P.gelu_in = 0;
-  P.nbn = wmz_cdiv(P.N, WG_BN); P.nbk = wmz_cdiv(P.K, WG_BK); P.nsplit = 0; P.direct = 0;
-  const int tiles = P.nbn * P.nbk;
-  int split = wmz_cdiv(256, tiles);
-  const int max_split = wmz_cdiv(P.M, 4 * WG_MS);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  P.rows_per_wg = wmz_cdiv(wmz_cdiv(P.M, split), WG_MS) * WG_MS;
-  split = wmz_cdiv(P.M, P.rows_per_wg);
-  dim3 grid((unsigned)(tiles * split)), block(NT);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 3>), grid, block, 0, st, P);
-  else hipLaunchKernelGGL((wgrad_kernel<float, 3>), grid, block, 0, st, P);
-  WMZ_LAUNCH_CHECK("wmz_conv2d_nhwc_wgrad");
-  return WMZ_OK;
-}
-
-// The same gradient by the two-stage reduction of wmz_linear_wgrad_ws (partial tiles in a caller-owned workspace, summed in a
-// fixed order): no float atomics -- the split-K atomics above are chains of ~30 same-address adds per element of dW (93 us per
-// call on the VQ-AE's 3x3 layers) --, and `overwrite` saves the caller the zero fill.
+// The weight gradient of a conv2d on NHWC x (implicit im2col) by the two-stage reduction of wmz_linear_wgrad_ws (partial tiles
+// in a caller-owned workspace, summed in a fixed order): no float atomics -- split-K atomics are chains of ~30 same-address adds
+// per element of dW (93 us per call on the VQ-AE's 3x3 layers) --, and `overwrite` saves the caller the zero fill.
 extern "C" long wmz_conv2d_nhwc_wgrad_workspace_floats(int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride,
                                                        int pad, int dtype) {
   const int Ho = (Hi + 2 * pad - KH) / stride + 1, Wo = (Wi + 2 * pad - KW) / stride + 1;

@@ -122,29 +122,24 @@ __global__ __launch_bounds__(256) void conv_operands_refresh_kernel(ConvOpTable 
 
 }  // namespace
 
-extern "C" int wmz_conv_operands_refresh(const void* const* weight, void* const* dst, const int* co, const int* ci, const int* kk,
-                                         const int* mode, int n, int dtype, void* stream) {
-  return wmz_conv_operands_refresh_packed(weight, dst, co, ci, kk, mode, nullptr, n, dtype, stream);
-}
-
 extern "C" int wmz_conv_operands_refresh_packed(const void* const* weight, void* const* dst, const int* co, const int* ci, const int* kk,
                                                 const int* mode, const int* pack, int n, int dtype, void* stream) {
-  WMZ_REQUIRE(n >= 0 && n <= 48, "wmz_conv_operands_refresh: at most 48 operands per call (got %d)", n);
+  WMZ_REQUIRE(n >= 0 && n <= 48, "wmz_conv_operands_refresh_packed: at most 48 operands per call (got %d)", n);
   if (n == 0) return WMZ_OK;
-  WMZ_REQUIRE(weight && dst && co && ci && kk && mode, "wmz_conv_operands_refresh: null table");
-  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_conv_operands_refresh: bad dtype %d", dtype);
+  WMZ_REQUIRE(weight && dst && co && ci && kk && mode, "wmz_conv_operands_refresh_packed: null table");
+  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_conv_operands_refresh_packed: bad dtype %d", dtype);
   ConvOpTable T;
   long off = 0;
   for (int i = 0; i < n; ++i) {
-    WMZ_REQUIRE(weight[i] && dst[i] && co[i] > 0 && ci[i] > 0 && kk[i] > 0 && (mode[i] == 0 || mode[i] == 1), "wmz_conv_operands_refresh: bad entry %d", i);
+    WMZ_REQUIRE(weight[i] && dst[i] && co[i] > 0 && ci[i] > 0 && kk[i] > 0 && (mode[i] == 0 || mode[i] == 1), "wmz_conv_operands_refresh_packed: bad entry %d", i);
     const int ci8 = (ci[i] + 7) & ~7, co8 = (co[i] + 7) & ~7;
     T.d[i].w = (const float*)weight[i]; T.d[i].dst = dst[i]; T.d[i].co = co[i]; T.d[i].ci = ci[i]; T.d[i].kk = kk[i];
     T.d[i].mode = mode[i]; T.d[i].f32 = dtype == WMZ_F32; T.d[i].start = off;
     T.d[i].pack = pack ? pack[i] : 0;
-    WMZ_REQUIRE(T.d[i].pack >= 0 && T.d[i].pack <= 2 && (T.d[i].pack == 0 || dtype == WMZ_BF16), "wmz_conv_operands_refresh: bad pack kind in entry %d", i);
+    WMZ_REQUIRE(T.d[i].pack >= 0 && T.d[i].pack <= 2 && (T.d[i].pack == 0 || dtype == WMZ_BF16), "wmz_conv_operands_refresh_packed: bad pack kind in entry %d", i);
     const int prows = mode[i] == 0 ? co8 : ci8, pkin = mode[i] == 0 ? ci8 : co8;
-    WMZ_REQUIRE(T.d[i].pack == 0 || prows <= 128, "wmz_conv_operands_refresh: packed operands have at most 128 rows (entry %d)", i);
-    WMZ_REQUIRE(T.d[i].pack != 1 || (kk[i] == 9 && (pkin == 64 || pkin == 128)), "wmz_conv_operands_refresh: entry %d is not a direct 3x3 shape", i);
+    WMZ_REQUIRE(T.d[i].pack == 0 || prows <= 128, "wmz_conv_operands_refresh_packed: packed operands have at most 128 rows (entry %d)", i);
+    WMZ_REQUIRE(T.d[i].pack != 1 || (kk[i] == 9 && (pkin == 64 || pkin == 128)), "wmz_conv_operands_refresh_packed: entry %d is not a direct 3x3 shape", i);
     if (T.d[i].pack == 1) T.d[i].count = (long)9 * pkin * (prows <= 64 ? 2 : 4) * 32;
     else if (T.d[i].pack == 2) T.d[i].count = (long)((kk[i] * pkin + 63) / 64) * 64 * (prows <= 64 ? 2 : 4) * 32;
     else
@@ -154,7 +149,7 @@ extern "C" int wmz_conv_operands_refresh_packed(const void* const* weight, void*
   T.n = n; T.total = off;
   const long blocks = (off + 255) / 256;
   hipLaunchKernelGGL(conv_operands_refresh_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, T);
-  WMZ_LAUNCH_CHECK("wmz_conv_operands_refresh");
+  WMZ_LAUNCH_CHECK("wmz_conv_operands_refresh_packed");
   return WMZ_OK;
 }
 

@@ -743,13 +743,9 @@ def _run_chain(tr, z, cone, out):
         n_in, n_q = src[l], need[l]
         heads, ext = attn.fn.heads, attn.fn.extents
         o = torch.empty((B, n_q, H, W, I_), dtype=bf, device=dev)
-        if ops._profile_hook is not None:
-            ops._profile_hook('wmz_local3d_attn_fwd', True)
         L.call('wmz_local3d_attn_fwd_planes', L.ptr(q), L.ptr(kv[0]), L.ptr(kv[1]), L.ptr(o), None,
                B, n_in, H, W, heads, I_ // heads, int(ext[0]), int(ext[1]), int(ext[2]), I_, I_, I_, I_,
                n_in - n_q, n_q, L.dtype_code(bf), L.stream())
-        if ops._profile_hook is not None:
-            ops._profile_hook('wmz_local3d_attn_fwd', False)
         tail = layers[l + 1] if l + 1 < depth else None
         wpack, vec = _layer_pack((attn, ff), tail, bf)
         xo = out if (tail is None and out is not None) else torch.empty((B, n_q, H, W, D_), dtype=bf, device=dev)

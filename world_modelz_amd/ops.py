@@ -7,15 +7,6 @@ import torch
 
 from . import _lib as L
 
-_profile_hook = None
-
-
-def set_profile_hook(fn):
-    """fn(kernel_name, is_start) is called right before / after a launch is enqueued (bench.py uses it to
-    bracket one kernel with HIP events on the launch stream)."""
-    global _profile_hook
-    _profile_hook = fn
-
 
 def _rows(t):
     """View [..., C] as rows; returns (tensor, nrows, row stride in elements). Last dim must be contiguous."""
@@ -48,13 +39,9 @@ def local3d_attention_fwd(q, k, v, extents, heads, need_lse=False, logits_dbg=Fa
     if logits_dbg:
         K = (2 * extents[0] + 1) * (2 * extents[1] + 1) * (2 * extents[2] + 1)
         dbg = torch.full((N, heads, K), -1e9, dtype=torch.float32, device=q.device)
-    if _profile_hook is not None:
-        _profile_hook('wmz_local3d_attn_fwd', True)
     L.call('wmz_local3d_attn_fwd_general' if general else 'wmz_local3d_attn_fwd', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out),
            L.ptr(lse), L.ptr(dbg),
            B, S, H, W, heads, dh, int(extents[0]), int(extents[1]), int(extents[2]), ldq, ldk, ldv, I, dt, L.stream())
-    if _profile_hook is not None:
-        _profile_hook('wmz_local3d_attn_fwd', False)
     return out, lse, dbg
 
 
@@ -379,10 +366,6 @@ def workspace_snapshot(device):
     side = _wgrad_side.get(device)
     return (_wgrad_ws.get(device), _embed_ws.get(device), _vq_ws.get(device), _vq_screen_ws.get(device),
             None if side is None else side[2])
-
-
-def workspace_same(a, b):
-    return all(x is y for x, y in zip(a, b))
 
 
 _wgrad_ws = {}          # device -> fp32 scratch for the two-stage weight-gradient reduction (grown on demand, never shrunk)
@@ -1127,17 +1110,6 @@ def bn_act_bwd(x, y, dy, mean, rstd, gamma, leaky, slope=0.01, into=None, remask
     L.call('wmz_bn_bwd_apply_add', L.ptr(x), L.ptr(g), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(sg), L.ptr(sgx), L.ptr(add),
            L.ptr(dx), M, C, dt, L.stream())
     return dx, sgx, sg, g
-
-
-def leaky_bwd(y, dy, slope=0.01):
-    """g = dy * LeakyReLU'(y) from the stored output."""
-    C = dy.shape[-1]
-    M = dy.numel() // C
-    dy = dy.contiguous()
-    g = torch.empty_like(dy)
-    L.call('wmz_bn_act_bwd_reduce', None, L.ptr(y), L.ptr(dy), None, None, L.ptr(g), None, None, M, C, 1, float(slope),
-           L.dtype_code(dy.dtype), L.stream())
-    return g
 
 
 def bilinear2x_nhwc_bwd(dy):
