@@ -292,6 +292,29 @@ def test_cone_planes_schedule():
                     assert src[l] == S - min(live)
 
 
+def test_inference_route_matches_the_written_out_table():
+    """fused.inference_route -- the one place both inference call sites (main.py, local_3d_attention.py) ask -- against the route
+    table of tests/route_table.py for every (widths, plane, mode) of the GPU route matrix, models built on the host.  The chain
+    rows ask the library which widths csrc/chain_widths.h holds (it loads on a CPU-only host)."""
+    import route_table as rt
+    from world_modelz_amd import config, fused
+    from world_modelz_amd.local_3d_attention import Local3dAttentionTransformer
+    for widths in rt.WIDTHS:
+        dim, heads, dh, mlp = widths
+        tr = Local3dAttentionTransformer(data_shape=(3, 16, 20), dim=dim, num_classes=17, extents=(1, 1, 2), depth=2, heads=heads,
+                                         dim_head=dh, mlp_dim=mlp)
+        for H, W in rt.PLANES:
+            for mode, dt in rt.MODES.items():
+                for policy in ('always', 'never'):
+                    prev = config.set_chain_policy(policy)
+                    try:
+                        got = fused.inference_route(tr, dt, H, W, 2 * 3 * H * W)
+                    finally:
+                        config.set_chain_policy(prev)
+                    want = rt.expected_route(widths, mode, H, W, policy)
+                    assert got == want, (widths, (H, W), mode, policy, got, want)
+
+
 def test_untracked_loads_stay_untouched_until_their_wait():
     """layer_fused.hip fetches the residual rows with inline-asm loads that hipcc does not track (so that it does not drain
     the weight ring at their first use).  That is only safe if no instruction touches their destination registers before

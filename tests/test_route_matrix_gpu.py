@@ -1,0 +1,277 @@
+"""The denoiser's inference / training dispatch across its seams: a deterministic table of model widths x planes x compute
+modes (tests/route_table.py, written out from config.py's documented rules) against the fp32 CPU oracle.  Every cell asserts
+WHICH entry points produced its result (conftest.recorded_calls) as well as the numbers: the routes each have their own tests
+at the shapes they were built for; this file runs the shapes between them -- precise-mode planes the half attention unit has
+no kernel for, head splits of the default width, Identity layers, heads off the granule, token counts off the fused packs."""
+import pytest
+import torch
+
+import route_table as rt
+from conftest import chain_policy, recorded_calls
+
+pytestmark = pytest.mark.gpu
+
+from oracle import denoiser as oden          # noqa: E402
+from oracle import train_step as ots         # noqa: E402
+
+B, S, C = 2, 3, 48
+
+# extents per plane: small windows clipped at the grid edges, a zero extent, one full (3, 3, 3) window on 8 x 8
+EXTENTS = {(16, 16): (1, 1, 2), (6, 16): (1, 0, 1), (1, 16): (1, 1, 2), (8, 8): (3, 3, 3), (2, 8): (1, 0, 1), (7, 8): (1, 1, 2),
+           (12, 12): (1, 0, 1), (5, 7): (1, 1, 2), (4, 20): (1, 0, 1)}
+
+TOL = {'fp32': 1e-5, 'bf16': 1e-2, 'precise': 1e-3}           # precise: on the half route; on the fp32 route it is 1e-5
+
+
+def rel(a, b):
+    a, b = a.detach().float().cpu(), b.detach().float().cpu()
+    return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+def wid(w):
+    return f'{w[0]}-{w[1]}x{w[2]}-{w[3]}'
+
+
+@pytest.fixture(scope='module')
+def wmz():
+    assert torch.cuda.is_available()
+    from world_modelz_amd import config, main, train
+    from world_modelz_amd._lib import WmzError
+    return dict(config=config, main=main, train=train, WmzError=WmzError)
+
+
+def _model(wmz, widths, H, W, ext, seed, shape=None):
+    dim, heads, dh, mlp = widths
+    torch.manual_seed(seed)
+    return wmz['main'].VqVideoDiffusionModel(data_shape=shape or (S, H, W), dim=dim, num_classes=C, extents=ext, depth=2,
+                                             dim_head=dh, mlp_dim=mlp, heads=heads)
+
+
+def check_route(seen, route, mode):
+    """The entry points a call reached are those of `route` in `mode`."""
+    names = set(seen)
+    sfx = '_f16' if mode == 'precise' else ''
+    if route == 'ops':
+        assert not any(rt.is_fused_or_chain(n) for n in names), names
+        assert not any(n.endswith('_f16') for n in names), names
+        return
+    if route == 'fused':
+        assert all(e + sfx in names for e in rt.FUSED_ENTRIES), names
+        assert not any('layer_chain' in n for n in names), names
+    else:
+        assert all(e + sfx in names for e in rt.CHAIN_ENTRIES), names
+        assert not any('layer_fused' in n or 'embed_qkv_fused' in n for n in names), names
+    if mode == 'precise':
+        assert not any(rt.is_fused_or_chain(n) and not n.endswith('_f16') for n in names), names
+    else:
+        assert not any(n.endswith('_f16') for n in names), names
+
+
+def _cells(mode):
+    """(mode, chain policy) runs of a row: a chain-width row runs bf16 under 'always' and again under 'never'."""
+    return [(mode, 'always'), (mode, 'never')] if mode == 'bf16' else [(mode, 'always')]
+
+
+@pytest.mark.parametrize('H,W', rt.PLANES, ids=[f'{h}x{w}' for h, w in rt.PLANES])
+@pytest.mark.parametrize('widths', rt.WIDTHS, ids=[wid(w) for w in rt.WIDTHS])
+def test_inference_route_and_logits_vs_oracle(wmz, widths, H, W):
+    """One (widths, plane) row in the three modes: the route the table names, the logits against the fp32 oracle (computed once
+    for the row), the last-frame cone bit-identical to the full grid, the module boundary in the parameters' dtype; in the precise
+    mode off the half route, the fp32 mode's logits bit for bit."""
+    cfg = wmz['config']
+    ext, heads = EXTENTS[(H, W)], widths[1]
+    m = _model(wmz, widths, H, W, ext, seed=1000 * H + W + widths[0])
+    sd = {k: v.clone() for k, v in m.state_dict().items()}
+    z = torch.randint(0, C + 1, (B, S, H, W))
+    ref = oden.denoiser_forward(sd, z, ext, heads)
+    m = m.cuda()
+    zc = z.cuda()
+    chain_row = (widths[0], widths[1] * widths[2], widths[3]) in rt.CHAIN_WIDTHS
+    out, lines = {}, []
+    for mode in ('fp32', 'bf16', 'precise'):
+        for _, policy in (_cells(mode) if chain_row else [(mode, 'always')]):
+            route = rt.expected_route(widths, mode, H, W, policy)
+            with cfg.compute_dtype(rt.MODES[mode]), chain_policy(policy), torch.no_grad():
+                with recorded_calls() as seen:
+                    y = m(zc)
+                with cfg.last_frame_cone(False):
+                    y_full = m(zc)
+                t = m.transformer(zc)
+            check_route(seen, route, mode)
+            assert y.dtype == torch.float32 and y.shape == (B, H, W, C)
+            assert torch.equal(y, y_full), (mode, policy, 'last-frame cone differs from the full grid')
+            assert t.dtype == torch.float32
+            e = rel(y, ref)
+            out[(mode, policy)] = (y, e, route)
+            tol = TOL[mode] if not (mode == 'precise' and route == 'ops') else 1e-5
+            lines.append((mode, policy, route, e, tol))
+    eb = out[('bf16', 'always')][1]
+    for mode, policy, route, e, tol in lines:
+        print(f'[route] {wid(widths)} {H}x{W} ext {ext} {mode}{"/" + policy if mode == "bf16" and chain_row else ""}: '
+              f'route {route}, rel {e:.2e} (bf16 {eb:.2e})')
+    for mode, policy, route, e, tol in lines:
+        assert e < tol, (mode, policy, route, e)
+    yp, _, route_p = out[('precise', 'always')]
+    if route_p == 'ops':
+        assert torch.equal(yp, out[('fp32', 'always')][0]), 'the precise mode off its half kernels must be the fp32 route'
+
+
+TRAIN_PLANES = [(16, 16), (7, 8), (12, 12)]
+
+
+@pytest.mark.parametrize('H,W', TRAIN_PLANES, ids=[f'{h}x{w}' for h, w in TRAIN_PLANES])
+@pytest.mark.parametrize('widths', rt.WIDTHS, ids=[wid(w) for w in rt.WIDTHS])
+def test_training_step_vs_oracle(wmz, widths, H, W):
+    """One DenoiserTrainer.forward_backward per mode: loss and every parameter gradient against the oracle's autograd.  At
+    B = 2, S = 3 a 7 x 8 plane is 336 tokens -- no multiple of 32: the default widths fall from the fused packs to the op-by-op
+    path.  The precise mode trains on the fp32 route (no half entry point) and meets the fp32 bounds."""
+    cfg, train = wmz['config'], wmz['train']
+    ext, heads = EXTENTS[(H, W)], widths[1]
+    m0 = _model(wmz, widths, H, W, ext, seed=7000 + 1000 * H + W + widths[0])
+    sd = {k: v.clone() for k, v in m0.state_dict().items()}
+    z = torch.randint(0, C + 1, (B, S, H, W))
+    target = torch.randint(0, C, (B, H, W))
+    _, _, loss_ref, grads_ref = ots.step_grads(sd, z, target, ext, heads)
+    for mode in ('fp32', 'bf16', 'precise'):
+        m = _model(wmz, widths, H, W, ext, seed=0)
+        m.load_state_dict(sd)
+        m = m.cuda()
+        with cfg.compute_dtype(rt.MODES[mode]), chain_policy('always'):
+            tr = train.DenoiserTrainer(m, C, lr=1e-3, warmup=0, max_steps=100, distributed=False)
+            tr.arena.zero_grad()
+            with recorded_calls() as seen:
+                _, mean = tr.forward_backward(z.cuda(), target.cuda())
+        torch.cuda.synchronize()
+        f32 = mode != 'bf16'
+        if mode == 'precise':
+            assert not any(n.endswith('_f16') for n in seen), set(seen)
+        worst = max((float((p.grad.detach().cpu() - grads_ref[n]).norm() / (grads_ref[n].norm() + 1e-12)), n)
+                    for n, p in m.named_parameters())
+        dl = abs(float(mean) - float(loss_ref))
+        path = 'fused' if 'wmz_layer_fused_fwd_train' in seen else ('chain' if 'wmz_layer_chain_fwd_train' in seen else 'ops')
+        print(f'[train] {wid(widths)} {H}x{W} {mode}: path {path}, loss diff {dl:.1e}, worst gradient {worst[0]:.2e} ({worst[1]})')
+        assert dl < (1e-5 if f32 else 2e-2), (mode, dl)
+        assert worst[0] < (3e-4 if f32 else 6e-2), (mode, worst)
+        del tr, m
+
+
+def test_route_switch_after_an_optimizer_step(wmz):
+    """Default widths: one full bf16 trainer step on the fused training route (a token count that is a multiple of 32), then
+    inference on a 16 x 16 grid and a 7 x 8 grid (the fused kernels on whole 32-token tiles and on planes without them: bf16 has
+    no op-by-op inference at these widths) and on the 7 x 8 grid in the precise mode (op by op, fp32), each against the oracle on
+    the UPDATED weights -- stale packed weight streams or operand copies on any of these routes would show as the pre-step
+    model's logits."""
+    cfg, train = wmz['config'], wmz['train']
+    widths, ext = (256, 1, 128, 256), (1, 1, 2)
+    m = _model(wmz, widths, 16, 16, ext, seed=31)
+    sd0 = {k: v.clone() for k, v in m.state_dict().items()}
+    m = m.cuda()
+    z = torch.randint(0, C + 1, (B, S, 16, 16))
+    zs = {(16, 16): z, (7, 8): torch.randint(0, C + 1, (B, S, 7, 8))}
+    runs = [((16, 16), 'bf16'), ((7, 8), 'bf16'), ((7, 8), 'precise')]
+    with torch.no_grad():
+        for plane, mode in runs:
+            with cfg.compute_dtype(rt.MODES[mode]):
+                m(zs[plane].cuda())                            # packs and operand copies of the pre-step weights exist
+    with cfg.compute_dtype(torch.bfloat16):
+        tr = train.DenoiserTrainer(m, C, lr=1e-2, warmup=0, max_steps=100, distributed=False)
+        with recorded_calls() as seen:
+            tr.train_step(z.cuda(), r=torch.full((B,), 0.5))
+    assert 'wmz_layer_fused_fwd_train' in seen, set(seen)
+    sd1 = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+    for (H, W), mode in runs:
+        zz = zs[(H, W)]
+        route = rt.expected_route(widths, mode, H, W)
+        with cfg.compute_dtype(rt.MODES[mode]), torch.no_grad(), recorded_calls() as seen:
+            y = m(zz.cuda())
+        check_route(seen, route, mode)
+        ref1 = oden.denoiser_forward(sd1, zz, ext, 1)
+        ref0 = oden.denoiser_forward(sd0, zz, ext, 1)
+        e1, e0 = rel(y, ref1), rel(ref0, ref1)
+        print(f'[switch] {H}x{W} {mode}: route {route}, rel vs updated weights {e1:.2e} (the step moved the logits by {e0:.2e})')
+        assert e0 > 3e-2                                       # the step moved the weights enough to catch a stale copy
+        assert e1 < (TOL[mode] if route != 'ops' else 1e-5), (mode, route, e1)
+
+
+def _uniforms(n_iter, H, W, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.rand(1, n_iter, B * H * W, generator=g), torch.rand(1, n_iter, B, H * W, generator=g)
+
+
+def test_graphed_sampler_in_the_precise_mode(wmz):
+    """sample_frames(use_graph=True) with injected uniforms, default widths: on 12 x 12 latents the precise mode runs the fp32
+    route -- the same tokens as the fp32 mode; on 16-wide latents the captured forward reaches the half entry points."""
+    from world_modelz_amd import sample
+    cfg = wmz['config']
+    n_iter = 4
+    toks = {}
+    for H, W in ((12, 12), (8, 16)):
+        m = _model(wmz, (256, 1, 128, 256), H, W, (1, 1, 1), seed=77).cuda()
+        z = torch.randint(0, C, (B, S, H, W), device='cuda')
+        u = _uniforms(n_iter, H, W, seed=H * W)
+        for mode in ('fp32', 'precise'):
+            with cfg.compute_dtype(rt.MODES[mode]), recorded_calls() as seen:
+                frames, _ = sample.sample_frames(m, z, C, num_frames=1, num_eval_iterations=n_iter, uniforms=u, use_graph=True)
+            toks[(H, W, mode)] = frames[0].cpu()
+            if mode == 'precise':
+                check_route(seen, 'ops' if W != 16 else 'fused', 'precise')
+        if W != 16:
+            assert torch.equal(toks[(H, W, 'precise')], toks[(H, W, 'fp32')])
+        del m
+
+
+def test_sparse_model_in_the_precise_mode_is_the_fp32_route(wmz):
+    """Config 5 (VqSparseDiffusionModel) has no half kernels: in the precise mode its logits are the fp32 mode's, bit for bit,
+    no half entry point is reached, and both are the oracle's within 1e-5."""
+    from oracle import denoiser as od
+    from world_modelz_amd.sparse_diffusion import VqSparseDiffusionModel
+    cfg = wmz['config']
+    torch.manual_seed(12)
+    shape, n = (3, 8, 8), 64
+    m = VqSparseDiffusionModel(shape=shape, dim=64, num_classes=C, depth=2, dim_head=32, mlp_dim=96, heads=2)
+    sd = {k: v.clone() for k, v in m.state_dict().items()}
+    tokens = torch.randint(0, C + 1, (B, n))
+    indices = torch.stack([torch.randperm(192)[:n] for _ in range(B)])
+    ref = od.sparse_denoiser_forward(sd, tokens, indices, shape, 2)
+    m = m.cuda()
+    with torch.no_grad():
+        with cfg.compute_dtype(torch.float32):
+            y32 = m(tokens.cuda(), indices.cuda())
+        with cfg.compute_dtype(torch.float16), recorded_calls() as seen:
+            yp = m(tokens.cuda(), indices.cuda())
+    assert not any(nm.endswith('_f16') for nm in seen), set(seen)
+    assert torch.equal(yp, y32)
+    assert rel(y32, ref) < 1e-5, rel(y32, ref)
+
+
+@pytest.mark.parametrize('mode', list(rt.MODES))
+def test_identity_with_dim_head_above_128_raises(wmz, mode):
+    """Quirk Q6 at the reference's default dim (heads 1, dim_head = dim = 256): the attention kernels are built up to dim_head 128,
+    so every mode refuses it with an error that names dim_head."""
+    cfg = wmz['config']
+    m = _model(wmz, (256, 1, 256, 256), 16, 16, (1, 1, 1), seed=3).cuda()
+    z = torch.randint(0, C + 1, (B, S, 16, 16), device='cuda')
+    with cfg.compute_dtype(rt.MODES[mode]), torch.no_grad():
+        with pytest.raises(wmz['WmzError'], match='dim_head'):
+            m(z)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('heads,dh', [(1, 36), (2, 18)])
+@pytest.mark.parametrize('mode', list(rt.MODES))
+def test_model_width_off_the_granule_is_refused_before_any_launch(wmz, mode, heads, dh):
+    """dim 36 (as an Identity layer of one head of 36, and as two heads of 18): every GEMM reduces over the model width in
+    8-element granules, so the denoiser and the config-5 model refuse it on the host -- an error naming the width and the
+    granule, no entry point reached."""
+    from world_modelz_amd.sparse_diffusion import VqSparseDiffusionModel
+    cfg = wmz['config']
+    m = _model(wmz, (36, heads, dh, 64), 8, 8, (1, 1, 1), seed=5).cuda()
+    z = torch.randint(0, C + 1, (B, S, 8, 8), device='cuda')
+    sp = VqSparseDiffusionModel(shape=(S, 8, 8), dim=36, num_classes=C, depth=2, dim_head=dh, mlp_dim=64, heads=heads).cuda()
+    tokens = torch.randint(0, C + 1, (B, 32), device='cuda')
+    indices = torch.stack([torch.randperm(S * 64)[:32] for _ in range(B)]).cuda()
+    with cfg.compute_dtype(rt.MODES[mode]), torch.no_grad():
+        for call in (lambda: m(z), lambda: m.transformer(z), lambda: sp(tokens, indices)):
+            with recorded_calls() as seen, pytest.raises(wmz['WmzError'], match=r'dim=36.*multiple of 8'):
+                call()
+            assert seen == [], seen

@@ -95,6 +95,22 @@ def half_attention_ok(transformer, H, W):
     return dh <= {32, 64, 128} and (W == 16 or (W == 8 and H % 2 == 0))
 
 
+def inference_route(transformer, dtype, H, W, ntok):
+    """The inference forward Local3dAttentionTransformer takes for fused-kernel dtype `dtype` (config.get_fused_dtype()) on
+    H x W planes of ntok tokens in all: 'fused' (the default widths), 'chain' (the widths of csrc/chain_widths.h) or 'ops'
+    (op by op in the compute dtype).  float16 -- the precise mode -- has half kernels for the row attention kernel's planes and
+    heads only (half_attention_ok); anything else runs op by op, which is fp32 there.  bfloat16 takes the chain kernels where
+    they pay (chain_pays)."""
+    half = dtype == torch.float16
+    if half and not half_attention_ok(transformer, H, W):
+        return 'ops'
+    if supported(transformer, dtype):
+        return 'fused'
+    if chain_supported(transformer, dtype, True) and (half or chain_pays(chain_widths(transformer), ntok, False)):
+        return 'chain'
+    return 'ops'
+
+
 def _chain_pieces(w, pad_value=0):
     """[N, K] fp32 -> the kernel's 1 KB MFMA 16x16x32 A operands in (k-step, 16-feature block) order, lane-linear:
     piece (ks, b), lane l = 16 ga + m, element j = W[(m >> 2) N/4 + 4 b + (m & 3)][ga K/4 + 8 ks + j] -- output feature and k

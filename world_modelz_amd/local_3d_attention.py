@@ -19,6 +19,15 @@ from torch import nn
 from . import functional as Fw
 
 
+def check_model_width(dim, what):
+    """Every GEMM of the stack reduces over the model width in the kernels' 8-element (16-byte) granule, and unlike a head width
+    (Local3dAttention._head_padded) the model width cannot be zero-padded: LayerNorm would average over the padding.  Refused on
+    the host, before any launch."""
+    if dim % 8:
+        raise Fw.ops.L.WmzError(f'{what}: model width dim={dim} is not a multiple of 8 (the kernels\' 8-element granule); '
+                                'widths off the granule are not supported')
+
+
 class PreNorm(nn.Module):
     """LayerNorm in front of `fn` (reference :11-17).  Only the positional input is normalised; keyword
     arguments (the attention's `q`) pass through untouched -- quirk Q1."""
@@ -207,17 +216,17 @@ class Local3dAttentionTransformer(nn.Module):
         """forward() without the boundary cast: the residual stream in the compute dtype (internal callers)."""
         if not img_z.is_cuda:
             raise Fw.ops.L.WmzError('Local3dAttentionTransformer runs on the GPU only (no CPU fallback)')
+        check_model_width(self.embedding.weight.shape[1], 'Local3dAttentionTransformer')
         self.check_grid(img_z)
         if not torch.is_grad_enabled():
             from . import fused
-            from .config import get_compute_dtype, get_fused_dtype
-            if fused.supported(self, get_fused_dtype()):
+            from .config import get_fused_dtype
+            route = fused.inference_route(self, get_fused_dtype(), img_z.shape[2], img_z.shape[3], img_z.numel())
+            if route == 'fused':
                 # inference, bf16 (or half: the precise mode), default widths: one attention launch + one per-token launch per
                 # layer, the embedding fused into the first one
                 return fused.transformer_forward(self, z=img_z)
-            if fused.chain_supported(self, get_fused_dtype(), True) and (
-                    fused.half_attention_ok(self, img_z.shape[2], img_z.shape[3]) if get_fused_dtype() == torch.float16
-                    else fused.chain_pays(fused.chain_widths(self), img_z.numel(), False)):
+            if route == 'chain':
                 # the width table of csrc/chain_widths.h: the same fusion on csrc/layer_chain.hip -- its half unit in the precise
                 # mode, where the planes are the row attention kernel's (other planes stay on the fp32 route below); in bfloat16
                 # where the token count fills enough 128-token workgroups to beat the op-by-op GEMMs (fused.chain_pays)

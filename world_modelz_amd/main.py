@@ -20,9 +20,9 @@ class VqVideoDiffusionModel(nn.Module):
     def forward(self, x):
         if not torch.is_grad_enabled() and x.is_cuda:
             from . import config, fused
-            if config.get_last_frame_cone() and fused.supported(self.transformer, config.get_fused_dtype()):
-                tr = self.transformer
-                _, S, H, W = x.shape
+            tr = self.transformer
+            _, S, H, W = x.shape
+            if config.get_last_frame_cone() and fused.inference_route(tr, config.get_fused_dtype(), H, W, x.numel()) == 'fused':
                 if S > tr.pos_emb_s.num_embeddings or H > tr.pos_emb_h.num_embeddings or W > tr.pos_emb_w.num_embeddings:
                     raise IndexError('token grid larger than the position-embedding tables')
                 last = fused.transformer_forward_last(tr, x)      # only the planes the last frame depends on

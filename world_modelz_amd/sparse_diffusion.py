@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fw
+from .local_3d_attention import check_model_width
 from .transformer import Transformer
 
 
@@ -74,6 +75,7 @@ class VqSparseDiffusionModel(nn.Module):
         return sum(tab[ix] for tab, ix in zip(tables, (plane, row, col)))
 
     def forward(self, x, indices):
+        check_model_width(self.embedding.weight.shape[1], 'VqSparseDiffusionModel')
         h = Fw.embed_tokens_indexed(x, indices, self.embedding.weight, self.pos_emb_s.weight, self.pos_emb_h.weight,
                                     self.pos_emb_w.weight, self.shape)
         h = self.transformer.forward_compute(h)

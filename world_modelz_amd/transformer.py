@@ -9,7 +9,7 @@ import torch
 from torch import nn
 
 from . import functional as Fw
-from .local_3d_attention import FeedForward, PreNorm  # same modules as the local-attention stack  # noqa: F401
+from .local_3d_attention import FeedForward, PreNorm, check_model_width  # same modules as the local-attention stack  # noqa: F401
 
 
 class Attention(nn.Module):
@@ -96,6 +96,7 @@ class Transformer(nn.Module):
         return self.forward_compute(x).to(x.dtype)       # boundary dtype rule: see local_3d_attention.py
 
     def forward_compute(self, x):
+        check_model_width(x.shape[-1], 'Transformer')
         x = Fw._as_compute(x)
         for attn, ff in self.layers:
             x = attn.fn.forward_prenorm(x, attn.norm, residual=x)     # attn(x) + x
