@@ -1,7 +1,7 @@
-"""The denoiser's inference dispatch written out from config.py's documented rules -- the table that
-tests/test_route_matrix_gpu.py runs on the GPU and tests/test_parallel_cpu.py pins against fused.inference_route on the host.
-It is deliberately NOT derived from fused.supported / chain_supported / half_attention_ok: a change of those gates has to
-change this table too."""
+"""The denoiser's inference and training dispatch written out from config.py's documented rules -- the tables that
+tests/test_route_matrix_gpu.py runs on the GPU and tests/test_parallel_cpu.py pins against fused.inference_route /
+fused.training_route on the host.  They are deliberately NOT derived from fused.supported / chain_supported / chain_pays /
+half_attention_ok: a change of those gates has to change these tables too."""
 import torch
 
 MODES = {'fp32': torch.float32, 'bf16': torch.bfloat16, 'precise': torch.float16}
@@ -22,6 +22,8 @@ WIDTHS = [
 
 # planes (H, W); S = 3, B = 2 in the GPU matrix
 PLANES = [(16, 16), (6, 16), (1, 16), (8, 8), (2, 8), (7, 8), (12, 12), (5, 7), (4, 20)]
+# ... and of the training matrix: 7 x 8 is 336 tokens, no multiple of 32
+TRAIN_PLANES = [(16, 16), (7, 8), (12, 12)]
 
 # (dim, dim_head * heads, mlp_dim) of the fused per-token kernels (csrc/layer_fused.hip) ...
 FUSED_WIDTHS = {(256, 128, 256)}
@@ -57,6 +59,23 @@ def expected_route(widths, mode, H, W, chain_policy='always'):
     return 'ops'
 
 
+def expected_training_route(widths, mode, ntok, fused_backward=True, chain_policy='always'):
+    """(forward, backward kernels) of a DenoiserTrainer step of the model `widths` in `mode` on ntok tokens, the fused training
+    switch on: forward 'fused' | 'chain' | 'ops', backward kernels True where that forward's own backward kernels run (else the
+    op-by-op block backward).  Training has no half kernels: the precise mode trains on the fp32 route, op by op.  The fused
+    backward kernels work on whole 32-token tiles; the chain kernels train in bf16 under chain_policy 'always' (the trainer's
+    step; a module called outside a trainer holds no chain packs and trains op by op)."""
+    dim, heads, dh, mlp = widths
+    if mode != 'bf16' or is_identity(dim, heads, dh):
+        return 'ops', False
+    key = (dim, heads * dh, mlp)
+    if key in FUSED_WIDTHS:
+        return 'fused', fused_backward and ntok % 32 == 0
+    if key in CHAIN_WIDTHS and chain_policy == 'always':
+        return 'chain', fused_backward
+    return 'ops', False
+
+
 # entry points that identify a route
 FUSED_ENTRIES = ('wmz_layer_fused_fwd_planes', 'wmz_embed_qkv_fused_fwd_planes')
 CHAIN_ENTRIES = ('wmz_layer_chain_fwd_planes',)
@@ -64,3 +83,7 @@ CHAIN_ENTRIES = ('wmz_layer_chain_fwd_planes',)
 
 def is_fused_or_chain(name):
     return 'layer_fused' in name or 'layer_chain' in name or 'embed_qkv_fused' in name
+
+
+# the backward kernels of each training family
+TRAIN_BWD_ENTRIES = {'fused': ('wmz_ff_fused_bwd', 'wmz_qkv_fused_bwd'), 'chain': ('wmz_chain_ff_bwd', 'wmz_chain_qkv_bwd')}

@@ -315,6 +315,50 @@ def test_inference_route_matches_the_written_out_table():
                     assert got == want, (widths, (H, W), mode, policy, got, want)
 
 
+
+def test_training_route_matches_the_written_out_table():
+    """fused.training_route -- the one place the trainer's step (train.py) and the module's training forward
+    (local_3d_attention.py) ask -- against the training table of tests/route_table.py for every (widths, token count, mode) of the
+    GPU training matrix, with the fused backward on and off and both chain policies; chain packs held where fused.training_packs
+    has a trainer build them.  Called outside a trainer (no chain packs), the chain rows train op by op.  The fused training
+    switch off: op by op everywhere."""
+    import route_table as rt
+    from world_modelz_amd import config, fused
+    from world_modelz_amd.local_3d_attention import Local3dAttentionTransformer
+    fb0, ft0 = config.fused_backward(), config.get_fused_training()
+    try:
+        for widths in rt.WIDTHS:
+            dim, heads, dh, mlp = widths
+            tr = Local3dAttentionTransformer(data_shape=(3, 16, 20), dim=dim, num_classes=17, extents=(1, 1, 2), depth=2,
+                                             heads=heads, dim_head=dh, mlp_dim=mlp)
+            for H, W in rt.TRAIN_PLANES:
+                ntok = 2 * 3 * H * W
+                for mode, mdt in rt.MODES.items():
+                    for fb in (True, False):
+                        for policy in ('always', 'never'):
+                            config.set_fused_backward(fb)
+                            prev = config.set_chain_policy(policy)
+                            try:
+                                with config.compute_dtype(mdt):
+                                    dt = config.get_compute_dtype()
+                                    packs = fused.training_packs(tr, dt)
+                                    got = fused.training_route(tr, dt, ntok, packs == 'chain')
+                                    alone = fused.training_route(tr, dt, ntok, False)
+                                    config.set_fused_training(False)
+                                    off = fused.training_route(tr, dt, ntok, packs == 'chain')
+                                    config.set_fused_training(ft0)
+                            finally:
+                                config.set_chain_policy(prev)
+                            want = rt.expected_training_route(widths, mode, ntok, fb, policy)
+                            cell = (widths, (H, W), mode, fb, policy, got, want)
+                            assert got == want, cell
+                            assert alone == (('ops', False) if want[0] == 'chain' else want), cell
+                            assert (packs == 'fused') == (want[0] == 'fused' and fb), (cell, packs)
+                            assert off == ('ops', False), cell
+    finally:
+        config.set_fused_backward(fb0)
+        config.set_fused_training(ft0)
+
 def test_untracked_loads_stay_untouched_until_their_wait():
     """layer_fused.hip fetches the residual rows with inline-asm loads that hipcc does not track (so that it does not drain
     the weight ring at their first use).  That is only safe if no instruction touches their destination registers before

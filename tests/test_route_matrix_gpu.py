@@ -116,10 +116,7 @@ def test_inference_route_and_logits_vs_oracle(wmz, widths, H, W):
         assert torch.equal(yp, out[('fp32', 'always')][0]), 'the precise mode off its half kernels must be the fp32 route'
 
 
-TRAIN_PLANES = [(16, 16), (7, 8), (12, 12)]
-
-
-@pytest.mark.parametrize('H,W', TRAIN_PLANES, ids=[f'{h}x{w}' for h, w in TRAIN_PLANES])
+@pytest.mark.parametrize('H,W', rt.TRAIN_PLANES, ids=[f'{h}x{w}' for h, w in rt.TRAIN_PLANES])
 @pytest.mark.parametrize('widths', rt.WIDTHS, ids=[wid(w) for w in rt.WIDTHS])
 def test_training_step_vs_oracle(wmz, widths, H, W):
     """One DenoiserTrainer.forward_backward per mode: loss and every parameter gradient against the oracle's autograd.  At
@@ -149,7 +146,13 @@ def test_training_step_vs_oracle(wmz, widths, H, W):
                     for n, p in m.named_parameters())
         dl = abs(float(mean) - float(loss_ref))
         path = 'fused' if 'wmz_layer_fused_fwd_train' in seen else ('chain' if 'wmz_layer_chain_fwd_train' in seen else 'ops')
-        print(f'[train] {wid(widths)} {H}x{W} {mode}: path {path}, loss diff {dl:.1e}, worst gradient {worst[0]:.2e} ({worst[1]})')
+        kernel_bwd = any(n in seen for bwd in rt.TRAIN_BWD_ENTRIES.values() for n in bwd)
+        print(f'[train] {wid(widths)} {H}x{W} {mode}: path {path}, backward kernels {kernel_bwd}, loss diff {dl:.1e}, '
+              f'worst gradient {worst[0]:.2e} ({worst[1]})')
+        want = rt.expected_training_route(widths, mode, B * S * H * W)
+        assert (path, kernel_bwd) == want, (mode, path, kernel_bwd, want)
+        if path != 'ops':
+            assert all(n in seen for n in rt.TRAIN_BWD_ENTRIES[path]) == kernel_bwd, set(seen)
         assert dl < (1e-5 if f32 else 2e-2), (mode, dl)
         assert worst[0] < (3e-4 if f32 else 6e-2), (mode, worst)
         del tr, m

@@ -42,7 +42,8 @@ for c in range(cases):
         config.set_chain_policy('always')        # (small grids: 'auto' would send every chain-width case to the op-by-op path)
         with config.compute_dtype(dt):
             tr = DenoiserTrainer(m, C, lr=1e-3, warmup=0, max_steps=100, distributed=False)
-            path = 'chain' if tr.chain_packs is not None else ('fused' if fused.supported(m.transformer, config.get_compute_dtype()) and z.numel() % 32 == 0 else 'ops')
+            route, kernel_bwd = fused.training_route(m.transformer, config.get_compute_dtype(), z.numel(), tr.chain_packs is not None)
+            path = route if kernel_bwd or route == 'ops' else route + ' forward, op-by-op backward'
             tr.arena.zero_grad()
             _, mean = tr.forward_backward(z.cuda(), target.cuda())
             torch.cuda.synchronize()

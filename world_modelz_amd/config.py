@@ -83,8 +83,8 @@ def last_frame_cone(on):
         set_last_frame_cone(prev)
 
 
-# Training forward of the denoiser on the fused kernels (bf16, default widths): one attention launch + one per-token
-# launch per layer instead of six; the backward recomputes the feed-forward pre-activation.  Off: the op-by-op forward.
+# Training forward of the denoiser on the fused or chain kernels (bf16): one attention launch + one per-token launch per layer
+# instead of six.  Off: the op-by-op forward.
 _fused_training = os.environ.get('WMZ_FUSED_TRAINING', '1') != '0'
 
 
@@ -97,9 +97,6 @@ def set_fused_training(on):
     _fused_training = bool(on)
 
 
-# ... and its backward on the fused per-token backward kernels (csrc/layer_fused_bwd.hip: wmz_ff_fused_bwd /
-# wmz_qkv_fused_bwd; the forward then also saves the feed-forward pre-activation).  Off: the op-by-op backward
-# (backward.py) behind the fused forward.
 # Which per-token path the chain kernels' widths (csrc/chain_widths.h) take in bfloat16: 'auto' = the chain kernels where they pay
 # (fused.chain_pays: their workgroups hold 128 tokens and stream the layer's whole weight set each, so below a token count that
 # grows with the weight bytes the op-by-op GEMMs -- tiled over tokens AND features -- are faster; profiles/r06/time_chain_tokens.txt),
@@ -119,6 +116,9 @@ def set_chain_policy(policy):
     return prev
 
 
+# The training stack's backward on its kernel family's backward kernels (csrc/layer_fused_bwd.hip, layer_chain_bwd.hip; the
+# forward then also saves what they read).  Off: the op-by-op backward (backward.py) behind the fused or chain forward.  Both
+# switches are read by fused.training_route.
 _fused_backward = True
 
 

@@ -111,6 +111,36 @@ def inference_route(transformer, dtype, H, W, ntok):
     return 'ops'
 
 
+def _trains_fused(transformer):
+    return config.get_fused_training() and hasattr(transformer, 'pos_emb_s')
+
+
+def training_packs(transformer, dtype):
+    """The packed weight streams a trainer keeps for the stack in compute dtype `dtype` -- the part of training_route that does
+    not depend on the token count: 'fused' (PackSet: the fused forward's and backward kernels' streams), 'chain' (ChainPackSet)
+    or None (the fused forward under the op-by-op backward packs its own streams per parameter version)."""
+    if not _trains_fused(transformer):
+        return None
+    if supported(transformer, dtype):
+        return 'fused' if config.fused_backward() else None
+    return 'chain' if chain_supported(transformer, dtype) else None
+
+
+def training_route(transformer, dtype, ntok, chain_packs):
+    """(forward, backward kernels) of the training stack of Local3dAttentionTransformer in compute dtype `dtype` at ntok tokens:
+    forward 'fused' (the default widths), 'chain' (the widths of csrc/chain_widths.h, where they pay: chain_pays) or 'ops'; backward
+    kernels True where that family's backward kernels run, else the op-by-op block backward.  chain_packs: the caller holds the
+    trainer's ChainPackSet (a module called outside a trainer never does).  The fused backward kernels work on whole 32-token tiles.
+    Training has no half kernels: the precise mode passes its compute dtype, fp32, and trains op by op."""
+    if not _trains_fused(transformer):
+        return 'ops', False
+    if supported(transformer, dtype):
+        return 'fused', config.fused_backward() and ntok % 32 == 0
+    if chain_packs and chain_pays(chain_widths(transformer), ntok, True):
+        return 'chain', config.fused_backward()
+    return 'ops', False
+
+
 def _chain_pieces(w, pad_value=0):
     """[N, K] fp32 -> the kernel's 1 KB MFMA 16x16x32 A operands in (k-step, 16-feature block) order, lane-linear:
     piece (ks, b), lane l = 16 ga + m, element j = W[(m >> 2) N/4 + 4 b + (m & 3)][ga K/4 + 8 ks + j] -- output feature and k
@@ -135,15 +165,6 @@ def _chain_pack(head, tail, D, I, M, MC, dt=torch.bfloat16):
     """(wpack in dt -- bf16, or half for the _f16 unit --, vec fp32) for one launch of wmz_layer_chain_fwd_planes: stages to_out | MC-wide feed-forward chunks (W1'
     rows, then W2 columns) | q | k | v, LayerNorm affines folded in (W1' = W1 diag(g2), b1' = b1 + W1 be2; to_k / to_v likewise
     with the next layer's norm); vec = bout | b1' | b2 | bk' | bv'.  Cached per parameter version."""
-    params = []
-    if head is not None:
-        attn, ff = head
-        params += [attn.fn.to_out[0].weight, attn.fn.to_out[0].bias, ff.norm.weight, ff.norm.bias,
-                   ff.fn.net[0].weight, ff.fn.net[0].bias, ff.fn.net[3].weight, ff.fn.net[3].bias]
-    if tail is not None:
-        an = tail[0]
-        params += [an.norm.weight, an.norm.bias, an.fn.to_q.weight, an.fn.to_k.weight, an.fn.to_v.weight, an.fn.to_v.bias]
-
     def build(*ps):
         ps = [p.detach().float() for p in ps]
         dev = ps[0].device
@@ -172,7 +193,7 @@ def _chain_pack(head, tail, D, I, M, MC, dt=torch.bfloat16):
         assert stream.shape[0] % sp == 0
         wpack = torch.cat([stream.reshape(-1), stream.new_zeros(3 * sp * 512)]).to(dt).contiguous()
         return wpack, vec
-    return _cast.cached(params, f'chainpack{D}_{I}_{M}{_sfx(dt)}', build)
+    return _cast.cached(_boundary_params(head, tail), f'chainpack{D}_{I}_{M}{_sfx(dt)}', build)
 
 
 def transformer_forward_chain(tr, z):
@@ -367,12 +388,36 @@ def _chain_layer_train(packs, l, o, x_in, head, tail, keep_raw):
     return r
 
 
-def _chain_layer_backward(packs, l, attn, ff, dy, x_in, xh_attn, st_attn, q, kv, o, lse, xh_ff, st_ff, z, h):
-    """One layer of the stack's backward on the chain kernels: wmz_chain_ff_bwd -> attention backward -> wmz_chain_qkv_bwd, the
-    weight gradients as plain GEMMs over the operands the forward and these kernels wrote (normalised rows behind the norms), the
-    LayerNorm affine gradients from the raw weight gradients (wmz_ln_affine_grads) -- the structure of _layer_backward_fused."""
+def _chain_stack_train(tr, packs, z, kernel_bwd):
+    """Training forward of the stack on the chain kernels (ChainPackSet of the trainer's arena): embedding, then per layer ONE
+    attention launch + ONE per-token launch that also leaves what the backward reads (normalised rows, pre-activation, GELU of
+    it, LayerNorm statistics; without the backward kernels the raw feed-forward input rows as well).  Returns (the stream
+    [B, S, H, W, D], the tensors _StackTrain saves: per layer x_in, q, kv, o, lse, x1, st_attn, st_ff, z, h, xh_attn, xh_ff)."""
+    from . import functional as Fw
     D, I, M, MC = packs.widths
-    an_g, an_b, wq, wk, wv, bv, wout, bout, fn_g, fn_b, w1, b1, w2, b2 = _layer_params(attn, ff)
+    layers = list(tr.layers)
+    B, S, H, W = z.shape
+    x0 = Fw.embed_tokens(z, tr.embedding.weight.detach(), tr.pos_emb_s.weight.detach(), tr.pos_emb_h.weight.detach(),
+                         tr.pos_emb_w.weight.detach())
+    cur = _chain_layer_train(packs, 0, None, x0, False, True, False)
+    x_in = x0.reshape(-1, D)
+    saved = []
+    empty = x0.new_empty(0)
+    for l, (attn, ff) in enumerate(layers):
+        q, kv = cur['q'].view(B, S, H, W, I), cur['kv'].view(B, S, H, W, 2 * I)
+        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I], kv[..., I:], attn.fn.extents, attn.fn.heads, need_lse=True)
+        nxt = _chain_layer_train(packs, l + 1, o, x_in, True, l + 1 < len(layers), not kernel_bwd)
+        saved += [x_in, q, kv, o, lse, nxt.get('x1', empty), cur['st_attn'], nxt['st_ff'], nxt['z'], nxt['h'], cur['xh_attn'],
+                  nxt['xh_ff']]
+        x_in, cur = nxt['x'], nxt
+    return x_in.view(B, S, H, W, D), saved
+
+
+def _chain_layer_backward(packs, l, attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff, z, h, xh_attn, xh_ff):
+    """One layer of the stack's backward on the chain kernels: wmz_chain_ff_bwd -> attention backward -> wmz_chain_qkv_bwd, the
+    weight gradients over the operands the forward and these kernels wrote (_layer_weight_grads).  x1 is not read: the kernels
+    work on the normalised rows xh_ff."""
+    D, I, M, MC = packs.widths
     dev, bf = dy.device, torch.bfloat16
     ntok = dy.numel() // D
     dy2 = dy.reshape(ntok, D)
@@ -385,135 +430,18 @@ def _chain_layer_backward(packs, l, attn, ff, dy, x_in, xh_attn, st_attn, q, kv,
     dx = torch.empty(dy.shape, dtype=bf, device=dev)
     L.call('wmz_chain_qkv_bwd', L.ptr(dq), L.ptr(dkv), L.ptr(xh_attn), L.ptr(st_attn[1]), L.ptr(dx1), L.ptr(dx),
            L.ptr(packs.stream('qkv_bwd', l)), ntok, D, I, L.stream())
-    s_ff2, s_out, s_q = _GradSink(w2, b2), _GradSink(wout, bout), _GradSink(wq)
-    G1 = torch.empty((M, D), dtype=torch.float32, device=dev)
-    c1 = torch.empty((M,), dtype=torch.float32, device=dev)
-    Gkv = torch.empty((2 * I, D), dtype=torch.float32, device=dev)
-    ckv = torch.empty((2 * I,), dtype=torch.float32, device=dev)
-    # ONE launch pair: at dim 384 all five fill >= 3/8 of their 256-wide tiles (wgrad3_kernel's bar; one ineligible problem would
-    # send the whole batch to the 128-wide kernel: 225 us a layer)
-    wide = [(dy2, h, s_ff2.bufs[0], s_ff2.bufs[1], False),                     # dW2 = dy^T GELU(z), db2 = colsum(dy)
-            (dz, xh_ff, G1, c1, True),                                          # against the NORMALISED rows: raw gradient + column sums
-            (dkv.reshape(ntok, 2 * I), xh_attn, Gkv, ckv, True)]
-    narrow = [(dx1, o.reshape(ntok, I), s_out.bufs[0], s_out.bufs[1], False),
-              (dq.reshape(ntok, I), x_in.reshape(ntok, D), s_q.bufs[0], None, False)]
-    s_ff1 = _GradSink(w1, b1, fn_g, fn_b)
-    s_kv = _GradSink(wk, wv, bv, an_g, an_b)
-    bk_, bw_ = s_kv.bufs[0], s_kv.bufs[1]
-    adjacent = (wk.is_contiguous() and wv.is_contiguous() and bk_.is_contiguous() and bw_.is_contiguous()
-                and wv.data_ptr() == wk.data_ptr() + 4 * wk.numel() and bw_.data_ptr() == bk_.data_ptr() + 4 * bk_.numel())
-    probs = [(G1, c1, w1, fn_g, fn_b, s_ff1.bufs[0], s_ff1.bufs[1], s_ff1.bufs[2], s_ff1.bufs[3], M, D, 0)]
-    if adjacent:
-        probs.append((Gkv, ckv, wk, an_g, an_b, bk_, s_kv.bufs[2], s_kv.bufs[3], s_kv.bufs[4], 2 * I, D, I))
-    else:
-        probs.append((Gkv[:I], ckv[:I], wk, an_g, an_b, bk_, None, s_kv.bufs[3], s_kv.bufs[4], I, D, I))
-        probs.append((Gkv[I:], ckv[I:], wv, an_g, an_b, bw_, s_kv.bufs[2], s_kv.bufs[3], s_kv.bufs[4], I, D, 0))
-
-    def weight_grads(side):
-        ops.linear_wgrad_batch(wide + narrow, side=side)
-        _ln_affine_grads_batch(probs)
-    # nothing in the backward chain reads these results: under capture they leave on the weight-gradient side branch (gradients that
-    # land in the flat arena only: a gradient handed back to autograd is consumed on the compute stream)
-    direct = all(sk.direct for sk in (s_ff2, s_out, s_q, s_ff1, s_kv))
-    if direct and config.get_wgrad_stream():
-        ops.side_branch(dev, (dy2, h, dz, xh_ff, dkv, xh_attn, dx1, o, dq, x_in, G1, c1, Gkv, ckv), weight_grads)
-    else:
-        weight_grads(None)
-    g_wk, g_wv, g_bv, g_ag, g_ab = s_kv.done()
-    (g_wq,) = s_q.done()
-    g_wout, g_bout = s_out.done()
-    g_w1, g_b1, g_fg, g_fb = s_ff1.done()
-    g_w2, g_b2 = s_ff2.done()
-    return dx, [g_ag, g_ab, g_wq, g_wk, g_wv, g_bv, g_wout, g_bout, g_fg, g_fb, g_w1, g_b1, g_w2, g_b2]
-
-
-class _ChainTrainForward(torch.autograd.Function):
-    """The whole stack as one autograd node for the widths of csrc/layer_chain.hip (the reference's published runs): forward =
-    embedding + per layer ONE attention launch + ONE per-token launch that also leaves what the backward reads (normalised rows,
-    pre-activation, GELU of it, LayerNorm statistics); backward per layer = wmz_chain_ff_bwd + the attention backward +
-    wmz_chain_qkv_bwd + one batched weight-gradient launch pair (config.fused_backward() off: the op-by-op block backward
-    functions instead, reading the raw rows the forward then keeps as well)."""
-
-    @staticmethod
-    def forward(ctx, tr, packs, z, last_only, *params):
-        from . import functional as Fw
-        D, I, M, MC = packs.widths
-        layers = list(tr.layers)
-        B, S, H, W = z.shape
-        fused_bwd = config.fused_backward()
-        x0 = Fw.embed_tokens(z, tr.embedding.weight.detach(), tr.pos_emb_s.weight.detach(), tr.pos_emb_h.weight.detach(),
-                             tr.pos_emb_w.weight.detach())
-        cur = _chain_layer_train(packs, 0, None, x0, False, True, False)
-        x_in = x0.reshape(-1, D)
-        saved = []
-        empty = x0.new_empty(0)
-        for l, (attn, ff) in enumerate(layers):
-            q, kv = cur['q'].view(B, S, H, W, I), cur['kv'].view(B, S, H, W, 2 * I)
-            o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I], kv[..., I:], attn.fn.extents, attn.fn.heads, need_lse=True)
-            nxt = _chain_layer_train(packs, l + 1, o, x_in, True, l + 1 < len(layers), not fused_bwd)
-            saved += [x_in, cur['xh_attn'], cur['st_attn'], q, kv, o, lse, nxt.get('x1', empty), nxt['xh_ff'], nxt['st_ff'],
-                      nxt['z'], nxt['h']]
-            x_in, cur = nxt['x'], nxt
-        ctx.tr, ctx.packs, ctx.last_only, ctx.fused_bwd = tr, packs, bool(last_only), fused_bwd
-        ctx.save_for_backward(z, *saved)
-        xo = x_in.view(B, S, H, W, D)
-        return xo[:, -1].contiguous() if last_only else xo
-
-    @staticmethod
-    def backward(ctx, dy):
-        from . import backward as Bk
-        tr, packs = ctx.tr, ctx.packs
-        D, I, M, MC = packs.widths
-        layers = list(tr.layers)
-        z, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
-        B, S, H, W = z.shape
-        grads = [None] * (14 * len(layers))
-        dy = dy.contiguous()
-        if ctx.last_only:
-            full = torch.zeros((B, S, H, W, D), dtype=dy.dtype, device=dy.device)
-            full[:, -1] = dy
-            dy = full
-        NS = 12
-        for l in range(len(layers) - 1, -1, -1):
-            attn, ff = layers[l]
-            x_in, xh_attn, st_attn, q, kv, o, lse, x1, xh_ff, st_ff, zpre, hact = saved[NS * l:NS * l + NS]
-            if ctx.fused_bwd:
-                dy, g = _chain_layer_backward(packs, l, attn, ff, dy, x_in, xh_attn, st_attn, q, kv, o, lse, xh_ff, st_ff, zpre, hact)
-                grads[14 * l:14 * l + 14] = g
-                continue
-            an_g, an_b, wq, wk, wv, bv, wout, bout, fn_g, fn_b, w1, b1, w2, b2 = _layer_params(attn, ff)
-            x1v, x_inv = x1.view(B, S, H, W, D), x_in.view(B, S, H, W, D)
-            cf = _Ctx((x1v, fn_g, fn_b, w1, b1, w2, b2, zpre.view(B, S, H, W, M), hact.view(B, S, H, W, M)),
-                      has_res=True, res_is_x=True, ln_stats=(st_ff[0], st_ff[1]))
-            dx1, g_fg, g_fb, g_w1, g_b1, g_w2, g_b2 = Bk.feed_forward_block_backward(cf, dy)[:7]
-            ca = _Ctx((x_inv, x_inv, an_g, an_b, wq, wk, wv, bv, wout, bout, q, kv, o, lse), extents=attn.fn.extents,
-                      heads=attn.fn.heads, has_res=True, res_is_xkv=True, same_src=True, ln_stats=(st_attn[0], st_attn[1]))
-            r = Bk.attention_block_backward(ca, dx1)
-            dy = r[0]
-            grads[14 * l:14 * l + 14] = [r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], g_fg, g_fb, g_w1, g_b1, g_w2, g_b2]
-        ce = _Ctx((z,), params=(tr.embedding.weight, tr.pos_emb_s.weight, tr.pos_emb_h.weight, tr.pos_emb_w.weight))
-        ge = Bk.embed_backward(ce, dy)
-        return (None, None, None, None, ge[1], ge[2], ge[3], ge[4], *grads)
-
-
-def transformer_forward_chain_train(tr, packs, z, last_only=False):
-    """Training forward of the stack on the chain kernel (ChainPackSet of the trainer's arena)."""
-    params = [tr.embedding.weight, tr.pos_emb_s.weight, tr.pos_emb_h.weight, tr.pos_emb_w.weight]
-    for attn, ff in tr.layers:
-        params += _layer_params(attn, ff)
-    return _ChainTrainForward.apply(tr, packs, z, last_only, *params)
+    return dx, _layer_weight_grads(attn, ff, (dy2, h), (dz, xh_ff), (dx1, o.reshape(ntok, I)),
+                                   (dq.reshape(ntok, I), x_in.reshape(ntok, D), False), (dkv.reshape(ntok, 2 * I), xh_attn), True)
 
 
 def _sfx(dt):
     return '_f16' if dt == torch.float16 else ''
 
 
-def _layer_pack(head, tail, dt=torch.bfloat16):
-    """head / tail: (attn PreNorm, ff PreNorm) of the layer whose to_out+FF run, and of the layer whose q|k|v run.
-    Returns (wpack bf16, vec fp32) built by ONE launch of wmz_layer_fused_pack from the fp32 parameters: the weights in
-    the kernel's streaming order (see _pack_w for the element order; W1 rows one chunk ahead of the W2 columns:
-    W1[0], W1[1], W2[0], W1[2], W2[1], .., W1[7], W2[6], W2[7]) with the LayerNorm affines folded in (W1' = W1 diag(g2),
-    b1' = b1 + W1 be2; same for to_k / to_v with the next layer's norm), and bout | b1' | b2 | bk' | bv'."""
+def _boundary_params(head, tail):
+    """The parameters one forward launch between two attention launches reads: head = (attn, ff) PreNorms of the layer whose
+    to_out + feed-forward run -- wout, bout, g2, be2, w1, b1, w2, b2 --, tail = those of the layer whose q | k | v run -- g1, be1,
+    wq, wk, wv, bv."""
     params = []
     if head is not None:
         attn, ff = head
@@ -522,7 +450,15 @@ def _layer_pack(head, tail, dt=torch.bfloat16):
     if tail is not None:
         an = tail[0]
         params += [an.norm.weight, an.norm.bias, an.fn.to_q.weight, an.fn.to_k.weight, an.fn.to_v.weight, an.fn.to_v.bias]
+    return params
 
+
+def _layer_pack(head, tail, dt=torch.bfloat16):
+    """head / tail: (attn PreNorm, ff PreNorm) of the layer whose to_out+FF run, and of the layer whose q|k|v run.
+    Returns (wpack bf16, vec fp32) built by ONE launch of wmz_layer_fused_pack from the fp32 parameters: the weights in
+    the kernel's streaming order (see _pack_w for the element order; W1 rows one chunk ahead of the W2 columns:
+    W1[0], W1[1], W2[0], W1[2], W2[1], .., W1[7], W2[6], W2[7]) with the LayerNorm affines folded in (W1' = W1 diag(g2),
+    b1' = b1 + W1 be2; same for to_k / to_v with the next layer's norm), and bout | b1' | b2 | bk' | bv'."""
     def build(*ps):
         ps = [p.detach() for p in ps]
         assert all(p.dtype == torch.float32 and p.is_contiguous() for p in ps)
@@ -535,7 +471,7 @@ def _layer_pack(head, tail, dt=torch.bfloat16):
         L.call('wmz_layer_fused_pack' + _sfx(dt), *[L.ptr(t) for t in hp], *[L.ptr(t) for t in tp], L.ptr(wpack), L.ptr(vec),
                D_, I_, M_, L.stream())
         return wpack, vec
-    return _cast.cached(params, 'fusedpack' + _sfx(dt), build)
+    return _cast.cached(_boundary_params(head, tail), 'fusedpack' + _sfx(dt), build)
 
 
 def _layer_pack_bwd(attn, ff):
@@ -593,13 +529,10 @@ class PackSet:
             nw = (D_ * I_ + 2 * M_ * D_ if head is not None else 0) + (3 * I_ * D_ if tail is not None else 0)
             wpack = torch.zeros(nw + _PAD // 2, dtype=torch.bfloat16, device=dev)
             vec = torch.zeros(2048, dtype=torch.float32, device=dev)
-            params, off = [], 0
+            params, off = _boundary_params(head, tail), 0
             job = [0] * 10
             if head is not None:
-                attn, ff = head
-                wout, bout, g2, be2 = attn.fn.to_out[0].weight, attn.fn.to_out[0].bias, ff.norm.weight, ff.norm.bias
-                w1, b1, w2, b2 = ff.fn.net[0].weight, ff.fn.net[0].bias, ff.fn.net[3].weight, ff.fn.net[3].bias
-                params += [wout, bout, g2, be2, w1, b1, w2, b2]
+                wout, bout, g2, be2, w1, b1, w2, b2 = params[:8]
                 off = block(wpack, off, wout, 0, I_, 1, D_, I_, D_, I_, None, None)
                 off = block(wpack, off, w1, 0, D_, 1, MC_, D_, MC_, D_, g2, None)
                 for c in range(1, M_ // MC_):
@@ -608,10 +541,7 @@ class PackSet:
                 off = block(wpack, off, w2, (M_ // MC_ - 1) * MC_, M_, 1, D_, MC_, D_, MC_, None, None)
                 job[0:5] = [ptr(bout), ptr(b1), ptr(w1), ptr(be2), ptr(b2)]
             if tail is not None:
-                an = tail[0]
-                g1, be1 = an.norm.weight, an.norm.bias
-                wq, wk, wv, bv = an.fn.to_q.weight, an.fn.to_k.weight, an.fn.to_v.weight, an.fn.to_v.bias
-                params += [g1, be1, wq, wk, wv, bv]
+                g1, be1, wq, wk, wv, bv = params[-6:]
                 off = block(wpack, off, wq, 0, D_, 1, I_, D_, I_, D_, None, None)
                 off = block(wpack, off, wk, 0, D_, 1, I_, D_, I_, D_, g1, None)
                 off = block(wpack, off, wv, 0, D_, 1, I_, D_, I_, D_, g1, None)
@@ -774,17 +704,10 @@ def _run_chain(tr, z, cone, out):
     return x
 
 
-def transformer_forward(tr, x=None, z=None):
-    """depth x [attention, feed-forward] on the fused kernels: per layer ONE attention launch + ONE per-token launch, the
-    embedding riding in the first per-token launch.  Returns the stream [B, S, H, W, D] (row-major)."""
-    if z is not None:
-        return _run(tr, z, cone=False)
-    layers = list(tr.layers)
-    _, q, kv = layer_fused(None, x, None, layers[0])
-    for l, (attn, ff) in enumerate(layers):
-        o, _, _ = ops.local3d_attention_fwd(q, kv[0], kv[1], attn.fn.extents, attn.fn.heads)
-        x, q, kv = layer_fused(o, x, (attn, ff), layers[l + 1] if l + 1 < len(layers) else None)
-    return x
+def transformer_forward(tr, z):
+    """depth x [attention, feed-forward] on the fused kernels over the token grid z: per layer ONE attention launch + ONE
+    per-token launch, the embedding riding in the first per-token launch.  Returns the stream [B, S, H, W, D] (row-major)."""
+    return _run(tr, z, cone=False)
 
 
 def transformer_forward_last(tr, z):
@@ -794,8 +717,8 @@ def transformer_forward_last(tr, z):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# training forward on the fused kernels (wmz_*_train): one attention launch + one per-token launch per layer, and the
-# tensors the op-by-op backward (backward.py) reads are written row-major on the way
+# training: the stack as one autograd node (_StackTrain) on the fused kernels (wmz_*_train) or the chain kernels
+# (_chain_stack_train), backward on that family's backward kernels or op by op (backward.py), as training_route decides
 
 def _embed_train(tr, z, tiled, xhat_rm=False):
     """xhat_rm (tiled only): the row-major output holds the NORMALISED rows (what the fused backward reads); the raw stream
@@ -900,15 +823,90 @@ def _ln_affine_grads_batch(probs):
     L.call('wmz_ln_affine_grads_batch', n, *cols, Ns, Ks, bf, L.stream())
 
 
-def _layer_backward_fused(attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff, zt, dy_last=None, x_in_tiled=None):
-    """One layer of the stack's backward on the fused per-token kernels: wmz_ff_fused_bwd -> attention backward ->
-    wmz_qkv_fused_bwd, the weight gradients as plain GEMMs over the operands those kernels write, the LayerNorm affine
-    gradients from the raw weight gradients (wmz_ln_affine_grads).  x1: the NORMALISED rows of the feed-forward block's input, as
-    the forward stored them (WMZ_FUSED_X1_NORMALISED).  x_in_tiled given: x_in holds the layer input's NORMALISED rows too
-    (WMZ_FUSED_XRM_NORMALISED) and x_in_tiled the raw stream in the tiled layout.  dy_last = (S, HW): dy holds only the clips' last planes
-    ([B, H, W, D], the last layer under the denoiser's last-frame loss).  Returns (gradient w.r.t. the layer's input, the 14
-    parameter gradients in _layer_params order)."""
+def _layer_weight_grads(attn, ff, ff2, ff1, out, q, kv, chain):
+    """The layer's five weight gradients as plain GEMMs over the token axis, ONE launch pair, from (gradient, operand) row pairs:
+    ff2 = (dy, GELU(z)), ff1 = (dz, the feed-forward input's NORMALISED rows), out = (dx1, o), q = (dq, the layer input's raw rows,
+    whether those are the fused kernels' tiled stream), kv = (dk | dv, the layer input's NORMALISED rows).  Those behind a LayerNorm
+    come out as raw gradients G and column sums c, turned into the parameter gradients by one wmz_ln_affine_grads_batch launch.
+    chain: the chain kernels' batch, which under capture leaves on the weight-gradient side branch; the fused kernels' batch stays
+    on the compute stream.  Returns the 14 parameter gradients in _layer_params order."""
     an_g, an_b, wq, wk, wv, bv, wout, bout, fn_g, fn_b, w1, b1, w2, b2 = _layer_params(attn, ff)
+    (M, D), I = w1.shape, wq.shape[0]
+    dev = w1.device
+    s_ff2, s_out, s_q = _GradSink(w2, b2), _GradSink(wout, bout), _GradSink(wq)
+    G1 = torch.empty((M, D), dtype=torch.float32, device=dev)
+    c1 = torch.empty((M,), dtype=torch.float32, device=dev)
+    Gkv = torch.empty((2 * I, D), dtype=torch.float32, device=dev)
+    ckv = torch.empty((2 * I,), dtype=torch.float32, device=dev)
+    s_ff1 = _GradSink(w1, b1, fn_g, fn_b)
+    s_kv = _GradSink(wk, wv, bv, an_g, an_b)
+    p_ff2 = (*ff2, s_ff2.bufs[0], s_ff2.bufs[1], False)                       # dW2 = dy^T GELU(z), db2 = colsum(dy)
+    p_ff1, p_kv = (*ff1, G1, c1, True), (*kv, Gkv, ckv, True)
+    p_out, p_q = (*out, s_out.bufs[0], s_out.bufs[1], False), (q[0], q[1], s_q.bufs[0], None, False, q[2])
+    # (the chain kernels' batch lists the wide problems first; at dim 384 all five fill >= 3/8 of wgrad3_kernel's 256-wide tiles,
+    # so the batch stays on it: one ineligible problem would send the whole batch to the 128-wide kernel, 225 us a layer)
+    wgrads = [p_ff2, p_ff1, p_kv, p_out, p_q] if chain else [p_ff2, p_ff1, p_out, p_q, p_kv]
+    bk_, bw_ = s_kv.bufs[0], s_kv.bufs[1]
+    adjacent = (wk.is_contiguous() and wv.is_contiguous() and bk_.is_contiguous() and bw_.is_contiguous()
+                and wv.data_ptr() == wk.data_ptr() + 4 * wk.numel() and bw_.data_ptr() == bk_.data_ptr() + 4 * bk_.numel())
+    # one launch for the layer's LayerNorm-affine conversions: (G, s, W, gamma, beta, dW, dbias, dgamma, dbeta, N, K, bias_from)
+    probs = [(G1, c1, w1, fn_g, fn_b, s_ff1.bufs[0], s_ff1.bufs[1], s_ff1.bufs[2], s_ff1.bufs[3], M, D, 0)]
+    # (the kernel only does pointer arithmetic on W and dW: two separately allocated neighbours are as good as one arena)
+    if adjacent:                        # FlatArena: to_k.weight | to_v.weight (and their gradients) are one [2I, D] block
+        probs.append((Gkv, ckv, wk, an_g, an_b, bk_, s_kv.bufs[2], s_kv.bufs[3], s_kv.bufs[4], 2 * I, D, I))
+    else:
+        probs.append((Gkv[:I], ckv[:I], wk, an_g, an_b, bk_, None, s_kv.bufs[3], s_kv.bufs[4], I, D, I))
+        probs.append((Gkv[I:], ckv[I:], wv, an_g, an_b, bw_, s_kv.bufs[2], s_kv.bufs[3], s_kv.bufs[4], I, D, 0))
+
+    def weight_grads(side):
+        ops.linear_wgrad_batch(wgrads, side=side)
+        _ln_affine_grads_batch(probs)
+    # nothing in the backward chain reads these results: under capture the chain kernels' batch leaves on the weight-gradient
+    # side branch (gradients that land in the flat arena only: a gradient handed back to autograd is consumed on the compute stream)
+    sinks = (s_ff2, s_out, s_q, s_ff1, s_kv)
+    if chain and all(sk.direct for sk in sinks) and config.get_wgrad_stream():
+        ops.side_branch(dev, [t for p in wgrads for t in p[:2]] + [G1, c1, Gkv, ckv], weight_grads)
+    else:
+        weight_grads(None)
+    g_wk, g_wv, g_bv, g_ag, g_ab = s_kv.done()          # (the order the data-parallel reducer sees the layer's gradients land)
+    (g_wq,) = s_q.done()
+    g_wout, g_bout = s_out.done()
+    g_w1, g_b1, g_fg, g_fb = s_ff1.done()
+    g_w2, g_b2 = s_ff2.done()
+    return [g_ag, g_ab, g_wq, g_wk, g_wv, g_bv, g_wout, g_bout, g_fg, g_fb, g_w1, g_b1, g_w2, g_b2]
+
+
+def _fused_stack_train(tr, z, kernel_bwd):
+    """Training forward of the stack on the fused per-token kernels (wmz_*_train): one attention launch + one per-token launch per
+    layer, the tensors the backward reads written row-major on the way.  Returns (the stream [B, S, H, W, D], the tensors
+    _StackTrain saves: per layer x_in, q, kv, o, lse, x1, st_attn, st_ff, zt, x_in_t)."""
+    layers = list(tr.layers)
+    B, S, H, W = z.shape
+    tiled = (H * W) % 32 == 0
+    # backward kernels on a tiled stream: a layer's row-major input copy holds the NORMALISED rows (all the backward needs of
+    # them: LayerNorm backward, to_k | to_v weight gradient); the raw rows -- the to_q weight gradient's operand -- are read from
+    # the tiled stream the forward kernels hand each other
+    xhat_rm = kernel_bwd and tiled
+    x_cur, x_rm, q, kv, st_attn = _embed_train(tr, z, tiled, xhat_rm)
+    saved = []
+    for l, (attn, ff) in enumerate(layers):
+        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I_], kv[..., I_:], attn.fn.extents, attn.fn.heads, need_lse=True)
+        x_in_rm, x_in_t = x_rm, (x_cur if xhat_rm else lse.new_empty(0))
+        x_cur, x_rm, x1, q_n, kv_n, st_ff, st_attn_n, zt = _layer_train(o, x_cur, (attn, ff),
+                                                                       layers[l + 1] if l + 1 < len(layers) else None,
+                                                                       tiled, kernel_bwd, xhat_rm)
+        saved += [x_in_rm, q, kv, o, lse, x1, st_attn, st_ff, zt if zt is not None else lse.new_empty(0), x_in_t]
+        q, kv, st_attn = q_n, kv_n, st_attn_n
+    return x_rm, saved
+
+
+def _layer_backward_fused(attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff, zt, x_in_t, dy_last=None):
+    """One layer of the stack's backward on the fused per-token kernels: wmz_ff_fused_bwd -> attention backward ->
+    wmz_qkv_fused_bwd, the weight gradients over the operands those kernels write (_layer_weight_grads).  x1: the NORMALISED rows
+    of the feed-forward block's input, as the forward stored them (WMZ_FUSED_X1_NORMALISED), zt the pre-activation.  x_in_t not
+    empty: x_in holds the layer input's NORMALISED rows too (WMZ_FUSED_XRM_NORMALISED) and x_in_t the raw stream in the tiled
+    layout.  dy_last = (S, HW): dy holds only the clips' last planes ([B, H, W, D], the last layer under the denoiser's last-frame
+    loss).  Returns (gradient w.r.t. the layer's input, the 14 parameter gradients in _layer_params order)."""
     dev, bf = dy.device, torch.bfloat16
     lead = x1.shape[:-1]
     ntok = x1.numel() // D_
@@ -917,64 +915,26 @@ def _layer_backward_fused(attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff,
     dz = torch.empty((ntok, M_), dtype=bf, device=dev)
     dx1 = torch.empty((ntok, D_), dtype=bf, device=dev)
     do = torch.empty(lead + (I_,), dtype=bf, device=dev)
+    S_, HW_ = dy_last or (0, 0)
+    L.call('wmz_ff_fused_bwd', L.ptr(dy), L.ptr(zt), L.ptr(x1), L.ptr(st_ff), L.ptr(g), L.ptr(dz), None, L.ptr(dx1),
+           L.ptr(do), L.ptr(wpack_ff), ntok, D_, I_, M_, S_, HW_, L.ptr(_zero_row(dev)) if dy_last else None, L.stream())
     if dy_last is None:
-        L.call('wmz_ff_fused_bwd', L.ptr(dy), L.ptr(zt), L.ptr(x1), L.ptr(st_ff), L.ptr(g), L.ptr(dz), None, L.ptr(dx1),
-               L.ptr(do), L.ptr(wpack_ff), ntok, D_, I_, M_, 0, 0, None, L.stream())
         dy2, g2 = dy.reshape(ntok, D_), g
-    else:
-        S_, HW_ = dy_last
-        L.call('wmz_ff_fused_bwd', L.ptr(dy), L.ptr(zt), L.ptr(x1), L.ptr(st_ff), L.ptr(g), L.ptr(dz), None, L.ptr(dx1),
-               L.ptr(do), L.ptr(wpack_ff), ntok, D_, I_, M_, S_, HW_, L.ptr(_zero_row(dev)), L.stream())
-        # dW2 = dy^T GELU(z) only has the last planes' rows to sum over
-        dy2 = dy.reshape(-1, D_)
-        g2 = g.view(-1, S_, HW_, M_)[:, -1].reshape(-1, M_)
+    else:                               # dW2 = dy^T GELU(z) only has the last planes' rows to sum over
+        dy2, g2 = dy.reshape(-1, D_), g.view(-1, S_, HW_, M_)[:, -1].reshape(-1, M_)
     # ---- attention core
     dq, dkv = ops.local3d_attention_bwd(q, kv[..., :I_], kv[..., I_:], o, lse, do, attn.fn.extents, attn.fn.heads)
     # ---- to_q / to_k / to_v inputs
     dx = torch.empty(lead + (D_,), dtype=bf, device=dev)
-    if x_in_tiled is None:
-        xhat = torch.empty((ntok, D_), dtype=bf, device=dev)
-        x_q, x_q_tiled = x_in.reshape(ntok, D_), False
-    else:
-        xhat = None
-        x_q, x_q_tiled = x_in_tiled, True
+    tiled = x_in_t.numel() > 0
+    xhat = None if tiled else torch.empty((ntok, D_), dtype=bf, device=dev)
     L.call('wmz_qkv_fused_bwd', L.ptr(dq), I_, L.ptr(dkv), 2 * I_, L.ptr(x_in), L.ptr(st_attn), L.ptr(dx1), L.ptr(dx),
            L.ptr(xhat), L.ptr(wpack_qkv), ntok, D_, I_, L.stream())
-    if xhat is None:
+    x_q = x_in_t if tiled else x_in.reshape(ntok, D_)
+    if tiled:
         xhat = x_in.reshape(ntok, D_)
-    # ---- the layer's five weight gradients: plain GEMMs over the token axis, ONE launch pair.  Those behind a LayerNorm
-    # are taken against the NORMALISED input (raw gradients G, column sums c) and turned into parameter gradients below.
-    s_ff2, s_out, s_q = _GradSink(w2, b2), _GradSink(wout, bout), _GradSink(wq)
-    G1 = torch.empty((M_, D_), dtype=torch.float32, device=dev)
-    c1 = torch.empty((M_,), dtype=torch.float32, device=dev)
-    Gkv = torch.empty((2 * I_, D_), dtype=torch.float32, device=dev)
-    ckv = torch.empty((2 * I_,), dtype=torch.float32, device=dev)
-    ops.linear_wgrad_batch([
-        (dy2, g2, s_ff2.bufs[0], s_ff2.bufs[1], False),                       # dW2 = dy^T GELU(z), db2 = colsum(dy)
-        (dz, x1.reshape(ntok, D_), G1, c1, True),            # x1 = the NORMALISED rows the forward stored
-        (dx1, o.reshape(ntok, I_), s_out.bufs[0], s_out.bufs[1], False),
-        (dq.reshape(ntok, I_), x_q, s_q.bufs[0], None, False, x_q_tiled),
-        (dkv.reshape(ntok, 2 * I_), xhat, Gkv, ckv, True)])
-    s_ff1 = _GradSink(w1, b1, fn_g, fn_b)
-    s_kv = _GradSink(wk, wv, bv, an_g, an_b)
-    bk_, bw_ = s_kv.bufs[0], s_kv.bufs[1]
-    adjacent = (wk.is_contiguous() and wv.is_contiguous() and bk_.is_contiguous() and bw_.is_contiguous()
-                and wv.data_ptr() == wk.data_ptr() + 4 * wk.numel() and bw_.data_ptr() == bk_.data_ptr() + 4 * bk_.numel())
-    # one launch for the layer's LayerNorm-affine conversions: (G, s, W, gamma, beta, dW, dbias, dgamma, dbeta, N, K, bias_from)
-    probs = [(G1, c1, w1, fn_g, fn_b, s_ff1.bufs[0], s_ff1.bufs[1], s_ff1.bufs[2], s_ff1.bufs[3], M_, D_, 0)]
-    # (the kernel only does pointer arithmetic on W and dW: two separately allocated neighbours are as good as one arena)
-    if adjacent:                        # FlatArena: to_k.weight | to_v.weight (and their gradients) are one [2I, D] block
-        probs.append((Gkv, ckv, wk, an_g, an_b, bk_, s_kv.bufs[2], s_kv.bufs[3], s_kv.bufs[4], 2 * I_, D_, I_))
-    else:
-        probs.append((Gkv[:I_], ckv[:I_], wk, an_g, an_b, bk_, None, s_kv.bufs[3], s_kv.bufs[4], I_, D_, I_))
-        probs.append((Gkv[I_:], ckv[I_:], wv, an_g, an_b, bw_, s_kv.bufs[2], s_kv.bufs[3], s_kv.bufs[4], I_, D_, 0))
-    _ln_affine_grads_batch(probs)
-    g_wk, g_wv, g_bv, g_ag, g_ab = s_kv.done()
-    (g_wq,) = s_q.done()
-    g_wout, g_bout = s_out.done()
-    g_w1, g_b1, g_fg, g_fb = s_ff1.done()
-    g_w2, g_b2 = s_ff2.done()
-    return dx, [g_ag, g_ab, g_wq, g_wk, g_wv, g_bv, g_wout, g_bout, g_fg, g_fb, g_w1, g_b1, g_w2, g_b2]
+    return dx, _layer_weight_grads(attn, ff, (dy2, g2), (dz, x1.reshape(ntok, D_)), (dx1, o.reshape(ntok, I_)),
+                                   (dq.reshape(ntok, I_), x_q, tiled), (dkv.reshape(ntok, 2 * I_), xhat), False)
 
 
 class _Ctx:                      # what backward.attention_block_backward / feed_forward_block_backward read off a ctx
@@ -983,90 +943,84 @@ class _Ctx:                      # what backward.attention_block_backward / feed
         self.__dict__.update(kw)
 
 
-class _TrainForward(torch.autograd.Function):
-    """The whole transformer stack (embedding + depth x [attention, feed-forward]) as one autograd node: forward on the
-    fused kernels, backward layer by layer through the same block backward functions as the op-by-op path (the
-    feed-forward pre-activation is recomputed there by one LayerNorm-GEMM instead of being stored)."""
+def _layer_backward_ops(attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff, zpre=None, hact=None):
+    """One layer of the stack's backward through the op-by-op block backward functions (backward.py), from the raw rows x_in / x1
+    of the two blocks' inputs and the LayerNorm statistics the forward kernels computed.  zpre / hact: the feed-forward
+    pre-activation and its GELU as the forward saved them; None: recomputed from x1 by one LayerNorm-GEMM.  Returns (gradient
+    w.r.t. the layer's input, the 14 parameter gradients in _layer_params order)."""
+    from . import backward as Bk
+    from .functional import LN_EPS
+    an_g, an_b, wq, wk, wv, bv, wout, bout, fn_g, fn_b, w1, b1, w2, b2 = _layer_params(attn, ff)
+    lead = q.shape[:-1]                 # (the chain kernels' rows are saved flat)
+    x_in, x1 = x_in.view(lead + (-1,)), x1.view(lead + (-1,))
+    # feed-forward block: y = W2 GELU(W1 LN(x1) + b1) + b2 + x1
+    stats = (st_ff[0], st_ff[1])
+    if zpre is None:
+        zpre, hact = ops.linear_fwd_gelu_pair(x1, _cast.operand(w1, x1.dtype), bias=b1.detach(), ln=(fn_g.detach(), fn_b.detach()),
+                                              ln_eps=LN_EPS, ln_stats=stats)
+    cf = _Ctx((x1, fn_g, fn_b, w1, b1, w2, b2, zpre.view(lead + (-1,)), hact.view(lead + (-1,))), has_res=True, res_is_x=True,
+              ln_stats=stats)
+    dx1, g_fg, g_fb, g_w1, g_b1, g_w2, g_b2 = Bk.feed_forward_block_backward(cf, dy)[:7]
+    # attention block: x1 = to_out(attn(LN(x), q = x)) + x
+    ca = _Ctx((x_in, x_in, an_g, an_b, wq, wk, wv, bv, wout, bout, q, kv, o, lse), extents=attn.fn.extents,
+              heads=attn.fn.heads, has_res=True, res_is_xkv=True, same_src=True, ln_stats=(st_attn[0], st_attn[1]))
+    r = Bk.attention_block_backward(ca, dx1)
+    return r[0], [r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], g_fg, g_fb, g_w1, g_b1, g_w2, g_b2]
+
+
+class _StackTrain(torch.autograd.Function):
+    """The whole transformer stack (embedding + depth x [attention, feed-forward]) as one autograd node.  Forward on the fused
+    per-token kernels (packs None: _fused_stack_train) or on the chain kernels (packs: the trainer's ChainPackSet,
+    _chain_stack_train).  Backward layer by layer on that family's backward kernels (kernel_bwd) or through the op-by-op block
+    backward functions (_layer_backward_ops), then the embedding's."""
 
     @staticmethod
-    def forward(ctx, tr, z, last_only, *params):
-        layers = list(tr.layers)
-        B, S, H, W = z.shape
-        tiled = (H * W) % 32 == 0
-        # the fused backward kernels (layer_fused_bwd.hip) work on whole 32-token tiles and read the pre-activation the
-        # forward leaves behind; otherwise the op-by-op backward recomputes it
-        fused_bwd = config.fused_backward() and (B * S * H * W) % 32 == 0
-        # fused backward on a tiled stream: a layer's row-major input copy holds the NORMALISED rows (all the backward needs
-        # of them: LayerNorm backward, to_k | to_v weight gradient); the raw rows -- the to_q weight gradient's operand -- are
-        # read from the tiled stream the forward kernels hand each other
-        xhat_rm = fused_bwd and tiled
-        x_cur, x_rm, q, kv, st_attn = _embed_train(tr, z, tiled, xhat_rm)
-        saved = []
-        for l, (attn, ff) in enumerate(layers):
-            o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I_], kv[..., I_:], attn.fn.extents, attn.fn.heads, need_lse=True)
-            x_in_rm, x_in_t = x_rm, (x_cur if xhat_rm else lse.new_empty(0))
-            x_cur, x_rm, x1, q_n, kv_n, st_ff, st_attn_n, zt = _layer_train(o, x_cur, (attn, ff),
-                                                                           layers[l + 1] if l + 1 < len(layers) else None,
-                                                                           tiled, fused_bwd, xhat_rm)
-            saved += [x_in_rm, q, kv, o, lse, x1, st_attn, st_ff, zt if zt is not None else lse.new_empty(0), x_in_t]
-            q, kv, st_attn = q_n, kv_n, st_attn_n
-        ctx.tr = tr
-        ctx.fused_bwd = fused_bwd
-        ctx.last_only = bool(last_only)
+    def forward(ctx, tr, packs, z, last_only, kernel_bwd, *params):
+        x, saved = _fused_stack_train(tr, z, kernel_bwd) if packs is None else _chain_stack_train(tr, packs, z, kernel_bwd)
+        ctx.tr, ctx.packs, ctx.last_only, ctx.kernel_bwd = tr, packs, bool(last_only), kernel_bwd
         ctx.save_for_backward(z, *saved)
         # last_only: the caller reads the last plane only (main.py:37) and hands back a gradient for it alone
-        return x_rm[:, -1].contiguous() if last_only else x_rm
+        return x[:, -1].contiguous() if last_only else x
 
     @staticmethod
     def backward(ctx, dy):
         from . import backward as Bk
-        from .functional import LN_EPS
-        tr = ctx.tr
+        tr, packs = ctx.tr, ctx.packs
         layers = list(tr.layers)
         z, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        B, S, H, W = z.shape
+        ns = len(saved) // len(layers)
         grads = [None] * (14 * len(layers))
         dy = dy.contiguous()
-        NS = 10
         dy_last = None
         if ctx.last_only:
-            B, S, H, W = z.shape
-            if ctx.fused_bwd:
+            if ctx.kernel_bwd and packs is None:
                 dy_last = (S, H * W)                       # the last layer's kernel reads the other planes' zeros from a zero row
             else:
-                full = torch.zeros((B, S, H, W, D_), dtype=dy.dtype, device=dy.device)
+                full = torch.zeros((B, S, H, W, dy.shape[-1]), dtype=dy.dtype, device=dy.device)
                 full[:, -1] = dy
                 dy = full
         for l in range(len(layers) - 1, -1, -1):
             attn, ff = layers[l]
-            x_in, q, kv, o, lse, x1, st_attn, st_ff, zt, x_in_t = saved[NS * l:NS * l + NS]
-            an_g, an_b, wq, wk, wv, bv, wout, bout, fn_g, fn_b, w1, b1, w2, b2 = _layer_params(attn, ff)
-            if ctx.fused_bwd:
-                dy, g = _layer_backward_fused(attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff, zt,
-                                              dy_last if l == len(layers) - 1 else None, x_in_t if x_in_t.numel() else None)
-                grads[14 * l:14 * l + 14] = g
-                continue
-            dt = x1.dtype
-            # feed-forward block: y = W2 GELU(W1 LN(x1) + b1) + b2 + x1
-            stats = (st_ff[0], st_ff[1])                   # computed by the fused forward: no extra pass over x1
-            zpre, hact = ops.linear_fwd_gelu_pair(x1, _cast.operand(w1, dt), bias=b1.detach(), ln=(fn_g.detach(), fn_b.detach()),
-                                                  ln_eps=LN_EPS, ln_stats=stats)
-            cf = _Ctx((x1, fn_g, fn_b, w1, b1, w2, b2, zpre, hact), has_res=True, res_is_x=True, ln_stats=stats)
-            dx1, g_fg, g_fb, g_w1, g_b1, g_w2, g_b2 = Bk.feed_forward_block_backward(cf, dy)[:7]
-            # attention block: x1 = to_out(attn(LN(x), q = x)) + x
-            ca = _Ctx((x_in, x_in, an_g, an_b, wq, wk, wv, bv, wout, bout, q, kv, o, lse), extents=attn.fn.extents,
-                      heads=attn.fn.heads, has_res=True, res_is_xkv=True, same_src=True, ln_stats=(st_attn[0], st_attn[1]))
-            r = Bk.attention_block_backward(ca, dx1)
-            dy = r[0]
-            grads[14 * l:14 * l + 14] = [r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], g_fg, g_fb, g_w1, g_b1, g_w2, g_b2]
+            s = saved[ns * l:ns * l + ns]
+            if not ctx.kernel_bwd:                         # (the chain forward saved the pre-activation and its GELU)
+                dy, g = _layer_backward_ops(attn, ff, dy, *s[:8], *(s[8:10] if packs is not None else ()))
+            elif packs is None:
+                dy, g = _layer_backward_fused(attn, ff, dy, *s, dy_last if l == len(layers) - 1 else None)
+            else:
+                dy, g = _chain_layer_backward(packs, l, attn, ff, dy, *s)
+            grads[14 * l:14 * l + 14] = g
         ce = _Ctx((z,), params=(tr.embedding.weight, tr.pos_emb_s.weight, tr.pos_emb_h.weight, tr.pos_emb_w.weight))
         ge = Bk.embed_backward(ce, dy)
-        return (None, None, None, ge[1], ge[2], ge[3], ge[4], *grads)
+        return (None, None, None, None, None, ge[1], ge[2], ge[3], ge[4], *grads)
 
 
-def transformer_forward_train(tr, z, last_only=False):
-    """The stack's output [B, S, H, W, D] -- or, with last_only, its last plane [B, H, W, D] (what the denoiser's loss reads:
-    the backward then never materialises the zero gradient of the other planes)."""
+def transformer_forward_train(tr, z, kernel_bwd, packs=None, last_only=False):
+    """Training forward of the stack on the kernels training_route names: the fused per-token kernels, or with packs (the trainer's
+    ChainPackSet) the chain kernels; kernel_bwd: that family's backward kernels run.  Returns the stream [B, S, H, W, D] -- or,
+    with last_only, its last plane [B, H, W, D] (what the denoiser's loss reads: the fused backward kernels then never
+    materialise the zero gradient of the other planes)."""
     params = [tr.embedding.weight, tr.pos_emb_s.weight, tr.pos_emb_h.weight, tr.pos_emb_w.weight]
     for attn, ff in tr.layers:
         params += _layer_params(attn, ff)
-    return _TrainForward.apply(tr, z, last_only, *params)
+    return _StackTrain.apply(tr, packs, z, last_only, kernel_bwd, *params)

@@ -225,16 +225,18 @@ class Local3dAttentionTransformer(nn.Module):
             if route == 'fused':
                 # inference, bf16 (or half: the precise mode), default widths: one attention launch + one per-token launch per
                 # layer, the embedding fused into the first one
-                return fused.transformer_forward(self, z=img_z)
+                return fused.transformer_forward(self, img_z)
             if route == 'chain':
                 # the width table of csrc/chain_widths.h: the same fusion on csrc/layer_chain.hip -- its half unit in the precise
                 # mode, where the planes are the row attention kernel's (other planes stay on the fp32 route below); in bfloat16
                 # where the token count fills enough 128-token workgroups to beat the op-by-op GEMMs (fused.chain_pays)
                 return fused.transformer_forward_chain(self, img_z)
         else:
-            from . import config, fused
-            if config.get_fused_training() and fused.supported(self, config.get_compute_dtype()):
-                return fused.transformer_forward_train(self, img_z)     # training forward on the fused kernels
+            from . import fused
+            from .config import get_compute_dtype
+            route, kernel_bwd = fused.training_route(self, get_compute_dtype(), img_z.numel(), chain_packs=False)
+            if route == 'fused':
+                return fused.transformer_forward_train(self, img_z, kernel_bwd)     # training forward on the fused kernels
         x = Fw.embed_tokens(img_z, self.embedding.weight, self.pos_emb_s.weight, self.pos_emb_h.weight,
                             self.pos_emb_w.weight)
         for attn, ff in self.layers:

@@ -424,16 +424,17 @@ class _TrainerBase(_AdamState):
         if dt == torch.float32 or not self.arena.flat_param.is_cuda:
             return bulk                                  # parity mode: weights are used as they are, transposes per use
         tr = self.model.transformer
-        from . import config, fused
-        # the default-width denoiser trains on the fused per-token kernels in both directions: they read their own packed
-        # weight streams (fused._layer_pack / _layer_pack_bwd), none of the per-layer operand copies below
+        from . import fused
         layers = list(tr.layers)
-        if hasattr(tr, 'pos_emb_s') and fused.supported(tr, dt) and config.get_fused_training() and config.fused_backward():
+        packs = fused.training_packs(tr, dt)
+        if packs == 'fused':
+            # the default-width denoiser trains on the fused per-token kernels in both directions: they read their own packed
+            # weight streams (fused._layer_pack / _layer_pack_bwd), none of the per-layer operand copies below
             layers = []
             self.packs = fused.PackSet(tr)
-        elif hasattr(tr, 'pos_emb_s') and fused.chain_supported(tr, dt) and config.get_fused_training():
-            # the reference's published widths: training FORWARD on the chain kernel (one gather rebuilds every launch's weight
-            # stream); the backward runs op by op and keeps reading the per-layer operand copies registered below
+        elif packs == 'chain':
+            # the chain kernels' widths: one gather rebuilds every launch's weight stream; where the chain kernels do not pay, or
+            # without their backward kernels, the op-by-op path reads the per-layer operand copies registered below
             try:
                 self.chain_packs = fused.ChainPackSet(tr, self.arena)
             except fused.ChainLayoutError:
@@ -628,24 +629,17 @@ class DenoiserTrainer(_TrainerBase):
         from . import config, fused
         m = self.model
         tr = m.transformer
-        dt = config.get_compute_dtype()
-        if (batch_z.is_cuda and hasattr(tr, 'pos_emb_s') and config.get_fused_training() and config.fused_backward()
-                and fused.supported(tr, dt) and batch_z.numel() % 32 == 0):
-            # fused stack in both directions: only the last plane leaves it (main.py:37), its logits and cross-entropy are
-            # one chunked linear + CE whose gradient is complete when the forward returns
+        route, kernel_bwd = fused.training_route(tr, config.get_compute_dtype(), batch_z.numel(), self.chain_packs is not None)
+        if batch_z.is_cuda and (route == 'chain' or (route == 'fused' and kernel_bwd)):
+            # the stack as one node: only the last plane leaves it (main.py:37), its logits and cross-entropy are one chunked
+            # linear + CE whose gradient is complete when the forward returns.  (The fused forward under the op-by-op backward
+            # takes the module path below.)
             tr.check_grid(batch_z)
-            last = fused.transformer_forward_train(tr, batch_z, last_only=True)              # [B, H, W, D]
+            last = fused.transformer_forward_train(tr, batch_z, kernel_bwd, self.chain_packs if route == 'chain' else None,
+                                                   last_only=True)                          # [B, H, W, D]
             mean, rows = linear_cross_entropy(last.reshape(-1, last.shape[-1]), m.logit_proj.weight, m.logit_proj.bias,
                                               target.reshape(-1), chunk=4096, grad_scale=loss_scale)
             mean.backward()                                # (the accumulation scale is inside the fused gradient)
-            return rows.view(batch_z.shape[0], -1).mean(dim=1), mean.detach()
-        if (batch_z.is_cuda and self.chain_packs is not None and config.get_fused_training()
-                and fused.chain_pays(self.chain_packs.widths, batch_z.numel(), True)):
-            tr.check_grid(batch_z)
-            last = fused.transformer_forward_chain_train(tr, self.chain_packs, batch_z, last_only=True)    # [B, H, W, D]
-            mean, rows = linear_cross_entropy(last.reshape(-1, last.shape[-1]), m.logit_proj.weight, m.logit_proj.bias,
-                                              target.reshape(-1), chunk=4096, grad_scale=loss_scale)
-            mean.backward()
             return rows.view(batch_z.shape[0], -1).mean(dim=1), mean.detach()
         y = m(batch_z)
         loss = cross_entropy_rows(y.reshape(-1, self.C), target.reshape(-1))
