@@ -25,11 +25,13 @@
 extern "C" {
 #endif
 
-#define WMZ_VERSION 114
+#define WMZ_VERSION 115
 
 enum { WMZ_F32 = 0, WMZ_BF16 = 1,
        WMZ_F16 = 2 /* IEEE half activations / MFMA operands: the PRECISE fused inference mode (wmz_local3d_attn_fwd* on the
-                      16- / 8-wide-plane fast path and the *_f16 per-token entry points below); other entry points refuse it */ };
+                      16- / 8-wide-plane fast path and the *_f16 per-token entry points below; the conv encoder / decoder's
+                      inference route: the *_f16 conv entry points and the element-wise ones that say so); other entry points
+                      refuse it */ };
 enum { WMZ_OK = 0, WMZ_ERR_ARG = 1, WMZ_ERR_HIP = 2, WMZ_ERR_UNSUPPORTED = 3 };
 
 /* epilogue / prologue flags of wmz_linear_fwd */
@@ -555,6 +557,25 @@ int wmz_affine_act_nhwc_bn(const void* a, const float* sa, const float* ta, cons
 int wmz_dilate_nhwc(const void* dy, void* dz, int B, int Ho, int Wo, int C, int Hz, int Wz, int stride, int dtype, void* stream);
 /* F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) (autoencoder.py:138) on NHWC. */
 int wmz_bilinear2x_nhwc(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
+
+/* ---- the conv encoder / decoder's half inference route (the precise mode with config.precise_conv on).  The reference computes
+ * these layers in fp32 (autoencoder.py:8-15 conv3x3 / conv1x1 inside Residual :18-42, the 2x2 / stride 2 down-sampling :29-33,
+ * SimpleResidualEncoder's conv_1 :60-86, UpscaleResidual :89-131, SimpleResidualDecoder :134-152); bf16 operands leave the latents
+ * 2e-2 from it, the fp32 route (wmz_conv2d_nhwc_fwd_pre, dtype WMZ_F32) runs the exact-f32 MFMA at 1/16 of the matrix rate.
+ * Contracts as the entry points without the suffix, every `bf16` there read as `half`: x, residual and out half; bias, scale,
+ * shift and the statistics fp32 (the statistics are those of the stored, rounded half output).  The weight streams come from the
+ * bfloat16 entry points (wmz_conv3x3_direct_pack / wmz_conv_point_pack only move 16-byte chunks: given a half operand they write a
+ * half stream), the shape queries too (wmz_conv3x3_direct_supported_strided, wmz_conv_point_supported).  Inference only: no
+ * backward entry point takes half.  Values beyond +-65504 become infinities.
+ * Element-wise entry points that also take WMZ_F16: wmz_nchw_to_nhwc8 as out_dtype (fp32 frames in), wmz_channel_stats_nhwc,
+ * wmz_affine_act_nhwc, wmz_affine_act_nhwc_bn / wmz_affine_act_bn_supported and wmz_bilinear2x_nhwc. */
+int wmz_conv3x3_direct_fwd_strided_f16(const void* x, const void* wpack, void* out, const float* bias, const float* scale,
+                                       const float* shift, const void* residual, float* stat_sum, float* stat_sq, int B, int H,
+                                       int W, int Cin, int Cout, int stride, int leaky, float slope, void* stream);
+int wmz_conv_point_fwd_bn_f16(const void* x, const void* wpack, void* out, const float* bias, const float* scale, const float* shift,
+                              float* stat_sum, float* stat_sq, const float* in_scale, const float* in_shift,
+                              const wmz_bn_stats* in_bn, float in_slope, int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW,
+                              int stride, int pad, int leaky, float slope, void* stream);
 
 /* ---- backward of the conv path (VQ-AE training, train_vqae.py:125-192; the reference gets these from autograd) ----
  * data gradient: wmz_conv2d_nhwc_fwd_pre on the (zero-dilated for stride 2) output gradient with flipped, transposed weights.

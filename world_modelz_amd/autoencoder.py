@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _cast, ops
+from . import _cast, config, ops
 from ._lib import WmzError
 from .config import get_compute_dtype
 
@@ -58,7 +58,8 @@ def _to_nhwc(x, dtype):
     """logical NCHW (any memory format) -> contiguous [B,H,W,C8] in the compute dtype."""
     if not x.is_cuda:
         raise WmzError('the conv encoder/decoder runs on the GPU only (no CPU fallback)')
-    if (x.dim() == 4 and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16) and not (torch.is_grad_enabled() and x.requires_grad)):
+    if (x.dim() == 4 and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16) and not (torch.is_grad_enabled() and x.requires_grad)
+            and (dtype != torch.float16 or x.dtype == torch.float32)):
         return ops.nchw_to_nhwc8(x, dtype)                         # flip + channel pad + cast in one launch
     x = x.permute(0, 2, 3, 1)
     c = x.shape[-1]
@@ -77,6 +78,59 @@ def _grad_path(x, *mods):
     block is trainable, or the INPUT carries a gradient (a frozen block inside a trainable encoder must still pass the
     gradient on to the layers in front of it)."""
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in mods for p in m.parameters()))
+
+
+def _pass_convs(module, shape):
+    """(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad, residual, prologue) -- ops.conv_family's arguments -- of every convolution a no-gradient forward_nhwc of `module` (a
+    SimpleResidualEncoder on NCHW frames of `shape`, or a SimpleResidualDecoder on NHWC latents of `shape`) launches, in the
+    form the forward passes hand them to ops.conv2d_nhwc (channels padded to 8)."""
+    out = []
+
+    def conv(B, H, W, m, residual=False, pre=False):
+        k, st, pd = m.kernel_size[0], m.stride[0], m.padding[0]
+        out.append((B, H, W, _pad8(m.in_channels), _pad8(m.out_channels), k, k, st, pd, residual, pre))
+        return (H + 2 * pd - k) // st + 1, (W + 2 * pd - k) // st + 1
+
+    if isinstance(module, SimpleResidualEncoder):
+        B, _, H, W = shape
+        H, W = conv(B, H, W, module._conv_1)
+        for blk in module._residual_stack._stack:
+            c1, bn1, c2 = blk._block[0], blk._block[1], blk._block[3]
+            Ho, Wo = conv(B, H, W, c1)
+            # (training-mode BatchNorm: bn1 + LeakyReLU ride in c2's prologue; eval: the skip add rides in c2's epilogue)
+            conv(B, Ho, Wo, c2, residual=not bn1.training, pre=bn1.training)
+            if blk.downsample is not None:
+                conv(B, H, W, blk.downsample[0])
+            H, W = Ho, Wo
+    elif isinstance(module, SimpleResidualDecoder):
+        B, H, W, _ = shape
+        mods = list(module.decoder_stack)
+        conv(B, H, W, mods[0])
+        for m in mods[1:-1]:
+            if m.upsample:
+                H, W = 2 * H, 2 * W
+            conv(B, H, W, m.conv1)
+            if m.learn_conv_residual:
+                conv(B, H, W, m.conv_residual)
+            conv(B, H, W, m.conv2, residual=True)
+        conv(B, H, W, mods[-1])
+    else:
+        raise TypeError(f'conv_route: a SimpleResidualEncoder or SimpleResidualDecoder, not {type(module).__name__}')
+    return out
+
+
+def conv_route(module, shape, grad=False):
+    """The dtype ONE forward_nhwc pass of `module` (SimpleResidualEncoder on NCHW frames of `shape` / SimpleResidualDecoder on NHWC
+    latents of `shape`) runs in -- decided once per call, for the whole pass.  The compute dtype, except in the precise mode with
+    config.precise_conv on: float16 when every convolution of the pass has a half kernel (ops.conv_family 'direct' or 'point'),
+    else the precise mode's fp32 route for all of it (never a mix, never bf16).  grad (a forward with a gradient path: VQ-AE
+    training, gradients through an encoder) keeps the compute dtype: there is no half backward."""
+    dt = get_compute_dtype()
+    if grad or not config.conv_half():
+        return dt
+    if all(ops.conv_family(*g) != 'gemm' for g in _pass_convs(module, shape)):
+        return torch.float16
+    return dt
 
 
 def _wT_op(weight, dtype):
@@ -367,10 +421,12 @@ class SimpleResidualEncoder(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def forward_nhwc(self, x):
-        """NCHW frames -> [B,h,w,E] latents (what VectorQuantizerEMA wants: no NCHW<->NHWC flips)."""
-        dt = get_compute_dtype()
+        """NCHW frames -> [B,h,w,E] latents (what VectorQuantizerEMA wants: no NCHW<->NHWC flips), in the pass's dtype
+        (conv_route: the compute dtype, or float16 on the precise mode's half conv route)."""
+        grad = _grad_path(x, self)
+        dt = conv_route(self, x.shape, grad)
         with ops.stat_arena():                                     # (one zero fill for every BatchNorm statistic of the pass)
-            if _grad_path(x, self):
+            if grad:
                 h = F.leaky_relu(_conv_g(_to_nhwc(x, dt), self._conv_1), LEAKY)
             else:
                 h = _conv(_to_nhwc(x, dt), self._conv_1, dt, leaky=True, slope=LEAKY)
@@ -447,10 +503,12 @@ class SimpleResidualDecoder(nn.Module):
 
     def forward_nhwc(self, h, raw=False):
         """[B,h,w,E] latents (NHWC, C % 8 == 0) -> logical NCHW image (raw: the last conv's NHWC output as it is, its channels
-        padded to a multiple of 8 -- what ops.recon_loss reads)."""
-        dt = get_compute_dtype()
+        padded to a multiple of 8 -- what ops.recon_loss reads), in the pass's dtype (conv_route; the latents are cast to it)."""
         mods = list(self.decoder_stack)
         grad = _grad_path(h, self)
+        dt = conv_route(self, h.shape, grad)
+        if h.dtype != dt:
+            h = h.to(dt).contiguous()
         with ops.stat_arena():
             h = _conv_g(h, mods[0]) if grad else _conv(h, mods[0], dt)
             for m in mods[1:-1]:
@@ -465,4 +523,6 @@ class SimpleResidualDecoder(nn.Module):
             return _to_nchw_view(y)[:, :mods[-1].out_channels]      # (the operand's output channels are padded to 8)
 
     def forward(self, x):
-        return self.forward_nhwc(_to_nhwc(x, get_compute_dtype())).to(x.dtype)
+        B, C, H, W = x.shape
+        dt = conv_route(self, (B, H, W, _pad8(C)), _grad_path(x, self))
+        return self.forward_nhwc(_to_nhwc(x, dt)).to(x.dtype)

@@ -14,7 +14,8 @@ _DTYPES = {'bf16': torch.bfloat16, 'bfloat16': torch.bfloat16, 'fp32': torch.flo
 #   float16 the PRECISE fused mode: inference at the default widths runs the fused kernels with IEEE-half MFMA operands and a half
 #           residual stream between the layers (~5e-4 at the bf16 speed: inside the 1e-3 BASELINE.json asks for); everything the
 #           half kernels are not built for (training, widths other than the default and the published ones, planes outside the row
-#           attention kernel's shapes, the conv encoder / decoder) runs the fp32 route -- never bf16.
+#           attention kernel's shapes, the conv encoder / decoder) runs the fp32 route -- never bf16.  The conv encoder / decoder
+#           has a half route of its own, opt-in: precise_conv below.
 _precise = False
 _compute_dtype = None
 
@@ -55,6 +56,40 @@ def compute_dtype(dt):
         yield
     finally:
         set_compute_dtype(prev)
+
+
+# The conv encoder / decoder in the precise mode.  Off (default): fp32, the route the precise mode gives everything off the half
+# kernels (latents ~5e-4 from the fp32 reference, exact-f32 MFMA at 1/16 of the matrix rate).  On: an encoder / decoder forward
+# without a gradient path runs in IEEE half on csrc/conv_direct_f16.hip and conv_point_f16.hip (the bf16 route's kernels and speed,
+# 3 more significand bits) when every layer of the pass has a half kernel, else the whole pass stays fp32
+# (autoencoder.conv_route).  The two routes trade accuracy for speed, and nothing in the input says which one a caller wants: hence
+# a switch.  Half holds +-65504: activations beyond that become infinities (no overflow check).  No effect in the bf16 and fp32
+# modes, nor on training (VQ-AE training and gradients through an encoder run the fp32 route).
+_precise_conv = os.environ.get('WMZ_PRECISE_CONV', '0') != '0'
+
+
+def get_precise_conv():
+    return _precise_conv
+
+
+def set_precise_conv(on):
+    global _precise_conv
+    _precise_conv = bool(on)
+
+
+@contextlib.contextmanager
+def precise_conv(on):
+    prev = get_precise_conv()
+    set_precise_conv(on)
+    try:
+        yield
+    finally:
+        set_precise_conv(prev)
+
+
+def conv_half():
+    """True when the conv encoder / decoder's inference passes may take the half route: the precise mode with precise_conv on."""
+    return _precise and _precise_conv
 
 
 # Inference only: the denoiser returns the last frame's logits (reference main.py:33-36), so the planes outside the

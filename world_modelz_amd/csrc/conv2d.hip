@@ -44,6 +44,18 @@ template <> __device__ __forceinline__ void chunk_to_f32<bf16_t>(const i32x4& c,
     f[2 * i + 1] = __uint_as_float(((unsigned)c[i]) & 0xFFFF0000u);
   }
 }
+// IEEE half by name (the precise mode's inference route: channel_stats / affine_act / bilinear2x take WMZ_F16); this unit's
+// bfloat16 forms stay on the unit's primitives
+template <> __device__ __forceinline__ void chunk_to_f32<_Float16>(const i32x4& c, float* f) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    // (through a scalar copy: a bit_cast straight from the vector element c[i] read element 0 for every i)
+    const unsigned w = (unsigned)c[i];
+    const f32x2 v = __builtin_convertvector(__builtin_bit_cast(f16x2_t, w), f32x2);
+    f[2 * i] = v[0];
+    f[2 * i + 1] = v[1];
+  }
+}
 template <typename T> __device__ __forceinline__ i32x4 f32_to_chunk(const float* f);
 template <> __device__ __forceinline__ i32x4 f32_to_chunk<float>(const float* f) {
   i32x4 c;
@@ -55,6 +67,12 @@ template <> __device__ __forceinline__ i32x4 f32_to_chunk<bf16_t>(const float* f
   i32x4 c;
 #pragma unroll
   for (int i = 0; i < 4; ++i) c[i] = (int)((unsigned)f32_to_bf16_bits(f[2 * i]) | ((unsigned)f32_to_bf16_bits(f[2 * i + 1]) << 16));
+  return c;
+}
+template <> __device__ __forceinline__ i32x4 f32_to_chunk<_Float16>(const float* f) {
+  i32x4 c;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) c[i] = (int)__builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){f[2 * i], f[2 * i + 1]}, f16x2_t));
   return c;
 }
 
@@ -880,7 +898,7 @@ __global__ __launch_bounds__(256) void bilinear2x_bwd_vec_kernel(const T* __rest
 
 // vector forms apply: C a multiple of the vector width, channel groups dividing the workgroup, 16-byte aligned tensors
 static bool vec_ok(int C, int dtype, std::initializer_list<const void*> ptrs) {
-  const int VW = dtype == WMZ_BF16 ? 8 : 4;
+  const int VW = dtype == WMZ_F32 ? 4 : 8;
   if (C % VW != 0 || 256 % (C / VW) != 0) return false;
   for (const void* q : ptrs) if (q != nullptr && (((uintptr_t)q) & 15) != 0) return false;
   return true;
@@ -940,19 +958,21 @@ extern "C" int wmz_conv2d_nhwc_fwd_pre(const void* x, const void* w, void* out, 
 
 extern "C" int wmz_channel_stats_nhwc(const void* x, long M, int C, float* sum, float* sq, int dtype, void* stream) {
   WMZ_REQUIRE(x && sum && sq && M > 0 && C > 0, "wmz_channel_stats_nhwc: bad arguments");
-  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_channel_stats_nhwc: bad dtype %d", dtype);
+  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16 || dtype == WMZ_F16, "wmz_channel_stats_nhwc: bad dtype %d", dtype);
   if (vec_ok(C, dtype, {x})) {
-    const int VW = dtype == WMZ_BF16 ? 8 : 4;
+    const int VW = dtype == WMZ_F32 ? 4 : 8;
     const long nvec = M * C / VW;
     const int gridv = grid_for(nvec, RED_NT * 4, 256);
-    if (dtype == WMZ_BF16) hipLaunchKernelGGL(channel_stats_vec_kernel<bf16_t>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const bf16_t*)x, nvec, C, sum, sq);
+    if (dtype == WMZ_F16) hipLaunchKernelGGL(channel_stats_vec_kernel<_Float16>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const _Float16*)x, nvec, C, sum, sq);
+    else if (dtype == WMZ_BF16) hipLaunchKernelGGL(channel_stats_vec_kernel<bf16_t>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const bf16_t*)x, nvec, C, sum, sq);
     else hipLaunchKernelGGL(channel_stats_vec_kernel<float>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const float*)x, nvec, C, sum, sq);
     WMZ_LAUNCH_CHECK("wmz_channel_stats_nhwc");
     return WMZ_OK;
   }
   dim3 grid((unsigned)grid_for(M, 64, 512), (unsigned)wmz_cdiv(C, 64));
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16) hipLaunchKernelGGL(channel_stats_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, M, C, sum, sq);
+  if (dtype == WMZ_F16) hipLaunchKernelGGL(channel_stats_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16*)x, M, C, sum, sq);
+  else if (dtype == WMZ_BF16) hipLaunchKernelGGL(channel_stats_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, M, C, sum, sq);
   else hipLaunchKernelGGL(channel_stats_kernel<float>, grid, dim3(256), 0, st, (const float*)x, M, C, sum, sq);
   WMZ_LAUNCH_CHECK("wmz_channel_stats_nhwc");
   return WMZ_OK;
@@ -972,8 +992,8 @@ extern "C" int wmz_bn_finalize(const float* sum, const float* sq, double count, 
 }
 
 extern "C" int wmz_affine_act_bn_supported(int C, int dtype) {
-  const int VW = dtype == WMZ_BF16 ? 8 : 4;
-  return (dtype == WMZ_F32 || dtype == WMZ_BF16) && C > 0 && C % VW == 0 && 256 % (C / VW) == 0 ? 1 : 0;
+  const int VW = dtype == WMZ_F32 ? 4 : 8;
+  return (dtype == WMZ_F32 || dtype == WMZ_BF16 || dtype == WMZ_F16) && C > 0 && C % VW == 0 && 256 % (C / VW) == 0 ? 1 : 0;
 }
 
 extern "C" int wmz_affine_act_nhwc_bn(const void* a, const float* sa, const float* ta, const wmz_bn_stats* bna, const void* b,
@@ -981,17 +1001,19 @@ extern "C" int wmz_affine_act_nhwc_bn(const void* a, const float* sa, const floa
                                       float slope, int dtype, void* stream) {
   WMZ_REQUIRE(a && y && M > 0 && C > 0 && C % 4 == 0, "wmz_affine_act_nhwc: bad arguments (C %% 4 == 0 required)");
   WMZ_REQUIRE((sa == nullptr) == (ta == nullptr) && (sb == nullptr) == (tb == nullptr), "wmz_affine_act_nhwc: scale/shift pairs");
-  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_affine_act_nhwc: bad dtype %d", dtype);
+  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16 || dtype == WMZ_F16, "wmz_affine_act_nhwc: bad dtype %d", dtype);
   WMZ_REQUIRE(bn_stats_ok(bna) && bn_stats_ok(bnb) && (bnb == nullptr || b != nullptr), "wmz_affine_act_nhwc_bn: incomplete wmz_bn_stats");
   const long total = M * C;
   hipStream_t st = (hipStream_t)stream;
-  const int VW = dtype == WMZ_BF16 ? 8 : 4;
+  const int VW = dtype == WMZ_F32 ? 4 : 8;
   const bool aligned = (((uintptr_t)a | (uintptr_t)y | (uintptr_t)(b ? b : a)) & 15) == 0;
   if (C % VW == 0 && aligned && 256 % (C / VW) == 0) {
     // every thread keeps its channel group: the grid stride (grid * 256 vectors) is a multiple of C / VW since 256 is
     const long nvec = total / VW;
     const int gridv = grid_for(nvec, 256, EW_GRID);
-    if (dtype == WMZ_BF16)
+    if (dtype == WMZ_F16)
+      hipLaunchKernelGGL(affine_act_vec_kernel<_Float16>, dim3(gridv), dim3(256), (size_t)4 * C * sizeof(float), st, (const _Float16*)a, sa, ta, (const _Float16*)b, sb, tb, (_Float16*)y, nvec, C, leaky, slope, bn_stats_from(bna), bn_stats_from(bnb));
+    else if (dtype == WMZ_BF16)
       hipLaunchKernelGGL(affine_act_vec_kernel<bf16_t>, dim3(gridv), dim3(256), (size_t)4 * C * sizeof(float), st, (const bf16_t*)a, sa, ta, (const bf16_t*)b, sb, tb, (bf16_t*)y, nvec, C, leaky, slope, bn_stats_from(bna), bn_stats_from(bnb));
     else
       hipLaunchKernelGGL(affine_act_vec_kernel<float>, dim3(gridv), dim3(256), (size_t)4 * C * sizeof(float), st, (const float*)a, sa, ta, (const float*)b, sb, tb, (float*)y, nvec, C, leaky, slope, bn_stats_from(bna), bn_stats_from(bnb));
@@ -1000,7 +1022,9 @@ extern "C" int wmz_affine_act_nhwc_bn(const void* a, const float* sa, const floa
   }
   WMZ_REQUIRE(bna == nullptr && bnb == nullptr, "wmz_affine_act_nhwc_bn: raw BatchNorm statistics need the 16-byte kernel (wmz_affine_act_bn_supported, 16-byte aligned tensors)");
   const int grid = grid_for(total, 1024, 4096);
-  if (dtype == WMZ_BF16)
+  if (dtype == WMZ_F16)
+    hipLaunchKernelGGL(affine_act_kernel<_Float16>, dim3(grid), dim3(256), 0, st, (const _Float16*)a, sa, ta, (const _Float16*)b, sb, tb, (_Float16*)y, total, C, leaky, slope);
+  else if (dtype == WMZ_BF16)
     hipLaunchKernelGGL(affine_act_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)a, sa, ta, (const bf16_t*)b, sb, tb, (bf16_t*)y, total, C, leaky, slope);
   else
     hipLaunchKernelGGL(affine_act_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)a, sa, ta, (const float*)b, sb, tb, (float*)y, total, C, leaky, slope);
@@ -1033,19 +1057,21 @@ extern "C" int wmz_dilate_nhwc(const void* dy, void* dz, int B, int Ho, int Wo, 
 
 extern "C" int wmz_bilinear2x_nhwc(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream) {
   WMZ_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0, "wmz_bilinear2x_nhwc: bad arguments");
-  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_bilinear2x_nhwc: bad dtype %d", dtype);
+  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16 || dtype == WMZ_F16, "wmz_bilinear2x_nhwc: bad dtype %d", dtype);
   const long total = (long)B * 4 * H * W * C;
   if (vec_ok(C, dtype, {x, y})) {
-    const int VW = dtype == WMZ_BF16 ? 8 : 4;
+    const int VW = dtype == WMZ_F32 ? 4 : 8;
     const int gridv = grid_for(total / VW, 256, 8192);
-    if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_vec_kernel<bf16_t>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
+    if (dtype == WMZ_F16) hipLaunchKernelGGL(bilinear2x_vec_kernel<_Float16>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, (_Float16*)y, B, H, W, C);
+    else if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_vec_kernel<bf16_t>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
     else hipLaunchKernelGGL(bilinear2x_vec_kernel<float>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, B, H, W, C);
     WMZ_LAUNCH_CHECK("wmz_bilinear2x_nhwc");
     return WMZ_OK;
   }
   const int grid = grid_for(total, 256, 8192);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
+  if (dtype == WMZ_F16) hipLaunchKernelGGL(bilinear2x_kernel<_Float16>, dim3(grid), dim3(256), 0, st, (const _Float16*)x, (_Float16*)y, B, H, W, C);
+  else if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
   else hipLaunchKernelGGL(bilinear2x_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C);
   WMZ_LAUNCH_CHECK("wmz_bilinear2x_nhwc");
   return WMZ_OK;

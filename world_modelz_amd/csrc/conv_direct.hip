@@ -1,5 +1,8 @@
 // Direct 3x3 (pad 1, stride 1 or 2) convolution of the VQ auto-encoder's conv encoder / decoder (vq-video-diffusion/autoencoder.py:8-15
-// conv3x3 inside Residual :18-42, UpscaleResidual :89-131, SimpleResidualDecoder :134-152) in bf16, NHWC, for gfx950.
+// conv3x3 inside Residual :18-42, UpscaleResidual :89-131, SimpleResidualDecoder :134-152) in bf16, NHWC, for gfx950.  The 16-bit
+// operand format is the translation unit's (wmz_common.h: the MFMA, the epilogue's packing and every re-read of a rounded value go
+// through the op16_* primitives): conv_direct_f16.hip compiles this file again in IEEE half -- wmz_conv3x3_direct_fwd_strided_f16,
+// the precise mode's inference route; the format-agnostic entry points (support queries, the weight pack, knobs) exist once, here.
 //
 // Same GEMM and the same epilogue arithmetic as conv2d.hip's implicit-GEMM kernel (C[px, co] = sum_k A[px, k] W[co, k], k tap-major),
 // re-staged around the LDS-DMA engine:
@@ -16,7 +19,7 @@
 // Two workgroups per CU (<= 80 KB of LDS each): one computes while the other loads its patch or stores its tile.
 #include "wmz_common.h"
 #include "wmz_debug.h"
-#ifdef WMZ_CONV_STAMPS         // diagnostic build (tools/build_variant.py -DWMZ_CONV_STAMPS): s_memtime stamps of wave 0 of every workgroup of
+#if defined(WMZ_CONV_STAMPS) && !defined(WMZ_OP16_F16)       // diagnostic build (tools/build_variant.py -DWMZ_CONV_STAMPS): s_memtime stamps of wave 0 of every workgroup of
                                // convr_kernel + the CU it ran on (tools/conv_stamps.py)
 __device__ unsigned long long conv_stamps[8192 * 8];
 #define CONV_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < 8192) conv_stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
       constexpr int n = decltype(nc)::value, kk = n / NPB, i = n % NPB;
       if constexpr (i == 0) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(bq[s & 1][kk]) : "n"(2 * KS - 1) : "memory");
       lgkm_wait_for<WIN - 1>(fr[n % WIN]);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[n % WIN], bq[s & 1][kk], acc[i], 0, 0, 0);
+      acc[i] = op16_mfma_32x32x16(fr[n % WIN], bq[s & 1][kk], acc[i]);
       if constexpr (n + WIN < NSEQ) read_n(sc, std::integral_constant<int, n + WIN>{});
       else read_n(std::integral_constant<int, s + 1>{}, std::integral_constant<int, n + WIN - NSEQ>{});    // next tap
 #if WMZ_CONV_ABL & 2
@@ -271,7 +274,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
 
   // ------------------------------------------------------------------------------------------------ epilogue
   CONV_STAMP(3);
-  if (P.dbg & 1) { if (acc[0][0] == 12345.f) P.out[0] = __float2bfloat16(acc[1][3]); return; }
+  if (P.dbg & 1) { if (acc[0][0] == 12345.f) P.out[0] = __builtin_bit_cast(bf16_t, f32_to_bf16_bits(acc[1][3])); return; }
   __syncthreads();                                                 // every wave is done with the patch: its LDS is the staging space
   CONV_STAMP(4);
   char* const stage = lds + wave * S::STAGE;
@@ -311,11 +314,11 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
             float v0 = acc[r * S::BPR + ib][reg] + cbias, v1 = acc[r * S::BPR + ib][reg + 1] + cbias;
             if constexpr (AFF) { v0 = v0 * cscale + cshift; v1 = v1 * cscale + cshift; }
             if constexpr (LEAKY) { v0 = fmaxf(v0, v0 * P.slope); v1 = fmaxf(v1, v1 * P.slope); }
-            const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){v0, v1}, bf16x2_t));
+            const unsigned pk = op16_pack2(v0, v1);
             *reinterpret_cast<unsigned short*>(wpos + rl * S::OPITCH) = (unsigned short)pk;
             *reinterpret_cast<unsigned short*>(wpos + (rl + 1) * S::OPITCH) = (unsigned short)(pk >> 16);
             if constexpr (STATS) {                                  // statistics of what the next stage will read
-              const f32x2 q = {__uint_as_float(pk << 16), __uint_as_float(pk & 0xFFFF0000u)};
+              const f32x2 q = op16_unpack2(pk);
               s1 += q;
               s2 = q * q + s2;
             }
@@ -396,8 +399,9 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
           float f[8] = {va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            f[2 * e] += __uint_as_float(((unsigned)rv[it][e]) << 16);
-            f[2 * e + 1] += __uint_as_float(((unsigned)rv[it][e]) & 0xFFFF0000u);
+            const f32x2 r = op16_unpack2((unsigned)rv[it][e]);
+            f[2 * e] += r[0];
+            f[2 * e + 1] += r[1];
           }
           if (P.leaky) {
 #pragma unroll
@@ -406,12 +410,13 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
           i32x4 pk;
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            pk[e] = (int)__builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){f[2 * e], f[2 * e + 1]}, bf16x2_t));
+            pk[e] = (int)op16_pack2(f[2 * e], f[2 * e + 1]);
           *reinterpret_cast<i32x4*>(const_cast<bf16_t*>(group_ptr(P.out, 32 * (i0 + 2 * r) + 16 * it))) = pk;
           if (want_stats) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float q0 = __uint_as_float(((unsigned)pk[e]) << 16), q1 = __uint_as_float(((unsigned)pk[e]) & 0xFFFF0000u);
+              const f32x2 q = op16_unpack2((unsigned)pk[e]);
+              const float q0 = q[0], q1 = q[1];
               s1[2 * e] += q0; s2[2 * e] = fmaf(q0, q0, s2[2 * e]);
               s1[2 * e + 1] += q1; s2[2 * e + 1] = fmaf(q1, q1, s2[2 * e + 1]);
             }
@@ -435,6 +440,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
   CONV_STAMP(5);
 }
 
+#ifndef WMZ_OP16_F16
 // GEMM operand [Cout, 9 * Cin] (tap-major, channels inside: autoencoder.py:_w_op) -> the fragment-order stream convr_kernel's
 // waves read: [pass = Cin / 64][tap 9][k-step 4][Cout block of 32][lane 64][8]: lane (l31, hh) of fragment (pass, tap, kk, j) holds
 // W[32 j + l31][tap * Cin + 64 pass + 16 kk + 8 hh + 0..7]; rows past Cout are zero.
@@ -454,11 +460,14 @@ __global__ __launch_bounds__(256) void convq_pack_kernel(const bf16_t* __restric
   if (co < Cout) v = *reinterpret_cast<const i32x4*>(w + (long)co * 9 * Cin + k);
   *reinterpret_cast<i32x4*>(dst + i * 8) = v;
 }
+#endif
 
+// (the half unit has its own copy of the knobs, at their defaults: wmz_debug_conv_knobs reaches the bfloat16 unit's)
 static int g_conv_skew = 1, g_conv_dbg = 0;
 
 }  // namespace
 
+#ifndef WMZ_OP16_F16              // (format-agnostic: compiled once, in the bfloat16 unit)
 #ifdef WMZ_CONV_STAMPS
 extern "C" int wmz_debug_conv_stamps(unsigned long long* out, int n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(conv_stamps), (size_t)n * sizeof(unsigned long long));
@@ -489,6 +498,7 @@ extern "C" int wmz_conv3x3_direct_pack(const void* w_op, void* wpack, int Cin, i
   WMZ_LAUNCH_CHECK("wmz_conv3x3_direct_pack");
   return WMZ_OK;
 }
+#endif  // WMZ_OP16_F16
 
 // stride 1 (pad 1): output = input plane, 8 x 32 or 16 x 16 output tiles
 static int direct_fwd_s1(const void* x, const void* wpack, void* out, const float* bias, const float* scale, const float* shift,
@@ -529,13 +539,15 @@ static int direct_fwd_s1(const void* x, const void* wpack, void* out, const floa
 }
 
 // stride 2 (pad 1): H, W the INPUT plane (even); the output is H / 2 x W / 2.  Cout = 128, output planes of 8 k x 16 m pixels.
+#ifndef WMZ_OP16_F16
 extern "C" int wmz_conv3x3_direct_supported_strided(int H, int W, int Cin, int Cout, int stride) {
   if (stride == 1) return wmz_conv3x3_direct_supported(H, W, Cin, Cout);
   if (stride != 2 || (Cin != 64 && Cin != 128) || Cout != 128 || (H & 1) || (W & 1)) return 0;
   return ((H / 2) & 7) == 0 && ((W / 2) & 15) == 0;
 }
+#endif
 
-extern "C" int wmz_conv3x3_direct_fwd_strided(const void* x, const void* wpack, void* out, const float* bias, const float* scale,
+extern "C" int WMZ_FN(wmz_conv3x3_direct_fwd_strided)(const void* x, const void* wpack, void* out, const float* bias, const float* scale,
                                               const float* shift, const void* residual, float* stat_sum, float* stat_sq, int B,
                                               int H, int W, int Cin, int Cout, int stride, int leaky, float slope, void* stream) {
   if (stride == 1)

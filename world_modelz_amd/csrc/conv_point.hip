@@ -14,6 +14,10 @@
 //     BatchNorm statistics as lane-local sums kept in registers ACROSS runs -- one atomic per channel and workgroup per launch),
 //     the bf16 tile transposed through the same LDS image into 16-byte stores of whole contiguous rows.
 // Same arithmetic as conv2d.hip's kernel (k order, epilogue): the same bits; statistics to fp32 summation order.
+// The 16-bit operand format is the translation unit's (wmz_common.h op16_* primitives: the MFMA, the prologue's unpacking, the
+// epilogue's packing and its re-read for the statistics): conv_point_f16.hip compiles this file again in IEEE half --
+// wmz_conv_point_fwd_bn_f16.  The format-agnostic entry points (support query, weight pack, wmz_nchw_to_nhwc8) exist once, here:
+// the pack kernel only moves 16-byte chunks, so wmz_conv_point_pack serves both formats.
 #include "wmz_common.h"
 #include "bn_lazy.h"
 
@@ -148,8 +152,8 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
         for (int i = 0; i < NLD; ++i) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float y0 = fmaf(__uint_as_float(((unsigned)ld[i][e]) << 16), sc[2 * e], sh[2 * e]);
-            float y1 = fmaf(__uint_as_float(((unsigned)ld[i][e]) & 0xFFFF0000u), sc[2 * e + 1], sh[2 * e + 1]);
+            float y0 = fmaf(op16_lo_f32((unsigned)ld[i][e]), sc[2 * e], sh[2 * e]);
+            float y1 = fmaf(op16_hi_f32((unsigned)ld[i][e]), sc[2 * e + 1], sh[2 * e + 1]);
             y0 = y0 > 0.f ? y0 : y0 * P.in_slope;
             y1 = y1 > 0.f ? y1 : y1 * P.in_slope;
             ld[i][e] = (int)((unsigned)f32_to_bf16_bits(y0) | ((unsigned)f32_to_bf16_bits(y1) << 16));
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
 #pragma unroll
         for (int i = 0; i < NPB; ++i)
 #pragma unroll
-          for (int j = 0; j < NCB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < NCB; ++j) acc[i][j] = op16_mfma_32x32x16(af[i], bf[j], acc[i][j]);
         // (keeps hipcc from hoisting all four k-steps' fragments in front of the first MFMA: 16-24 fragments = 64-96 registers,
         //  which spilled; the LDS latency of a k-step is covered by the other waves of the CU -- the kernel is memory-bound)
         __builtin_amdgcn_sched_barrier(0);
@@ -205,11 +209,11 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
             float v0 = acc[i][j][reg] + cbias[j], v1 = acc[i][j][reg + 1] + cbias[j];
             if constexpr (AFF) { v0 = v0 * cscale[j] + cshift[j]; v1 = v1 * cscale[j] + cshift[j]; }
             if constexpr (LEAKY) { v0 = fmaxf(v0, v0 * P.slope); v1 = fmaxf(v1, v1 * P.slope); }
-            const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){v0, v1}, bf16x2_t));
+            const unsigned pk = op16_pack2(v0, v1);
             *reinterpret_cast<unsigned short*>(wp + rl * OP) = (unsigned short)pk;
             *reinterpret_cast<unsigned short*>(wp + (rl + 1) * OP) = (unsigned short)(pk >> 16);
             if constexpr (STATS) {                                  // statistics of what the next stage will read
-              const f32x2 q = {__uint_as_float(pk << 16), __uint_as_float(pk & 0xFFFF0000u)};
+              const f32x2 q = op16_unpack2(pk);
               s1[j] += q;
               s2[j] = q * q + s2[j];
             }
@@ -262,6 +266,7 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
   }
 }
 
+#ifndef WMZ_OP16_F16
 // GEMM operand [Cout, K] (K = KH KW Cin, tap-major) -> [k-step = ceil64(K) / 16][channel block ncb][lane 64][8]: lane (l31, hh) of
 // fragment (ks, j) holds W[32 j + l31][16 ks + 8 hh + 0..7]; zero past Cout / K.
 __global__ __launch_bounds__(256) void convp_pack_kernel(const bf16_t* __restrict__ w, bf16_t* __restrict__ dst, int K, int Cout, int ncb,
@@ -279,7 +284,8 @@ __global__ __launch_bounds__(256) void convp_pack_kernel(const bf16_t* __restric
   *reinterpret_cast<i32x4*>(dst + i * 8) = v;
 }
 
-// logical NCHW frames (contiguous, fp32 or bf16) -> NHWC with the channels zero-padded to a multiple of 8, in the compute dtype:
+// logical NCHW frames (contiguous, fp32 or bf16) -> NHWC with the channels zero-padded to a multiple of 8, in the compute dtype
+// (fp32, bf16, or half: the precise mode's conv route):
 // the layout flip + pad + cast in front of conv_1 (autoencoder.py:83) as ONE pass (F.pad + copy + cast were three launches,
 // 34 us for 256 frames of 64 x 64).  A thread owns one pixel and one group of 8 channels: plane reads coalesce along W, the
 // write is one 16-byte (bf16) / two 16-byte (fp32) chunks.
@@ -298,7 +304,12 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const TI* __restrict
     f[e] = c < C ? Elem<TI>::to_f32(x[(b * C + c) * HW + p]) : 0.f;
   }
   TO* const dst = y + pix * C8 + grp * 8;
-  if constexpr (sizeof(TO) == 2) {
+  if constexpr (std::is_same<TO, _Float16>::value) {              // (half by name: this kernel lives in the bfloat16 unit only)
+    i32x4 pk;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pk[e] = (int)__builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){f[2 * e], f[2 * e + 1]}, f16x2_t));
+    *reinterpret_cast<i32x4*>(dst) = pk;
+  } else if constexpr (sizeof(TO) == 2) {
     i32x4 pk;
 #pragma unroll
     for (int e = 0; e < 4; ++e) pk[e] = (int)((unsigned)f32_to_bf16_bits(f[2 * e]) | ((unsigned)f32_to_bf16_bits(f[2 * e + 1]) << 16));
@@ -308,11 +319,13 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const TI* __restrict
     *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){f[4], f[5], f[6], f[7]};
   }
 }
+#endif  // WMZ_OP16_F16
 
 int point_ncb(int Cout) { return Cout <= 64 ? 2 : 4; }
 
 }  // namespace
 
+#ifndef WMZ_OP16_F16              // (format-agnostic: compiled once, in the bfloat16 unit)
 extern "C" int wmz_conv_point_supported(int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad) {
   if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || (Cin & 7) != 0 || Cout <= 0 || Cout > 128 || (Cout & 7) != 0) return 0;
   if (KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || pad > 1 || Hi >= 32768 || Wi >= 32768) return 0;
@@ -337,9 +350,10 @@ extern "C" int wmz_conv_point_pack(const void* w_op, void* wpack, int K, int Cou
   WMZ_LAUNCH_CHECK("wmz_conv_point_pack");
   return WMZ_OK;
 }
+#endif  // WMZ_OP16_F16
 
 // in_bn (optional, HOST pointer to a wmz_bn_stats): the prologue's BatchNorm from its raw batch statistics (replaces in_scale / in_shift)
-extern "C" int wmz_conv_point_fwd_bn(const void* x, const void* wpack, void* out, const float* bias, const float* scale, const float* shift,
+extern "C" int WMZ_FN(wmz_conv_point_fwd_bn)(const void* x, const void* wpack, void* out, const float* bias, const float* scale, const float* shift,
                                      float* stat_sum, float* stat_sq, const float* in_scale, const float* in_shift,
                                      const wmz_bn_stats* in_bn, float in_slope, int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW,
                                      int stride, int pad, int leaky, float slope, void* stream) {
@@ -389,17 +403,21 @@ extern "C" int wmz_conv_point_fwd_bn(const void* x, const void* wpack, void* out
   return WMZ_OK;
 }
 
+#ifndef WMZ_OP16_F16
 extern "C" int wmz_nchw_to_nhwc8(const void* x, void* y, int B, int C, int H, int W, int in_dtype, int out_dtype, void* stream) {
   WMZ_REQUIRE(x && y && B > 0 && C > 0 && H > 0 && W > 0, "wmz_nchw_to_nhwc8: bad arguments");
-  WMZ_REQUIRE((in_dtype == WMZ_F32 || in_dtype == WMZ_BF16) && (out_dtype == WMZ_F32 || out_dtype == WMZ_BF16), "wmz_nchw_to_nhwc8: bad dtype");
+  WMZ_REQUIRE((in_dtype == WMZ_F32 || in_dtype == WMZ_BF16) && (out_dtype == WMZ_F32 || out_dtype == WMZ_BF16 || out_dtype == WMZ_F16), "wmz_nchw_to_nhwc8: bad dtype");
+  WMZ_REQUIRE(out_dtype != WMZ_F16 || in_dtype == WMZ_F32, "wmz_nchw_to_nhwc8: half output is built for fp32 frames");
   const int C8 = (C + 7) & ~7;
   const long HW = (long)H * W, total = (long)B * HW * (C8 >> 3);
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == WMZ_F32 && out_dtype == WMZ_BF16) hipLaunchKernelGGL((nchw_to_nhwc8_kernel<float, bf16_t>), grid, block, 0, st, (const float*)x, (bf16_t*)y, C, C8, HW, total);
+  if (out_dtype == WMZ_F16) hipLaunchKernelGGL((nchw_to_nhwc8_kernel<float, _Float16>), grid, block, 0, st, (const float*)x, (_Float16*)y, C, C8, HW, total);
+  else if (in_dtype == WMZ_F32 && out_dtype == WMZ_BF16) hipLaunchKernelGGL((nchw_to_nhwc8_kernel<float, bf16_t>), grid, block, 0, st, (const float*)x, (bf16_t*)y, C, C8, HW, total);
   else if (in_dtype == WMZ_F32) hipLaunchKernelGGL((nchw_to_nhwc8_kernel<float, float>), grid, block, 0, st, (const float*)x, (float*)y, C, C8, HW, total);
   else if (out_dtype == WMZ_BF16) hipLaunchKernelGGL((nchw_to_nhwc8_kernel<bf16_t, bf16_t>), grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, C, C8, HW, total);
   else hipLaunchKernelGGL((nchw_to_nhwc8_kernel<bf16_t, float>), grid, block, 0, st, (const bf16_t*)x, (float*)y, C, C8, HW, total);
   WMZ_LAUNCH_CHECK("wmz_nchw_to_nhwc8");
   return WMZ_OK;
 }
+#endif  // WMZ_OP16_F16

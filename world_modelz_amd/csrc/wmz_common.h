@@ -85,6 +85,15 @@ __device__ __forceinline__ f32x16 op16_mfma_32x32x16(const s16x8& a, const s16x8
 __device__ __forceinline__ f32x4 op16_mfma_16x16x16(const s16x4& a, const s16x4& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, a), __builtin_bit_cast(f16x4_t, b), c, 0, 0, 0);
 }
+// two floats -> the two 16-bit values of one dword (a in the low half), round-to-nearest-even: one v_cvt_pk_f16_f32
+__device__ __forceinline__ unsigned op16_pack2(float a, float b) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, f16x2_t));
+}
+// the two 16-bit values of a dword -> floats (low half first): two v_cvt_f32_f16 (the high half by op_sel)
+__device__ __forceinline__ f32x2 op16_unpack2(unsigned w) { return __builtin_convertvector(__builtin_bit_cast(f16x2_t, w), f32x2); }
+// one of them: the low / the high half (a caller that consumes the two at different places keeps its own instruction order)
+__device__ __forceinline__ float op16_lo_f32(unsigned w) { return (float)__builtin_bit_cast(f16x2_t, w)[0]; }
+__device__ __forceinline__ float op16_hi_f32(unsigned w) { return (float)__builtin_bit_cast(f16x2_t, w)[1]; }
 #else
 #define WMZ_FN(name) name
 constexpr int kOp16Dtype = WMZ_BF16;
@@ -114,6 +123,15 @@ __device__ __forceinline__ f32x16 op16_mfma_32x32x16(const s16x8& a, const s16x8
 __device__ __forceinline__ f32x4 op16_mfma_16x16x16(const s16x4& a, const s16x4& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
 }
+// two floats -> the two 16-bit values of one dword (a in the low half), round-to-nearest-even: one v_cvt_pk_bf16_f32
+__device__ __forceinline__ unsigned op16_pack2(float a, float b) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2_t));
+}
+// the two 16-bit values of a dword -> floats (low half first): a shift and a mask
+__device__ __forceinline__ f32x2 op16_unpack2(unsigned w) { return (f32x2){__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u)}; }
+// one of them: the low / the high half (a caller that consumes the two at different places keeps its own instruction order)
+__device__ __forceinline__ float op16_lo_f32(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float op16_hi_f32(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
 #endif
 
 template <typename T> struct Elem;
@@ -128,6 +146,15 @@ template <> struct Elem<bf16_t> {
   static constexpr int kPerChunk = 8;
   __device__ static __forceinline__ float to_f32(bf16_t v) { return bf16_bits_to_f32(__builtin_bit_cast(unsigned short, v)); }
   __device__ static __forceinline__ bf16_t from_f32(float v) { return __builtin_bit_cast(bf16_t, f32_to_bf16_bits(v)); }
+};
+
+// IEEE half by name, whatever the unit's 16-bit operand format: the element-wise kernels that take a WMZ_F16 dtype argument next to
+// WMZ_BF16 in one (bfloat16) unit -- conv2d.hip's, wmz_nchw_to_nhwc8's output
+template <> struct Elem<_Float16> {
+  static constexpr int kDtype = WMZ_F16;
+  static constexpr int kPerChunk = 8;
+  __device__ static __forceinline__ float to_f32(_Float16 v) { return (float)v; }
+  __device__ static __forceinline__ _Float16 from_f32(float v) { return (_Float16)v; }
 };
 
 // An MFMA operand fragment of 8 consecutive k-elements (lane-local).

@@ -126,6 +126,10 @@ class GraphedEncoder(GraphedForward):
 
         enc = GraphedEncoder(ae, example_frames)
         tokens = enc(frames)                               # [B, h, w] int64 (the runner's static output)
+
+    A captured encoder keeps the conv route it was captured with (autoencoder.conv_route: in the precise mode, the half route of
+    config.precise_conv or the fp32 one): toggling config.precise_conv afterwards does not re-capture it -- build a new one.  A
+    change of compute dtype does re-capture (the stamp holds the mode).
     """
 
     def __init__(self, ae, example_frames, warmup=2):

@@ -766,7 +766,7 @@ def _direct_pack(w_op, Cin, Cout):
 
     def build(w):
         n = L.lib().wmz_conv3x3_direct_pack_elems(Cin, Cout)
-        dst = torch.empty(n, dtype=torch.bfloat16, device=w.device)
+        dst = torch.empty(n, dtype=w.dtype, device=w.device)         # (the pack moves 16-byte chunks: bf16 or half alike)
         L.call('wmz_conv3x3_direct_pack', L.ptr(w), L.ptr(dst), Cin, Cout, L.stream())
         return dst
     return _cast.cached((w_op,), 'convq', build)
@@ -778,16 +778,34 @@ def _point_pack(w_op, K, Cout):
 
     def build(w):
         n = L.lib().wmz_conv_point_pack_elems(K, Cout)
-        dst = torch.empty(n, dtype=torch.bfloat16, device=w.device)
+        dst = torch.empty(n, dtype=w.dtype, device=w.device)
         L.call('wmz_conv_point_pack', L.ptr(w), L.ptr(dst), K, Cout, L.stream())
         return dst
     return _cast.cached((w_op,), 'convp', build)
 
 
+def conv_family(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad, residual=False, pre=False, slope=0.01):
+    """The kernel family conv2d_nhwc runs a 16-bit (bf16 or half) convolution of this geometry on: 'direct' (csrc/conv_direct.hip),
+    'point' (csrc/conv_point.hip) -- both have a half form -- or 'gemm' (the implicit-GEMM kernel: bf16 / fp32 only).  residual /
+    pre: the layer has a residual operand / an input prologue."""
+    if not DIRECT_CONV or not 0.0 <= slope <= 1.0:
+        return 'gemm'
+    lib = L.lib()
+    if KH == 3 and KW == 3 and pad == 1 and not pre and lib.wmz_conv3x3_direct_supported_strided(Hi, Wi, Cin, Cout, stride):
+        return 'direct'
+    if (not residual and lib.wmz_conv_point_supported(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad)
+            # (the streaming kernel's input prologue is built for 1x1 layers of <= 128 channels: wider hidden planes keep the
+            #  implicit-GEMM kernel's prologue)
+            and (not pre or (KH == 1 and KW == 1 and pad == 0 and Cin <= 128))):
+        return 'point'
+    return 'gemm'
+
+
 def conv2d_nhwc(x, w_op, KH, KW, stride, pad, bias=None, scale=None, shift=None, residual=None, leaky=False,
                 slope=0.01, stats=False, pre=None):
     """x: [B,H,W,Cin] contiguous (Cin % 8 == 0), w_op: [Cout, KH*KW*Cin] in x's dtype -> [B,Ho,Wo,Cout] (+ sum, sq: fp32
-    [STAT_REPLICAS, Cout] partial sums, summed by bn_finalize)."""
+    [STAT_REPLICAS, Cout] partial sums, summed by bn_finalize).  float16 (the precise mode's conv route) runs on the half forms of
+    the direct / streaming kernels and raises for a geometry they do not hold (conv_family)."""
     B, Hi, Wi, Cin = x.shape
     Cout = w_op.shape[0]
     assert x.is_contiguous() and w_op.is_contiguous() and w_op.shape[1] == KH * KW * Cin and w_op.dtype == x.dtype
@@ -799,19 +817,22 @@ def conv2d_nhwc(x, w_op, KH, KW, stride, pad, bias=None, scale=None, shift=None,
         s, q = _stat_pair(Cout, x.device)
     if residual is not None:
         assert residual.shape == out.shape and residual.is_contiguous() and residual.dtype == x.dtype
-    if (DIRECT_CONV and x.dtype == torch.bfloat16 and KH == 3 and KW == 3 and pad == 1 and pre is None and 0.0 <= slope <= 1.0
-            and L.lib().wmz_conv3x3_direct_supported_strided(Hi, Wi, Cin, Cout, stride)):
+    half = x.dtype == torch.float16
+    fam = (conv_family(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad, residual is not None, pre is not None, slope)
+           if x.dtype in (torch.bfloat16, torch.float16) else 'gemm')
+    if half and fam == 'gemm':
+        raise L.WmzError(f'conv2d_nhwc: no half kernel for B={B} {Hi}x{Wi} Cin={Cin} Cout={Cout} {KH}x{KW}/s{stride}/p{pad}'
+                         f'{" + residual" if residual is not None else ""}{" + prologue" if pre is not None else ""} '
+                         '(the precise conv route runs a pass in half only when every layer has one: autoencoder.conv_route)')
+    sfx = '_f16' if half else ''
+    if fam == 'direct':
         # csrc/conv_direct.hip: the haloed patch by LDS-DMA, decoupled waves (same arithmetic as the implicit-GEMM kernel)
-        L.call('wmz_conv3x3_direct_fwd_strided', L.ptr(x), L.ptr(_direct_pack(w_op, Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
+        L.call('wmz_conv3x3_direct_fwd_strided' + sfx, L.ptr(x), L.ptr(_direct_pack(w_op, Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
                L.ptr(shift), L.ptr(residual), L.ptr(s), L.ptr(q), B, Hi, Wi, Cin, Cout, stride, 1 if leaky else 0, float(slope),
                L.stream())
         return (out, s, q) if stats else out
     psc, psh, psl = pre if pre is not None else (None, None, 0.0)     # 1x1 only: LeakyReLU(x * psc + psh) on load
-    point = (DIRECT_CONV and x.dtype == torch.bfloat16 and residual is None and 0.0 <= slope <= 1.0
-             and L.lib().wmz_conv_point_supported(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad)
-             # (the streaming kernel's input prologue is built for 1x1 layers of <= 128 channels: wider hidden planes keep
-             #  the implicit-GEMM kernel's prologue)
-             and (pre is None or (KH == 1 and KW == 1 and pad == 0 and Cin <= 128)))
+    point = fam == 'point'
     pst = None
     if isinstance(psc, BnLazy):                   # the prologue's BatchNorm as raw statistics: the streaming kernel finalises it
         if point and not psc.done:
@@ -820,7 +841,7 @@ def conv2d_nhwc(x, w_op, KH, KW, stride, pad, bias=None, scale=None, shift=None,
             psc, psh = psc.materialize()
     if point:
         # csrc/conv_point.hip: small-K layers (1x1, 2x2 / stride 2, the 3-channel conv_1) as a persistent streaming kernel
-        L.call('wmz_conv_point_fwd_bn', L.ptr(x), L.ptr(_point_pack(w_op, KH * KW * Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
+        L.call('wmz_conv_point_fwd_bn' + sfx, L.ptr(x), L.ptr(_point_pack(w_op, KH * KW * Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
                L.ptr(shift), L.ptr(s), L.ptr(q), L.ptr(psc), L.ptr(psh), ctypes.addressof(pst) if pst is not None else None, float(psl),
                B, Hi, Wi, Cin, Cout, KH, KW, stride, pad, 1 if leaky else 0, float(slope), L.stream())
         return (out, s, q) if stats else out

@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from .autoencoder import SimpleResidualDecoder, SimpleResidualEncoder, _pad8
+from .autoencoder import SimpleResidualDecoder, SimpleResidualEncoder, _grad_path, _pad8, conv_route
 from .config import get_compute_dtype
 from .vq import VectorQuantizerEMA
 
@@ -20,13 +20,15 @@ class VqAutoEncoder(nn.Module):
         self.vq = VectorQuantizerEMA(embedding_dim, num_embeddings)
 
     def _latents(self, x):
-        return self.encoder.forward_nhwc(x).float()          # [B,h,w,E]; the codebook search is fp32
+        return self.encoder.forward_nhwc(x).float()          # [B,h,w,E]; the codebook search is fp32 (whatever route the encoder took)
 
     def _decode_latents(self, q):
         E = q.shape[-1]
         if _pad8(E) != E:
             q = torch.nn.functional.pad(q, (0, _pad8(E) - E))
-        return self.decoder.forward_nhwc(q.to(get_compute_dtype()).contiguous()).float()
+        # (the decoder pass's own dtype: the compute dtype, or float16 on the precise mode's half conv route)
+        dt = conv_route(self.decoder, q.shape, _grad_path(q, self.decoder))
+        return self.decoder.forward_nhwc(q.to(dt).contiguous()).float()
 
     def _quantized_nhwc(self, x):
         """frames -> (straight-through latents in the decoder's operand dtype, channel-padded for its first conv; commitment loss;
