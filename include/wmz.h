@@ -44,6 +44,22 @@ enum {
 int wmz_version(void);
 const char* wmz_last_error(void);
 
+/* ---- The half guard of the precise mode (no counterpart in the reference, which computes in fp32: local_3d_attention.py:153-163
+ * carries its residual stream through 20 layers without a final LayerNorm, main.py:33-36).  IEEE half holds +-65504; a kernel of a
+ * half unit (the *_f16 per-token, chain and conv entry points, wmz_affine_act_nhwc[_bn] on WMZ_F16) that STORES a value whose rounding to half left the finite range ORs the
+ * kind into the bound word: at most one vector atomic per wave, none on a clean run.  A value rounded only to feed an MFMA
+ * (LayerNorm output, GELU hidden) shows in the rows its kernel stores next.
+ *   wmz_half_guard_bind(word): the calling thread's current device; word = one zero-initialised device uint32 that outlives the
+ *     binding, or NULL = no guard (the default: the kernels' outputs are those of a library without the guard, bit for bit).
+ *     Synchronous (a symbol copy per guarded unit): not inside a stream capture.  Kernels launched -- or graphs replayed -- afterwards
+ *     see the new binding.
+ *   wmz_half_guard_clear(word, stream): word = 0 on the stream (a memset node inside a capture).
+ * Reading the word is a 4-byte copy. */
+enum { WMZ_HG_STREAM = 1 /* the residual stream */, WMZ_HG_QKV = 2 /* q, k | v */,
+       WMZ_HG_CONV = 4 /* an activation of the conv encoder / decoder's half route */ };
+int wmz_half_guard_bind(void* word);
+int wmz_half_guard_clear(void* word, void* stream);
+
 /* ---- Local3dAttention.local_attention (local_3d_attention.py:78-99; pad :57-63, unfold :65-69, mask :71-76)
  * q,k,v: [B,S,H,W,heads*dh] (row strides ldq/ldk/ldv in elements, head-major channels), out same shape
  * (row stride ldo).  Softmax runs over the in-grid neighbours of the (2eS+1)(2eH+1)(2eW+1) window, which

@@ -25,6 +25,8 @@ c_void_p, c_int, c_long, c_float, c_double = (ctypes.c_void_p, ctypes.c_int, cty
 SIGNATURES = {
     'wmz_local3d_attn_fwd': [c_void_p] * 6 + [c_int] * 9 + [c_long] * 4 + [c_int, c_void_p],
     'wmz_local3d_attn_fwd_general': [c_void_p] * 6 + [c_int] * 9 + [c_long] * 4 + [c_int, c_void_p],
+    'wmz_half_guard_bind': [c_void_p],
+    'wmz_half_guard_clear': [c_void_p, c_void_p],
     'wmz_debug_attn_knobs': [c_int, c_int],
     'wmz_debug_linear_knobs': [c_int],
     'wmz_local3d_attn_bwd': [c_void_p] * 10 + [c_int] * 9 + [c_long] * 8 + [c_int, c_void_p],

@@ -425,6 +425,11 @@ class SimpleResidualEncoder(nn.Module):
         (conv_route: the compute dtype, or float16 on the precise mode's half conv route)."""
         grad = _grad_path(x, self)
         dt = conv_route(self, x.shape, grad)
+        if dt == torch.float16:
+            from . import half_guard
+            if half_guard.wanted():            # config.half_guard: this pass again, guarded (inside, wanted() is False)
+                return half_guard.guarded('SimpleResidualEncoder', self, x.device, lambda: self.forward_nhwc(x),
+                                          half_guard.with_buffers_restored(self, lambda: self.forward_nhwc(x)))
         with ops.stat_arena():                                     # (one zero fill for every BatchNorm statistic of the pass)
             if grad:
                 h = F.leaky_relu(_conv_g(_to_nhwc(x, dt), self._conv_1), LEAKY)
@@ -507,6 +512,11 @@ class SimpleResidualDecoder(nn.Module):
         mods = list(self.decoder_stack)
         grad = _grad_path(h, self)
         dt = conv_route(self, h.shape, grad)
+        if dt == torch.float16:
+            from . import half_guard
+            if half_guard.wanted():
+                return half_guard.guarded('SimpleResidualDecoder', self, h.device, lambda: self.forward_nhwc(h, raw),
+                                          half_guard.with_buffers_restored(self, lambda: self.forward_nhwc(h, raw)))
         if h.dtype != dt:
             h = h.to(dt).contiguous()
         with ops.stat_arena():

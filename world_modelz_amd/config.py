@@ -63,8 +63,8 @@ def compute_dtype(dt):
 # without a gradient path runs in IEEE half on csrc/conv_direct_f16.hip and conv_point_f16.hip (the bf16 route's kernels and speed,
 # 3 more significand bits) when every layer of the pass has a half kernel, else the whole pass stays fp32
 # (autoencoder.conv_route).  The two routes trade accuracy for speed, and nothing in the input says which one a caller wants: hence
-# a switch.  Half holds +-65504: activations beyond that become infinities (no overflow check).  No effect in the bf16 and fp32
-# modes, nor on training (VQ-AE training and gradients through an encoder run the fp32 route).
+# a switch.  Half holds +-65504: activations beyond that become infinities; config.half_guard below reports them.  No effect in the bf16 and fp32 modes, nor on training (VQ-AE training and
+# gradients through an encoder run the fp32 route).
 _precise_conv = os.environ.get('WMZ_PRECISE_CONV', '0') != '0'
 
 
@@ -90,6 +90,54 @@ def precise_conv(on):
 def conv_half():
     """True when the conv encoder / decoder's inference passes may take the half route: the precise mode with precise_conv on."""
     return _precise and _precise_conv
+
+
+# The half guard of the precise mode's denoiser (half_guard.py; DESIGN 4.7 "Range").  IEEE half holds +-65504 and the stack has no
+# final LayerNorm: a trained checkpoint's residual stream, q or k | v can leave that range, the rounding then gives an infinity,
+# and the result can be finite and wrong (a key at -inf gets probability 0).  With the guard on, the half per-token kernels record
+# on the device that a value they store rounded out of range (one word, one atomic per wave and only then), and every guarded call
+# -- the model's / the transformer's inference forward on the half route, a GraphedForward / GraphedEncoder replay,
+# sample.sample_frames, the conv encoder / decoder's half passes (precise_conv) -- reads
+# that word once, at its end (one device -> host copy, i.e. one stream synchronisation per call):
+#   'off'       (default) nothing is read; nothing is bound either until a process first turns the guard on (the word then stays
+#               bound for the process: leaving the guard costs no synchronisation; half_guard.unbind() drops it);
+#   'raise'     WmzError naming the call and what overflowed (the residual stream, q / k | v, a conv activation);
+#   'fallback'  one warning per call site and model, then the same call again on the fp32 route -- the route the precise mode
+#               gives everything it has no half kernel for; the result is the fp32 mode's, bit for bit.
+# No effect in the bf16 and fp32 modes, on training, or on what already runs the fp32 route in the precise mode.
+_HALF_GUARD_POLICIES = ('off', 'raise', 'fallback')
+
+
+def _check_half_guard(policy):
+    if policy not in _HALF_GUARD_POLICIES:
+        raise ValueError(f"half guard policy: 'off', 'raise' or 'fallback', got {policy!r}")
+    return policy
+
+
+_half_guard = _check_half_guard(os.environ.get('WMZ_HALF_GUARD', 'off').lower())
+
+
+def get_half_guard():
+    return _half_guard
+
+
+def set_half_guard(policy):
+    global _half_guard
+    _half_guard = _check_half_guard(policy)
+
+
+@contextlib.contextmanager
+def half_guard(policy):
+    prev = get_half_guard()
+    set_half_guard(policy)
+    try:
+        yield
+    finally:
+        set_half_guard(prev)
+
+
+def is_precise():
+    return _precise
 
 
 # Inference only: the denoiser returns the last frame's logits (reference main.py:33-36), so the planes outside the

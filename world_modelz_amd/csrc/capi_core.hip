@@ -14,6 +14,39 @@ void wmz_set_error(const char* fmt, ...) {
 extern "C" int wmz_version(void) { return WMZ_VERSION; }
 extern "C" const char* wmz_last_error(void) { return g_err; }
 
+// ---- the half guard's binding (wmz_common.h HalfGuard): every guarded unit registers the setter of its own __constant__ copy of
+// the word's address from a static constructor, so the table lives behind a function (initialised on first use, whatever the
+// order the units' constructors run in)
+typedef int (*wmz_hg_setter)(unsigned*);
+namespace {
+struct HgUnits { wmz_hg_setter set[32]; int n; };       // (n counts every registration: one past the table is an error at bind)
+HgUnits& hg_units() { static HgUnits u = {{nullptr}, 0}; return u; }
+}
+void wmz_half_guard_register_unit(wmz_hg_setter set) {
+  HgUnits& u = hg_units();
+  if (u.n < 32) u.set[u.n] = set;
+  ++u.n;
+}
+extern "C" int wmz_half_guard_bind(void* word) {
+  WMZ_REQUIRE(((uintptr_t)word & 3) == 0, "wmz_half_guard_bind: the word must be 4-byte aligned");
+  const HgUnits& u = hg_units();
+  WMZ_REQUIRE(u.n <= 32, "wmz_half_guard_bind: %d guarded units registered, the table holds 32: a unit would stay unguarded", u.n);
+  for (int i = 0; i < u.n; ++i)
+    if (u.set[i]((unsigned*)word) != 0) {
+      wmz_set_error("wmz_half_guard_bind: symbol copy failed: %s", hipGetErrorString(hipGetLastError()));
+      return WMZ_ERR_HIP;
+    }
+  return WMZ_OK;
+}
+extern "C" int wmz_half_guard_clear(void* word, void* stream) {
+  WMZ_REQUIRE(word != nullptr, "wmz_half_guard_clear: NULL word");
+  if (hipMemsetAsync(word, 0, 4, (hipStream_t)stream) != hipSuccess) {
+    wmz_set_error("wmz_half_guard_clear: %s", hipGetErrorString(hipGetLastError()));
+    return WMZ_ERR_HIP;
+  }
+  return WMZ_OK;
+}
+
 namespace {
 
 // x[b,s,h,w,:] = emb[z] + ((pos_s[s] + pos_h[h]) + pos_w[w])   (local_3d_attention.py:140-157)

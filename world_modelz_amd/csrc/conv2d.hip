@@ -7,6 +7,7 @@
 //          Epilogue: bias, per-channel affine (folded eval-mode BatchNorm), residual add, LeakyReLU, and optionally
 //          per-channel sum / sum-of-squares of the stored output (training-mode BatchNorm statistics).
 //   channel_stats / bn_finalize / affine_act / bilinear2x: the memory-bound companions.
+#define WMZ_HALF_GUARD 1      // the _Float16 forms of affine_act carry the half guard (wmz_common.h HalfGuard); the others hold no object of it
 #include "wmz_common.h"
 #include "bn_lazy.h"
 #ifndef WMZ_ABL_NOSTAT
@@ -387,6 +388,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ a
                                                          const float* __restrict__ ta, const T* __restrict__ b,
                                                          const float* __restrict__ sb, const float* __restrict__ tb,
                                                          T* __restrict__ y, long total, int C, int leaky, float slope) {
+  // (no half guard here: the half conv route's tensors are all on the vector form -- C % 8 == 0, 16-byte aligned)
   for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < total; i += (long)gridDim.x * blockDim.x * 4) {
     const int c = (int)(i % C);
 #pragma unroll
@@ -438,6 +440,11 @@ __device__ __forceinline__ void tab_row(const float* tab, int C, int k, int c0, 
 template <typename T>
 __device__ __forceinline__ i32x4 ld16(const T* p, long i) { return *reinterpret_cast<const i32x4*>(p + i * (16 / (int)sizeof(T))); }
 
+// (affine_act_vec_kernel's guard type: the half form tests what it stores -- the train-mode encoder's latents leave through this
+//  kernel; bilinear2x interpolates between stored values and every other element-wise output is read next by a guarded conv)
+template <typename T> struct EwGuard { typedef HalfGuardNone type; };
+template <> struct EwGuard<_Float16> { typedef HalfGuard type; };
+
 template <typename T>
 __global__ __launch_bounds__(256) void affine_act_vec_kernel(const T* __restrict__ a, const float* __restrict__ sa,
                                                              const float* __restrict__ ta, const T* __restrict__ b,
@@ -462,6 +469,7 @@ __global__ __launch_bounds__(256) void affine_act_vec_kernel(const T* __restrict
   float s1[VW], t1[VW], s2[VW], t2[VW];
   tab_row<VW>(ew_tab, C, 0, c0, s1); tab_row<VW>(ew_tab, C, 1, c0, t1);
   tab_row<VW>(ew_tab, C, 2, c0, s2); tab_row<VW>(ew_tab, C, 3, c0, t2);
+  typename EwGuard<T>::type hg;
   auto finish = [&](const i32x4& va, const i32x4& vb, long at) {
     float f[VW];
     chunk_to_f32<T>(va, f);
@@ -477,7 +485,9 @@ __global__ __launch_bounds__(256) void affine_act_vec_kernel(const T* __restrict
 #pragma unroll
       for (int e = 0; e < VW; ++e) f[e] = f[e] > 0.f ? f[e] : f[e] * slope;
     }
-    *reinterpret_cast<i32x4*>(y + at * VW) = f32_to_chunk<T>(f);
+    const i32x4 out = f32_to_chunk<T>(f);
+    if (hg.on()) hg.see(out);
+    *reinterpret_cast<i32x4*>(y + at * VW) = out;
   };
   if (b) {
     for (; i + stride < nvec; i += 2 * stride) {
@@ -497,6 +507,7 @@ __global__ __launch_bounds__(256) void affine_act_vec_kernel(const T* __restrict
     issued(a0, b0);
     finish(a0, b0, i);
   }
+  if (hg.on()) { hg.fold(WMZ_HG_CONV); hg.commit(); }
 }
 
 // dz[b, s y, s x, :] = dy[b, y, x, :], zero elsewhere: the zero-inserted plane on which a strided convolution's data gradient runs as a

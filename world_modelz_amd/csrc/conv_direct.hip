@@ -293,6 +293,15 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
     if (nt) __builtin_nontemporal_store(v, reinterpret_cast<i32x4*>(const_cast<bf16_t*>(p)));
     else *reinterpret_cast<i32x4*>(const_cast<bf16_t*>(p)) = v;
   };
+#ifdef WMZ_HALF_GUARD
+  // half guard (wmz_common.h): the epilogue's BatchNorm sum of squares of the STORED values is the detector (finite unless one of
+  // them is not); a launch without statistics takes the same epilogue form while a word is bound and only tests the sum.  The
+  // residual form compares the fp32 values where it has no sums.  Scalar masks only: no VGPR (the bf16 forms' budgets are pinned).
+  HalfGuard hg;
+  const bool sums = want_stats || hg.on();
+#else
+  const bool sums = want_stats;
+#endif
   if (P.res == nullptr) {
     f32x2 s1 = {0.f, 0.f}, s2 = {0.f, 0.f};
     auto finish = [&](auto affc, auto leakyc, auto statsc) {
@@ -340,7 +349,7 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
       }
     };
     using T_ = std::true_type; using F_ = std::false_type;
-    const int sel = (P.scale ? 4 : 0) | (P.leaky ? 2 : 0) | (want_stats ? 1 : 0);
+    const int sel = (P.scale ? 4 : 0) | (P.leaky ? 2 : 0) | (sums ? 1 : 0);
     if (P.dbg & 64) {
       if (chunk_ok) {
 #pragma unroll
@@ -360,6 +369,9 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
       case 6: finish(T_{}, T_{}, F_{}); break;
       default: finish(T_{}, T_{}, T_{}); break;
     }
+#ifdef WMZ_HALF_GUARD
+    if (hg.on()) hg.see_nonfinite_if(col < P.Cout, s2[0] + s2[1]);
+#endif
     if (want_stats) {
       const float t1 = wave_halves_sum(s1[0] + s1[1]), t2 = wave_halves_sum(s2[0] + s2[1]);
       if (hh == 0 && col < P.Cout) {
@@ -407,6 +419,12 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], f[e] * P.slope);
           }
+#ifdef WMZ_HALF_GUARD
+          if (hg.on() && !want_stats) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) hg.see_f32(f[e]);            // (inside chunk_ok: stored channels only)
+          }
+#endif
           i32x4 pk;
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -430,6 +448,12 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
 #pragma unroll
         for (int o = 4; o < 64; o <<= 1) { s1[e] += __shfl_xor(s1[e], o); s2[e] += __shfl_xor(s2[e], o); }
       }
+#ifdef WMZ_HALF_GUARD
+      if (hg.on()) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) hg.see_nonfinite_if(chunk_ok, s2[e]);
+      }
+#endif
       if (lane < 4 && chunk_ok) {
         const long rep = (long)(blockIdx.x % WMZ_STAT_REPLICAS) * P.Cout;
 #pragma unroll
@@ -437,6 +461,9 @@ __global__ __launch_bounds__(256, STRIDE == 1 ? 2 : 3) void convr_kernel(DirectP
       }
     }
   }
+#ifdef WMZ_HALF_GUARD
+  if (hg.on()) { hg.fold(WMZ_HG_CONV); hg.commit(); }
+#endif
   CONV_STAMP(5);
 }
 

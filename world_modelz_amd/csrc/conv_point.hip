@@ -58,6 +58,12 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
   char* const img = lds + wbytes + 1024 + wave * CP_IMG;
   const int l31 = lane & 31, hh = lane >> 5;
   const bool pre = P.in_scale != nullptr || P.in_bn.sum != nullptr;
+#ifdef WMZ_HALF_GUARD
+  // half guard (wmz_common.h), as in conv_direct.hip: the epilogue's BatchNorm sums of squares of the STORED values are the detector;
+  // a launch without statistics takes the same epilogue form while a word is bound and only tests the sums.  No new code in the loop.  (The prologue's operand
+  // rounding needs no test: a non-finite operand element makes every channel of its pixel non-finite, and that row is stored.)
+  HalfGuard hg;
+#endif
 
   // ---- once per workgroup: weights (fragment order, contiguous) and the prologue's per-channel constants into LDS
   for (int i = tid; i < wbytes / 16; i += 256)
@@ -87,6 +93,11 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
   char* const a_wr = img + sr * CP_PITCH + gc * 16;
   const char* const b_rd = wlds + lane * 16;
   const bool want_stats = P.stat_sum != nullptr;
+#ifdef WMZ_HALF_GUARD
+  const bool sums = want_stats || hg.on();
+#else
+  const bool sums = want_stats;
+#endif
   f32x2 s1[NCB], s2[NCB];
 #pragma unroll
   for (int j = 0; j < NCB; ++j) { s1[j] = (f32x2){0.f, 0.f}; s2[j] = (f32x2){0.f, 0.f}; }
@@ -232,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
       }
     };
     using T_ = std::true_type; using F_ = std::false_type;
-    const int sel = (P.scale ? 4 : 0) | (P.leaky ? 2 : 0) | (want_stats ? 1 : 0);
+    const int sel = (P.scale ? 4 : 0) | (P.leaky ? 2 : 0) | (sums ? 1 : 0);
     switch (sel) {
       case 0: finish(F_{}, F_{}, F_{}); break;
       case 1: finish(F_{}, F_{}, T_{}); break;
@@ -246,6 +257,12 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
     __builtin_amdgcn_wave_barrier();                                // (the image is the next run's staging space)
   }
 
+#ifdef WMZ_HALF_GUARD
+  if (hg.on()) {                   // the lane's sums of squares of the values it STORED: finite unless one of them is not
+#pragma unroll
+    for (int j = 0; j < NCB; ++j) hg.see_nonfinite_if(32 * j + l31 < P.Cout, s2[j][0] + s2[j][1]);
+  }
+#endif
   if (want_stats) {
     // lane-local sums of all this wave's runs -> channel sums of the workgroup (LDS) -> one atomic per channel
     __syncthreads();                                                // every wave is done with its image: reuse the first KB pair
@@ -264,6 +281,9 @@ __global__ __launch_bounds__(256, 2) void convp_kernel(PointParams P) {
       atomicAdd(P.stat_sq + rep + tid, red[NCB * 32 + tid]);
     }
   }
+#ifdef WMZ_HALF_GUARD
+  if (hg.on()) { hg.fold(WMZ_HG_CONV); hg.commit(); }
+#endif
 }
 
 #ifndef WMZ_OP16_F16

@@ -3,4 +3,5 @@
 // Same source as conv_point.hip with the translation unit's 16-bit operand format switched (wmz_common.h); the weight pack, the
 // support query and wmz_nchw_to_nhwc8 are the bfloat16 unit's.
 #define WMZ_OP16_F16 1
+#define WMZ_HALF_GUARD 1      // this unit carries the half guard (wmz_common.h HalfGuard)
 #include "conv_point.hip"

@@ -273,7 +273,12 @@ __device__ __forceinline__ void load_bop_tiled(Frag8<bf16_t> (&bop)[KS], const b
   for (int s = 0; s < KS; ++s) bop[s].v = *reinterpret_cast<const s16x8*>(tile + (s * 64 + lane) * 8);   // (2s+h)*32+t = 64s+lane
 }
 template <int KS>
-__device__ __forceinline__ void store_bop_tiled(bf16_t* tile, const Frag8<bf16_t> (&bop)[KS], int lane) {
+__device__ __forceinline__ void store_bop_tiled(bf16_t* tile, const Frag8<bf16_t> (&bop)[KS], int lane, HalfGuard& hg) {
+  if (hg.on()) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) hg.see(bop[s].v);
+    hg.fold(WMZ_HG_STREAM);
+  }
 #pragma unroll
   for (int s = 0; s < KS; ++s) *reinterpret_cast<s16x8*>(tile + (s * 64 + lane) * 8) = bop[s].v;
 }
@@ -304,7 +309,8 @@ __device__ __forceinline__ void stage_put(char* stg, const s16x8& v, int t, int 
 }
 // copy the 8 KB image out: row r of the image -> dst + (tok0 + r) * ROWF + col0, 128 features (256 B) per row
 template <int ROWF>
-__device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long tok0, int ntok, int col0, int lane) {
+__device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long tok0, int ntok, int col0, int lane, HalfGuard& hg,
+                                            unsigned kind) {
   asm volatile("" : "+s"(tok0), "+v"(lane));   // compute the store addresses HERE (hoisted / shared with the prologue's
                                                // index math they only get spilled)
   // all eight LDS reads first, unconditionally, then the predicated stores: with the read inside the predicate hipcc
@@ -312,12 +318,22 @@ __device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long t
   s16x8 v[8];
 #pragma unroll
   for (int p = 0; p < 8; ++p) v[p] = *reinterpret_cast<const s16x8*>(stg + p * 1024 + lane * 16);
+  if (hg.on()) {                               // half guard: the image's rows are all rows of real tokens (clamped past ntok)
+#pragma unroll
+    for (int p = 0; p < 8; ++p) hg.see(v[p]);
+    hg.fold(kind);
+  }
 #pragma unroll
   for (int p = 0; p < 8; ++p) {
     const int r = p * 4 + (lane >> 4), pc = lane & 15;
     const int c = pc ^ (r & 15);
     if (tok0 + r < ntok) *reinterpret_cast<s16x8*>(dst + (tok0 + r) * ROWF + col0 + c * 8) = v[p];
   }
+}
+template <int ROWF>
+__device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long tok0, int ntok, int col0, int lane) {
+  HalfGuard none;                                                      // (the backward unit: bfloat16 only, nothing to guard)
+  stage_flush<ROWF>(stg, dst, tok0, ntok, col0, lane, none, 0u);
 }
 // operand fragments parked in the wave's LDS image, lane-linear (each lane reads back what it wrote)
 __device__ __forceinline__ void frag_park(char* stg, int slot, const Frag8<bf16_t>& f, int lane) {
@@ -331,16 +347,21 @@ __device__ __forceinline__ Frag8<bf16_t> frag_unpark(const char* stg, int slot, 
 
 // an I-feature tile (q, k, v: 128 features, every lane holds 8 chunks of its row): one pass
 __device__ __forceinline__ void store_tile128(char* stg, bf16_t* dst, int rowf, long tok0, int ntok, int col0,
-                                              const Frag8<bf16_t> (&b)[8], int lane) {
+                                              const Frag8<bf16_t> (&b)[8], int lane, HalfGuard& hg) {
   const int t = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int s = 0; s < 8; ++s) stage_put(stg, b[s].v, t, h * 8 + s);
-  if (rowf == 128) stage_flush<128>(stg, dst, tok0, ntok, col0, lane);
-  else stage_flush<256>(stg, dst, tok0, ntok, col0, lane);
+  if (rowf == 128) stage_flush<128>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
+  else stage_flush<256>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
+}
+__device__ __forceinline__ void store_tile128(char* stg, bf16_t* dst, int rowf, long tok0, int ntok, int col0,
+                                              const Frag8<bf16_t> (&b)[8], int lane) {
+  HalfGuard none;                                                      // (the backward unit: bfloat16 only, nothing to guard)
+  store_tile128(stg, dst, rowf, tok0, ntok, col0, b, lane, none);
 }
 // the D-feature stream (256 features, a lane holds 16 chunks = its whole 256-byte half row): one pass per lane half
 __device__ __forceinline__ void store_tile256(char* stg, bf16_t* dst, long tok0, int ntok, const Frag8<bf16_t> (&b)[16],
-                                              int lane) {
+                                              int lane, HalfGuard& hg) {
   const int t = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int hh = 0; hh < 2; ++hh) {
@@ -348,8 +369,13 @@ __device__ __forceinline__ void store_tile256(char* stg, bf16_t* dst, long tok0,
 #pragma unroll
       for (int s = 0; s < 16; ++s) stage_put(stg, b[s].v, t, s);
     }
-    stage_flush<256>(stg, dst, tok0, ntok, hh * 128, lane);
+    stage_flush<256>(stg, dst, tok0, ntok, hh * 128, lane, hg, WMZ_HG_STREAM);
   }
+}
+__device__ __forceinline__ void store_tile256(char* stg, bf16_t* dst, long tok0, int ntok, const Frag8<bf16_t> (&b)[16],
+                                              int lane) {
+  HalfGuard none;
+  store_tile256(stg, dst, tok0, ntok, b, lane, none);
 }
 
 template <int NB>

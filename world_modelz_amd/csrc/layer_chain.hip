@@ -188,8 +188,20 @@ __global__ __launch_bounds__(CW * 64, 2) void layer_chain_kernel(ChainParams P) 
       }
     }
   };
-  auto store_rows = [&](auto nbc, bf16_t* row, const auto& acc) {
+#ifdef WMZ_HALF_GUARD
+  HalfGuard hg;                                             // (the half units only: in the bfloat16 unit not even an empty object --
+#endif                                                      //  a captured one reorders hipcc's register allocation in five kernels)
+  auto store_rows = [&](auto nbc, bf16_t* row, const auto& acc, unsigned kind) {
     constexpr int NB = decltype(nbc)::value;
+#ifdef WMZ_HALF_GUARD
+    if (hg.on()) {                                          // half guard, on the fp32 values: this kernel has no VGPR to spare for
+#pragma unroll                                              // the packed form (rows past the end are the last token's: real values)
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hg.see_f32(acc[b][r]);
+      hg.fold(kind);
+    }
+#endif
 #pragma unroll
     for (int s = 0; s < NB / 2; ++s) {
       i32x4 c;
@@ -247,7 +259,7 @@ __global__ __launch_bounds__(CW * 64, 2) void layer_chain_kernel(ChainParams P) 
     if constexpr (TRAIN) {
       // what the backward reads: the raw rows (op-by-op fallback only), the statistics, and the NORMALISED rows -- which are
       // exactly the B operand just packed: 16 bytes per k-step, no extra arithmetic
-      if (P.x1 != nullptr) store_rows(CNBD{}, P.x1 + tok * D + g * (D / 4), xr);
+      if (P.x1 != nullptr) store_rows(CNBD{}, P.x1 + tok * D + g * (D / 4), xr, WMZ_HG_STREAM);
       if (ok && g == 0) { P.st_ff[tok] = mean; P.st_ff[ntok + tok] = rstd; }
 #pragma unroll
       for (int s2 = 0; s2 < KSD; ++s2)
@@ -275,7 +287,7 @@ __global__ __launch_bounds__(CW * 64, 2) void layer_chain_kernel(ChainParams P) 
           h[b] = op16_mfma_16x16x32(a, xb[ks], h[b]);
         } else {
           if constexpr (p == NBC * KSD) {
-            if constexpr (TRAIN) store_rows(CNBC{}, P.z + tok * M + c * MC + g * (MC / 4), h);
+            if constexpr (TRAIN) store_rows(CNBC{}, P.z + tok * M + c * MC + g * (MC / 4), h, WMZ_HG_STREAM);
 #pragma unroll
             for (int s2 = 0; s2 < KSC; ++s2)
 #pragma unroll
@@ -291,7 +303,7 @@ __global__ __launch_bounds__(CW * 64, 2) void layer_chain_kernel(ChainParams P) 
         }
       });
     }
-    store_rows(CNBD{}, P.xo + tok * D + g * (D / 4), xr);
+    store_rows(CNBD{}, P.xo + tok * D + g * (D / 4), xr, WMZ_HG_STREAM);
   }
   if constexpr (TAIL) {
     float mean, rstd;
@@ -309,16 +321,19 @@ __global__ __launch_bounds__(CW * 64, 2) void layer_chain_kernel(ChainParams P) 
 #pragma unroll
     for (int b = 0; b < NBI; ++b) a[b] = (f32x4)(0.f);
     gemm(CNBI{}, CKSD{}, a, xq);
-    store_rows(CNBI{}, P.q + tok * I + g * (I / 4), a);
+    store_rows(CNBI{}, P.q + tok * I + g * (I / 4), a, WMZ_HG_QKV);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
       for (int b = 0; b < NBI; ++b) a[b] = *reinterpret_cast<const f32x4*>(vec + 2 * D + M + t * I + g * (I / 4) + 4 * b);
       gemm(CNBI{}, CKSD{}, a, xn);
-      store_rows(CNBI{}, P.kv + (long)t * P.voff + tok * P.ldkv + g * (I / 4), a);
+      store_rows(CNBI{}, P.kv + (long)t * P.voff + tok * P.ldkv + g * (I / 4), a, WMZ_HG_QKV);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the ring's run-ahead requests land before the LDS is handed back
+#ifdef WMZ_HALF_GUARD
+  hg.commit();
+#endif
 }
 
 template <int D, int I, int M, int MC, bool TRAIN>

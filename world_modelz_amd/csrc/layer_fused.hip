@@ -170,6 +170,7 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
   const int h = lane >> 5;
   float* vecs = reinterpret_cast<float*>(smem);
   const char* ring0 = smem + VECB;
+  HalfGuard hg;
   WStream ws;
   ws.ring = smem + VECB + wave * (SLAB / FW);
   ws.src = P.wpack + wave * (SLAB / FW) + lane * 16;
@@ -235,14 +236,14 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
     const bool x1_hat = (P.xflags & WMZ_FUSED_X1_NORMALISED) != 0;
     if (P.x1o != nullptr && !x1_hat) {                                 // training, op-by-op backward: x1 itself
       bop_from_acc<D / 32>(xb, xr);
-      store_tile256(stg, P.x1o, tok0, P.ntok, xb, lane);
+      store_tile256(stg, P.x1o, tok0, P.ntok, xb, lane, hg);
       ws_extra(ws, 16);
     }
     WMZ_TS(3);
     ln_to_bop<D / 32>(xb, xr, P.eps, P.st_ff, tok, P.ntok, lane);   // LN2(x1)
     if (P.st_ff != nullptr) ws_extra(ws, 2);
     if (P.x1o != nullptr && x1_hat) {                                  // training, fused backward: the NORMALISED rows -- all the
-      store_tile256(stg, P.x1o, tok0, P.ntok, xb, lane);               // backward needs of x1 (LayerNorm backward and the dW1
+      store_tile256(stg, P.x1o, tok0, P.ntok, xb, lane, hg);               // backward needs of x1 (LayerNorm backward and the dW1
       ws_extra(ws, 16);                                                // operand), already in registers as the W1 operand
     }
     WMZ_TS(4);
@@ -311,12 +312,12 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
     }
     else bop_from_acc<D / 32>(x2b, xr);
     WMZ_TS(30);
-    if (P.xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16>(P.xo + tok0 * D, x2b, lane); }
-    else store_tile256(stg, P.xo, tok0, P.ntok, x2b, lane);
+    if (P.xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16>(P.xo + tok0 * D, x2b, lane, hg); }
+    else store_tile256(stg, P.xo, tok0, P.ntok, x2b, lane, hg);
     ws_extra(ws, 16);
     if (P.xo_rm != nullptr) {        // training: the row-major copy for the backward -- x2 itself, or (WMZ_FUSED_XRM_NORMALISED)
-      if (TAIL && (P.xflags & WMZ_FUSED_XRM_NORMALISED)) store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane);   // LN1'(x2)'s rows
-      else store_tile256(stg, P.xo_rm, tok0, P.ntok, x2b, lane);
+      if (TAIL && (P.xflags & WMZ_FUSED_XRM_NORMALISED)) store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane, hg);   // LN1'(x2)'s rows
+      else store_tile256(stg, P.xo_rm, tok0, P.ntok, x2b, lane, hg);
       ws_extra(ws, 16);
     }
     WMZ_TS(31);
@@ -344,10 +345,10 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
     for (int i = 0; i < 8 / FW; ++i) *reinterpret_cast<f32x4*>(vecs + (tid + i * NTHR) * 4) = vecv[i];
     __syncthreads();
     if (P.z != nullptr) {
-      if (P.xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16>(P.xo + tok0 * D, xb, lane); }
-      else store_tile256(stg, P.xo, tok0, P.ntok, xb, lane);
+      if (P.xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16>(P.xo + tok0 * D, xb, lane, hg); }
+      else store_tile256(stg, P.xo, tok0, P.ntok, xb, lane, hg);
       ws_extra(ws, 16);
-      if (P.xo_rm != nullptr && !(P.xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane); ws_extra(ws, 16); }
+      if (P.xo_rm != nullptr && !(P.xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane, hg); ws_extra(ws, 16); }
     }
     {
       f32x16 qa[I / 32];
@@ -358,30 +359,31 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
     acc_from_bop<D / 32>(xr, xb);
     ln_to_bop<D / 32>(xb, xr, P.eps, P.st_attn, tok, P.ntok, lane);   // LN1'(x)
     if (P.st_attn != nullptr) ws_extra(ws, 2);
-    if (P.xo_rm != nullptr && (P.xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane); ws_extra(ws, 16); }
+    if (P.xo_rm != nullptr && (P.xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane, hg); ws_extra(ws, 16); }
   }
   if constexpr (TAIL) {
     f32x16 ka[I / 32];
     Frag8<bf16_t> kb[I / 16];
     init_vec<I / 32>(ka, v_bk);
-    store_tile128(stg, P.q, I, tok0, P.ntok, 0, qkvb, lane);         // q rows (as side work under the to_k MFMAs: slower)
+    store_tile128(stg, P.q, I, tok0, P.ntok, 0, qkvb, lane, hg);         // q rows (as side work under the to_k MFMAs: slower)
     ws_extra(ws, 8);
     WMZ_TS(33);
     gemm_stage<I / 32, D / 16>(ka, xb, ring0, ws, lane);               // to_k
     WMZ_TS(34);
     bop_from_acc<I / 32>(kb, ka);
-    if (P.kv_combined) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, 0, kb, lane);   // k | v column halves of [ntok, 2I]
-    else store_tile128(stg, P.kv, I, tok0, P.ntok, 0, kb, lane);       // k rows
+    if (P.kv_combined) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, 0, kb, lane, hg);   // k | v column halves of [ntok, 2I]
+    else store_tile128(stg, P.kv, I, tok0, P.ntok, 0, kb, lane, hg);       // k rows
     ws_extra(ws, 8);
     init_vec<I / 32>(ka, v_bv);
     WMZ_TS(35);
     gemm_stage<I / 32, D / 16>(ka, xb, ring0, ws, lane);               // to_v
     WMZ_TS(36);
     bop_from_acc<I / 32>(kb, ka);
-    if (P.kv_combined) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, I, kb, lane);
-    else store_tile128(stg, P.kv + (long)P.ntok * I, I, tok0, P.ntok, 0, kb, lane);    // v rows, behind the k rows
+    if (P.kv_combined) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, I, kb, lane, hg);
+    else store_tile128(stg, P.kv + (long)P.ntok * I, I, tok0, P.ntok, 0, kb, lane, hg);    // v rows, behind the k rows
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the padding slabs still in flight target this workgroup's LDS
+  hg.commit();
   WMZ_TS(37);
 }
 

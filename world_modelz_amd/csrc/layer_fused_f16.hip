@@ -4,4 +4,5 @@
 // wmz_fused_pack_table_f16).  Same source as layer_fused.hip with the translation unit's 16-bit operand format switched
 // (wmz_common.h); the training forward and the backward streams exist in the bfloat16 unit only.
 #define WMZ_OP16_F16 1
+#define WMZ_HALF_GUARD 1      // this unit carries the half guard (wmz_common.h HalfGuard)
 #include "layer_fused.hip"

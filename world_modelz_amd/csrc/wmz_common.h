@@ -134,6 +134,87 @@ __device__ __forceinline__ float op16_lo_f32(unsigned w) { return __uint_as_floa
 __device__ __forceinline__ float op16_hi_f32(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
 #endif
 
+// ---- the half guard (DESIGN 4.7 "Range"; include/wmz.h wmz_half_guard_bind).  IEEE half holds +-65504: an fp32 value beyond that
+// rounds to an infinity.  A kernel of a half unit passes the packed dwords it is about to STORE through HalfGuard::see (one
+// v_pk_fma_f16 per dword: value * 0 + acc is +-0 while every value seen is finite and a NaN from the first infinity or NaN on), folds
+// the lanes' accumulators into a wave-uniform mask of WMZ_HG_* kinds with one ballot, and at its very end -- behind its last
+// counted vmcnt wait -- issues at most ONE vector atomic OR per wave, and only when that mask is non-zero: a clean run adds no
+// memory traffic.  The values a kernel rounds only to feed an MFMA (LayerNorm output, GELU hidden) need no test of their own: a
+// non-finite operand element makes every output feature of that token's product non-finite (inf * w is an infinity or a NaN for
+// every w), so the next rows the kernel stores for that token carry it.  The word's address is per-unit __constant__ state set by
+// wmz_half_guard_bind (each guarded unit registers its setter with capi_core.hip when the library loads): NULL -- the default --
+// skips the tests behind one wave-uniform branch per store site.  Units without WMZ_HALF_GUARD get the empty form below: no code.
+// INVARIANT the operand argument rests on: every product of an operand rounded without a test ends, in the SAME kernel, in a row
+// that is stored through a tested site.  A kernel that writes such a product to an untested buffer needs a test of its own.
+// (WMZ_HALF_GUARD is defined by the units that carry the guard -- layer_fused_f16, layer_chain*_f16, conv_direct_f16,
+// conv_point_f16, conv2d -- in front of this header: only they own a copy of the word's address and register its setter.)
+#ifdef WMZ_HALF_GUARD
+typedef int (*wmz_hg_setter)(unsigned*);
+void wmz_half_guard_register_unit(wmz_hg_setter set);          // capi_core.hip
+namespace {
+__constant__ unsigned* wmz_hg_word = nullptr;
+int wmz_hg_set(unsigned* word) { return hipMemcpyToSymbol(HIP_SYMBOL(wmz_hg_word), &word, sizeof(word)) == hipSuccess ? 0 : 1; }
+struct WmzHgUnit { WmzHgUnit() { wmz_half_guard_register_unit(wmz_hg_set); } } wmz_hg_unit;
+}
+struct HalfGuard {
+  unsigned* word;      // wave-uniform: NULL = no guard
+  unsigned acc;        // per lane: a half pair, +-0 or NaN
+  unsigned kinds;      // wave-uniform: WMZ_HG_* of what overflowed so far
+  unsigned long long bad;   // wave-uniform: lanes whose see_f32 saw a value that rounds out of range
+  __device__ __forceinline__ HalfGuard() : word(wmz_hg_word), acc(0u), kinds(0u), bad(0ull) {}
+  __device__ __forceinline__ bool on() const { return word != nullptr; }
+  __device__ __forceinline__ void see(unsigned w) { asm("v_pk_fma_f16 %0, %1, 0, %0" : "+v"(acc) : "v"(w)); }
+  __device__ __forceinline__ void see(const s16x4& v) {
+    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+    const u32x2 w = __builtin_bit_cast(u32x2, v);
+    see(w[0]); see(w[1]);
+  }
+  __device__ __forceinline__ void see(const s16x8& v) {
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    const u32x4 w = __builtin_bit_cast(u32x4, v);
+    see(w[0]); see(w[1]); see(w[2]); see(w[3]);
+  }
+  // the fp32 value in front of its conversion, for kernels with no register to spare: one compare into a scalar mask, no VGPR
+  // (round-to-nearest-even takes |x| >= 65520 -- halfway between 65504 and 2^16 -- to an infinity; a NaN fails the < too)
+  __device__ __forceinline__ void see_f32(float x) { bad |= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(x) < 65520.0f)); }
+  // ... only where `use` holds (a lane whose value is never stored: a padded channel), and the plain non-finite test for an fp32
+  // sum of stored values (the conv epilogues' BatchNorm sums of squares: finite unless a stored value was not)
+  __device__ __forceinline__ void see_f32_if(bool use, float x) { bad |= __builtin_amdgcn_ballot_w64(use && !(__builtin_fabsf(x) < 65520.0f)); }
+  __device__ __forceinline__ void see_nonfinite_if(bool use, float x) {
+    bad |= __builtin_amdgcn_ballot_w64(use && !(__builtin_fabsf(x) < __builtin_inff()));
+  }
+  __device__ __forceinline__ void see(const i32x4& v) { see(__builtin_bit_cast(s16x8, v)); }
+  __device__ __forceinline__ void see(_Float16 v) { see((unsigned)__builtin_bit_cast(unsigned short, v)); }
+  // the lanes' accumulators -> the wave's mask; the accumulator register is free again
+  __device__ __forceinline__ void fold(unsigned kind) {
+    if ((bad | __builtin_amdgcn_ballot_w64((acc & 0x7C007C00u) != 0u)) != 0ull) kinds |= kind;
+    acc = 0u;
+    bad = 0ull;
+  }
+  // once per wave, at the kernel's end (behind every counted vmcnt wait: the atomic is a VMEM operation)
+  __device__ __forceinline__ void commit() {
+    // (the lane test is computed HERE: a lane id carried from the kernel's prologue would stay live across its GEMMs)
+    if (word != nullptr && kinds != 0u) {
+      if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+        __hip_atomic_fetch_or(word, kinds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+};
+typedef HalfGuard HalfGuardOn;
+#endif
+struct HalfGuardNone {
+  __device__ __forceinline__ bool on() const { return false; }
+  template <typename V> __device__ __forceinline__ void see(const V&) {}
+  __device__ __forceinline__ void see_f32(float) {}
+  __device__ __forceinline__ void see_f32_if(bool, float) {}
+  __device__ __forceinline__ void see_nonfinite_if(bool, float) {}
+  __device__ __forceinline__ void fold(unsigned) {}
+  __device__ __forceinline__ void commit() {}
+};
+#ifndef WMZ_HALF_GUARD
+typedef HalfGuardNone HalfGuard;
+#endif
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int kDtype = WMZ_F32;

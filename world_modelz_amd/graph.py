@@ -8,7 +8,7 @@ capturable; torch's caching allocator provides the graph-private pool for interm
 """
 import torch
 
-from . import _cast, config
+from . import _cast, config, half_guard
 
 
 def capture_mode():
@@ -44,7 +44,11 @@ class GraphedForward:
     streams: _cast).  It therefore (i) holds strong references to every operand tensor that existed at capture time, so
     none of them can be freed and recycled under a retained graph, and (ii) stamps the parameter versions / addresses,
     the _cast epoch and the run-time configuration it was captured under, and re-captures when any of them changed
-    (optimizer step, load_state_dict, EMA copy, .to(), another compute dtype) instead of replaying stale weights."""
+    (optimizer step, load_state_dict, EMA copy, .to(), another compute dtype) instead of replaying stale weights.
+
+    config.half_guard: a replay is a guarded call (the word is cleared in front of it and read behind it, outside the graph).  A
+    runner built with pre / post work is NOT guarded on its own -- its caller has to be (sample.sample_frames is): the fallback
+    would have to repeat that work too."""
 
     def __init__(self, model, example, warmup=3, pre=None, post=None):
         """pre(static_in) / post(static_out): optional device-only work captured in front of / behind the forward (the
@@ -69,7 +73,7 @@ class GraphedForward:
         self._tensors = list(self.model.parameters()) + list(self.model.buffers())
         s = config.shared_stream('warmup')
         s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s), torch.no_grad():
+        with torch.cuda.stream(s), torch.no_grad(), half_guard.suspended():       # (the replays are guarded, not the warm-up)
             for _ in range(self.warmup):
                 if self.pre is not None:
                     self.pre(self.static_in)
@@ -96,6 +100,22 @@ class GraphedForward:
             self._capture()
 
     def __call__(self, tokens):
+        if half_guard.wanted() and self.pre is None and self.post is None:
+            # config.half_guard: the word is cleared in front of the replay and read behind it, both outside the graph (the kernels
+            # find the word through the library's binding, not through an argument baked into the capture); 'fallback' runs the
+            # forward eagerly on the fp32 route.  (A runner with captured pre / post work -- the sampler's -- is guarded by its
+            # caller, which can repeat the whole call.)
+            return half_guard.guarded(type(self).__name__, self.model, self.static_in.device, lambda: self._replay(tokens),
+                                      half_guard.with_buffers_restored(self.model, lambda: self._eager(tokens)))
+        return self._replay(tokens)
+
+    def _eager(self, tokens):
+        """The fallback's forward, eagerly on the fp32 route, handed out like a replay's: in the runner's static output."""
+        with torch.no_grad():
+            self.static_out.copy_(self.model(tokens))
+        return self.static_out
+
+    def _replay(self, tokens):
         self.refresh()
         if tokens is not self.static_in:
             self.static_in.copy_(tokens, non_blocking=True)

@@ -219,9 +219,13 @@ class Local3dAttentionTransformer(nn.Module):
         check_model_width(self.embedding.weight.shape[1], 'Local3dAttentionTransformer')
         self.check_grid(img_z)
         if not torch.is_grad_enabled():
-            from . import fused
+            from . import fused, half_guard
             from .config import get_fused_dtype
             route = fused.inference_route(self, get_fused_dtype(), img_z.shape[2], img_z.shape[3], img_z.numel())
+            if route in ('fused', 'chain') and half_guard.wanted():
+                # the half route with config.half_guard on: this call again, guarded (inside, wanted() is False)
+                return half_guard.guarded('Local3dAttentionTransformer.forward', self, img_z.device,
+                                          lambda: self.forward_compute(img_z))
             if route == 'fused':
                 # inference, bf16 (or half: the precise mode), default widths: one attention launch + one per-token launch per
                 # layer, the embedding fused into the first one

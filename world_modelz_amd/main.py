@@ -19,6 +19,15 @@ class VqVideoDiffusionModel(nn.Module):
 
     def forward(self, x):
         if not torch.is_grad_enabled() and x.is_cuda:
+            from . import config, fused, half_guard
+            # (the precise mode with config.half_guard on, where the stack takes the half route: one read-back at the end of the call)
+            if half_guard.wanted() and fused.inference_route(self.transformer, config.get_fused_dtype(), x.shape[2], x.shape[3],
+                                                             x.numel()) in ('fused', 'chain'):
+                return half_guard.guarded('VqVideoDiffusionModel.forward', self, x.device, lambda: self._forward(x))
+        return self._forward(x)
+
+    def _forward(self, x):
+        if not torch.is_grad_enabled() and x.is_cuda:
             from . import config, fused
             tr = self.transformer
             _, S, H, W = x.shape

@@ -38,6 +38,22 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     (main.py:85, :97-100), which makes the loop a deterministic function of its inputs (parity tests); default: device RNG.
     trace: optional list that receives every last frame fed to the model."""
     assert batch_z.is_cuda
+    from . import half_guard
+    if half_guard.wanted():
+        # config.half_guard: the whole call is one guarded call (its forwards only accumulate into the word); a fallback repeats
+        # it on the fp32 route with the random state it started from, so the tokens are the fp32 mode's
+        gens = [generator] if generator is not None else [torch.default_generator, torch.cuda.default_generators[batch_z.device.index]]
+        states = [g.get_state() for g in gens]
+        args = (model, batch_z, num_embeddings, num_frames, num_eval_iterations, sample_topk, noise_schedule, consistent_masking,
+                generator, use_graph, uniforms)
+
+        def again():
+            for g, st in zip(gens, states):
+                g.set_state(st)
+            if trace is not None:
+                del trace[:]
+            return sample_frames(*args, trace=trace)
+        return half_guard.guarded('sample.sample_frames', model, batch_z.device, lambda: sample_frames(*args, trace=trace), again)
     B, S, H, W = batch_z.shape
     mask_token = num_embeddings
     batch_z = batch_z.clone()
