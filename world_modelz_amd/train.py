@@ -380,6 +380,8 @@ class _TrainerBase(_AdamState):
     """One object = model + flat arenas + AdamW state + (optional) data-parallel reducer; subclasses supply the step body
     (DenoiserTrainer: main.py:216-287 on token grids; SparseDenoiserTrainer: minecraft/sparse_diffusion.py:398-467)."""
 
+    graph_accumulates = False              # enable_graph captures accumulation_steps > 1 (trainers whose train_step accumulates)
+
     def __init__(self, model, num_embeddings, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-7, warmup=500,
                  max_steps=200 * 1000, distributed=None, bucket_bytes=None, accumulation_steps=1):
         """bucket_bytes None: one all-reduce bucket per transformer layer (plus the embeddings and the head), so the
@@ -494,7 +496,7 @@ class _TrainerBase(_AdamState):
     @_gc_quiet
     def enable_graph(self, example_batch, warmup=3, keep_warmup_updates=False):
         """Capture corrupt -> forward -> CE -> backward -> [gradient all-reduce] -> grad-norm -> AdamW -> operand re-pack as ONE
-        hipGraph and replay it from train_step() (single micro-batch).  With a data-parallel reducer the per-layer RCCL
+        hipGraph and replay it from train_step().  With a data-parallel reducer the per-layer RCCL
         all-reduces are captured too: the reducer's side stream forks from the capturing stream when a bucket's last gradient
         has landed and joins it again in finish(), so inside the graph every collective is a node whose only dependencies are
         the backward kernels that produced its bucket -- the overlap of the eager path, without the host between the launches.
@@ -503,12 +505,34 @@ class _TrainerBase(_AdamState):
         torch's device RNG (config 5's position sampling) is capture-aware and advances per replay by itself.
         The warm-up steps run the real step body on `example_batch` (RCCL creates its communicator and the kernels their
         caches outside the capture); unless keep_warmup_updates, the weights, moments and step count they moved are restored,
-        so a run starts from the same state whether or not it is graphed."""
-        assert self.acc_steps == 1, 'the graphed step is one micro-batch per optimizer step'
+        so a run starts from the same state whether or not it is graphed.
+        accumulation_steps = K > 1 (main.py:221, :274-280; the trainers whose train_step accumulates): example_batch is a list of
+        K equal-shaped micro-batches, and the ONE graph holds the whole optimizer step -- gradient arena zeroed once, operands and
+        packs rebuilt once (the weights do not move between micro-batches), K x (corruption -> forward -> CE -> backward at
+        loss_scale 1/K, each from a Philox stream of its own: the device counter advances after every micro-batch), then one
+        reducer join, one AdamW, one EMA update, one packed read-back [loss_sum, sqnorm, the K x B per-sample losses].  The clips
+        live in one [K,B,S,H,W] buffer, the K x B noise levels in front of lr and the bias corrections in the one scalar buffer."""
+        K = self.acc_steps
+        if K > 1 and not self.graph_accumulates:
+            raise NotImplementedError(f'{type(self).__name__}.enable_graph: accumulation_steps = {K}, but this trainer has no gradient '
+                                      f'accumulation step to capture (its graphed step is one micro-batch per optimizer step)')
+        if isinstance(example_batch, (list, tuple)):
+            micro = list(example_batch)
+            if len(micro) != K or any(z.shape != micro[0].shape for z in micro):
+                raise ValueError(f'{type(self).__name__}.enable_graph: accumulation_steps = {K} needs {K} micro-batches of one shape, '
+                                 f'got {[tuple(z.shape) for z in micro]}')
+        elif K > 1:
+            raise ValueError(f'{type(self).__name__}.enable_graph: accumulation_steps = {K} captures the whole optimizer step: pass '
+                             f'a list of {K} equal-shaped [B,S,H,W] micro-batches (as to train_step), not a single tensor')
+        else:
+            micro = [example_batch]
         dev = self.arena.flat_param.device
-        self._g_z = example_batch.contiguous().clone()
-        # the step's host-written scalars live in ONE device buffer fed from ONE pinned host buffer: noise levels | lr, bias corrections
-        nb = example_batch.shape[0]
+        # K == 1: the [B,S,H,W] buffer itself; K > 1: one [K,B,S,H,W] buffer whose planes are the micro-batches
+        self._g_z = micro[0].contiguous().clone() if K == 1 else torch.stack([z.contiguous() for z in micro])
+        self._g_micro = [self._g_z] if K == 1 else list(self._g_z.unbind(0))
+        # the step's host-written scalars live in ONE device buffer fed from ONE pinned host buffer: noise levels (of every
+        # micro-batch, in order) | lr, bias corrections
+        nb = K * micro[0].shape[0]
         self._g_in = torch.zeros(nb + 3, dtype=torch.float32, device=dev)
         self._g_in_host = torch.zeros(nb + 3, dtype=torch.float32).pin_memory()
         self._g_in_np = self._g_in_host.numpy()
@@ -567,10 +591,19 @@ class _TrainerBase(_AdamState):
 
     def _set_step_inputs(self, r):
         """Host side of one graphed step: next noise levels and the optimizer scalars of step t into device memory."""
-        B = self._g_z.shape[0]
-        if r is None:
-            r = self.sampler.sample(B, generator=self.sampler_gen)
-        self._g_r_host = r
+        K, B = self.acc_steps, self._g_micro[0].shape[0]
+        if K == 1:
+            if r is None:
+                r = self.sampler.sample(B, generator=self.sampler_gen)
+            flat = r
+        else:
+            # every micro-batch's levels before the launch, drawn in the eager step's order; the sampler itself is updated when
+            # the step's losses are back (as the eager step does: _replay)
+            rs = list(r) if isinstance(r, (list, tuple)) else [r] * K
+            r = [self.sampler.sample(B, generator=self.sampler_gen) if rr is None else rr for rr in rs]
+            flat = torch.cat([rr.detach().reshape(-1).to('cpu', torch.float32) for rr in r])
+        B = K * B
+        self._g_r_host = r                 # (K > 1: the list of K, each handed back to the sampler with its micro-batch's losses)
         self.step_count += 1
         lr = lr_at(self.step_count, self.lr, self.warmup, self.max_steps)
         bc1 = 1.0 - self.betas[0] ** self.step_count
@@ -580,7 +613,7 @@ class _TrainerBase(_AdamState):
         if ev is not None:
             ev.synchronize()               # the last copy out of the pinned buffer is done (a no-op behind a step's read-back)
         hn = self._g_in_np                                 # (a view of the pinned buffer: element writes without tensor indexing --
-        hn[:B] = r.detach().reshape(-1).to('cpu', torch.float32).numpy()     # this runs with the GPU idle between two replays)
+        hn[:B] = flat.detach().reshape(-1).to('cpu', torch.float32).numpy()  # this runs with the GPU idle between two replays)
         hn[B], hn[B + 1], hn[B + 2] = lr, bc1, math.sqrt(bc2)
         self._g_in.copy_(h, non_blocking=True)
         if ev is None:
@@ -594,9 +627,22 @@ class _TrainerBase(_AdamState):
         # launch here, the fused kernels' weight streams by the forward (their cache entries are stale by construction)
         _cast.invalidate(self.arena.params)
         self._refresh_operands()
-        per_sample, mean = self._graph_step(self._g_z, self._g_r)      # subclass: corruption (device counter) -> forward / backward
-        self._g_ctr += 1
-        ops.wgrad_join()                   # (already joined by the autograd pass's end-of-backward callback)
+        K, B = self.acc_steps, self._g_micro[0].shape[0]
+        rows, loss_sum = [], None
+        for k, z in enumerate(self._g_micro):
+            # subclass: corruption (device counter as it stands) -> forward / backward of mean loss / K (main.py:274-278)
+            per_sample, mean = self._graph_step(z, self._g_r[k * B:(k + 1) * B], 1.0 / K)
+            self._g_ctr += 1               # the next micro-batch, and the next replay, draw from Philox streams of their own
+            # Weight gradients of ONE parameter from successive micro-batches accumulate into one arena address, some from the
+            # compute stream (the fused and chain backward kernels, _LinearCrossEntropy's arena shortcut in the forward), some
+            # from the weight-gradient side branch (ops.side_branch): every fork is JOINED before the next micro-batch issues
+            # anything -- by the autograd pass's end-of-backward callback, of which this call is the explicit form (a no-op
+            # behind it) -- so the accumulations are ordered by the graph's edges, not by launch order across two queues.  The
+            # tail of micro-batch k's weight gradients therefore does not overlap micro-batch k + 1's corruption and first
+            # forward kernels: profiles/graph_accumulation has what that costs.
+            ops.wgrad_join()
+            rows.append(per_sample.reshape(-1))
+            loss_sum = mean if K == 1 else (mean / K if loss_sum is None else loss_sum + mean / K)     # main.py:280
         # data parallel: buckets the backward did not launch itself, then the compute stream joins the reducer's side stream
         # (under capture: the fork / join edges of the graph); the 1/world of the gradient MEAN rides in the AdamW pass
         scale = self.reducer.finish() if self.reducer is not None else 1.0
@@ -605,23 +651,34 @@ class _TrainerBase(_AdamState):
         L.call('wmz_adamw_step_dev', L.ptr(a.flat_param), L.ptr(a.flat_grad), L.ptr(self.m), L.ptr(self.v), a.numel,
                L.ptr(self._g_hyper), self.betas[0], self.betas[1], self.eps, self.wd, float(scale), L.ptr(self.sq), st)   # + grad norm
         self._ema_update()
-        return torch.cat([mean.reshape(1), self.sq.reshape(1), per_sample.reshape(-1)])     # the step's one read-back, packed in the graph
+        return torch.cat([loss_sum.reshape(1), self.sq.reshape(1)] + rows)     # the step's one read-back, packed in the graph
 
 
     def _replay(self, batch_z, r):
         """One graphed step: inputs into the static buffers, one hipGraph launch, ONE host read-back (loss, grad-norm, per-sample
         losses for the loss-aware sampler).  Returns (mean loss, grad norm)."""
-        self._g_z.copy_(batch_z, non_blocking=True)
+        K = self.acc_steps
+        if K == 1:
+            self._g_z.copy_(batch_z, non_blocking=True)
+        else:
+            torch.stack(list(batch_z), out=self._g_z)   # the K micro-batches into their planes of the one buffer: one launch
         self._set_step_inputs(r)
         self._graph.replay()
         _cast.invalidate(self.arena.params)             # the replay rewrote the weights: eager consumers rebuild their operand copies
         out = self._g_out.cpu()                                                  # the step's one host sync
-        self.sampler.update_with_losses(self._g_r_host, out[2:])
+        if K == 1:
+            self.sampler.update_with_losses(self._g_r_host, out[2:])
+        else:
+            B = self._g_micro[0].shape[0]
+            for k, rr in enumerate(self._g_r_host):     # once per micro-batch, each with the levels it was given (main.py:271-272)
+                self.sampler.update_with_losses(rr, out[2 + k * B:2 + (k + 1) * B])
         return float(out[0]), math.sqrt(float(out[1]))
 
 
 class DenoiserTrainer(_TrainerBase):
     """The step body of vq-video-diffusion/main.py:train on [B,S,H,W] token clips (last frame corrupted and predicted)."""
+
+    graph_accumulates = True
 
     def forward_backward(self, batch_z, target, loss_scale=1.0):
         """Forward, per-sample CE over the last frame, backward of loss.mean() * loss_scale (gradient accumulation:
@@ -648,15 +705,15 @@ class DenoiserTrainer(_TrainerBase):
         (mean if loss_scale == 1.0 else mean * loss_scale).backward()
         return per_sample.detach(), mean.detach()
 
-    def _graph_step(self, z, r):
+    def _graph_step(self, z, r, loss_scale=1.0):
         zc, target = corrupt_last_frame(z, r, self.C, seed=self._g_seed, rank=self.rank, counter=self._g_ctr)
-        return self.forward_backward(zc, target)
+        return self.forward_backward(zc, target, loss_scale)
 
     def train_step(self, batch_z, r=None, generator=None):
         """corrupt -> forward/backward (all-reduce overlapped) -> grad-norm -> AdamW; sampler update on the host.
         batch_z: one micro-batch [B,S,H,W], or a list of `accumulation_steps` of them (main.py:221-280: gradients
         accumulate over the micro-batches, each micro-loss scaled by 1/acc_steps, loss_sum is their sum)."""
-        if self._graph is not None and not isinstance(batch_z, (list, tuple)) and batch_z.shape == self._g_z.shape:
+        if self._graph is not None and self._replayable(batch_z, r):
             return self._replay(batch_z, r)
         micro = list(batch_z) if isinstance(batch_z, (list, tuple)) else [batch_z]
         assert len(micro) == self.acc_steps, f'expected {self.acc_steps} micro-batches, got {len(micro)}'
@@ -674,6 +731,15 @@ class DenoiserTrainer(_TrainerBase):
         for rr, per_sample in seen:
             self.sampler.update_with_losses(rr, per_sample)   # the step's host sync (reference: ~50 per micro-batch)
         return float(loss_sum), math.sqrt(float(sq))
+
+    def _replayable(self, batch_z, r):
+        """The captured step takes these inputs: K == 1, one tensor of the captured shape; K > 1, K micro-batches of the captured
+        shape with r None or a list of K.  Anything else is the eager step's."""
+        K = self.acc_steps
+        if K == 1:
+            return not isinstance(batch_z, (list, tuple)) and batch_z.shape == self._g_z.shape
+        return (isinstance(batch_z, (list, tuple)) and len(batch_z) == K and all(z.shape == self._g_z.shape[1:] for z in batch_z)
+                and (r is None or (isinstance(r, (list, tuple)) and len(r) == K)))
 
 
 class SparseDenoiserTrainer(_TrainerBase):
@@ -711,7 +777,7 @@ class SparseDenoiserTrainer(_TrainerBase):
         mean.backward()                                    # (the accumulation scale is inside the fused gradient)
         return rows.view(tokens.shape[0], -1).mean(dim=1), mean.detach()
 
-    def _graph_step(self, z, r):
+    def _graph_step(self, z, r, loss_scale=1.0):
         """The device side of one step on static inputs (captured by enable_graph): position sampling (torch's capture-aware
         device RNG), gather, corruption from the in-kernel Philox stream counted on the device, forward / backward."""
         B = z.shape[0]
@@ -719,11 +785,11 @@ class SparseDenoiserTrainer(_TrainerBase):
             # one launch instead of ~45 graph nodes (window arithmetic on B-element tensors, top-k, sort, gather, corruption)
             indices, tokens, target = draw_sparse_context(z, r, self.num_context, self.model.shape, self.C, seed=self._g_seed,
                                                           rank=self.rank, counter=self._g_ctr)
-            return self.forward_backward(tokens, indices, target)
+            return self.forward_backward(tokens, indices, target, loss_scale)
         indices = self.sample_positions(B, r, z.device)
         gathered = torch.gather(z.reshape(B, -1), 1, indices)
         tokens, target = corrupt_tokens(gathered, r, self.C, seed=self._g_seed, rank=self.rank, counter=self._g_ctr)
-        return self.forward_backward(tokens, indices, target)
+        return self.forward_backward(tokens, indices, target, loss_scale)
 
     def fused_context(self, z):
         """The step prologue runs as wmz_sparse_draw_context: the reference's default sampler ('neighbors'), a grid the kernel
