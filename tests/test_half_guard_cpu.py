@@ -57,17 +57,16 @@ def test_guard_off_or_not_precise_wants_nothing():
 
 
 def test_guard_entry_points_are_declared_exported_and_bound():
-    from world_modelz_amd import _lib
-    hdr = open(os.path.join(ROOT, 'include', 'wmz.h')).read()
+    import abi_header
+    from world_modelz_amd import _lib, half_guard
     lib = _lib.lib()
     for n in ('wmz_half_guard_bind', 'wmz_half_guard_clear'):
-        assert re.search(r'\b' + n + r'\s*\(', hdr), n
-        assert n in _lib.SIGNATURES and hasattr(lib, n), n
+        abi_header.assert_bound(lib, n)
         assert not any(s in n for s in ('layer_fused', 'layer_chain', 'embed_qkv_fused'))
     assert lib.wmz_version() == _lib.EXPECTED_VERSION == 115           # the guard adds entry points, changes none
-    m = re.search(r'WMZ_HG_STREAM = (\d+).*?WMZ_HG_QKV = (\d+).*?WMZ_HG_CONV = (\d+)', hdr, flags=re.S)
-    from world_modelz_amd import half_guard
-    assert m and tuple(int(g) for g in m.groups()) == tuple(b for b, _ in half_guard.KINDS)
+    kinds = abi_header.constants('WMZ_HG_')
+    assert list(kinds) == ['WMZ_HG_STREAM', 'WMZ_HG_QKV', 'WMZ_HG_CONV']
+    assert tuple(kinds.values()) == tuple(b for b, _ in half_guard.KINDS) == (1, 2, 4)
 
 
 # (VGPRs incl. AGPRs, scratch bytes) of every kernel of the half denoiser units in the PARENT commit's build (dee100e), taken with

@@ -264,11 +264,9 @@ def test_lr_schedule_and_sampler_match_golden():
 
 def test_c_abi_exports_every_declared_symbol():
     """include/wmz.h <-> libwmz_hip.so: the library loads on a CPU-only host and exports every entry point."""
-    import re
+    import abi_header
     from world_modelz_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, 'include', 'wmz.h')).read()
-    declared = set(re.findall(r'\b(wmz_[a-z0-9_]+)\s*\(', hdr))
+    declared = abi_header.declared()
     assert len(declared) >= 15
     lib = _lib.lib()
     assert lib.wmz_version() >= 100
@@ -276,6 +274,7 @@ def test_c_abi_exports_every_declared_symbol():
     assert not missing, missing
     for n in declared - {'wmz_version', 'wmz_last_error'}:
         assert n in _lib.SIGNATURES, f'{n} has no ctypes signature'
+    assert set(_lib.SIGNATURES) == declared | abi_header.declared(abi_header.DEBUG_HEADER)
 
 
 def test_cone_planes_schedule():

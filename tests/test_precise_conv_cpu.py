@@ -63,12 +63,12 @@ def test_half_direct_conv_never_touches_loads_in_flight():
 
 
 def test_half_conv_entry_points_are_declared_and_bound():
+    import abi_header
     from world_modelz_amd import _lib
-    hdr = open(os.path.join(ROOT, 'include', 'wmz.h')).read()
-    for n in ('wmz_conv3x3_direct_fwd_strided_f16', 'wmz_conv_point_fwd_bn_f16'):
-        assert re.search(r'\b' + n + r'\s*\(', hdr), n
-        assert _lib.SIGNATURES[n] == _lib.SIGNATURES[n[:-4]], n
     lib = _lib.lib()
+    for n in ('wmz_conv3x3_direct_fwd_strided_f16', 'wmz_conv_point_fwd_bn_f16'):
+        abi_header.assert_bound(lib, n)
+        assert _lib.SIGNATURES[n] == _lib.SIGNATURES[n[:-4]], n
     assert lib.wmz_version() == _lib.EXPECTED_VERSION == 115
     # the half forms share the bfloat16 units' format-agnostic entry points: one of each
     for n in ('wmz_conv3x3_direct_fwd_strided_f16', 'wmz_conv_point_fwd_bn_f16', 'wmz_nchw_to_nhwc8', 'wmz_conv3x3_direct_pack'):

@@ -16,9 +16,7 @@ for _ in range(5):
 torch.cuda.synchronize()
 n = 4096
 buf = (ctypes.c_ulonglong * (n * 8))()
-fn = L.lib().wmz_debug_conv_stamps
-fn.argtypes = [ctypes.c_void_p, ctypes.c_int]
-assert fn(buf, n * 8) == 0
+assert L.lib().wmz_debug_conv_stamps(buf, n * 8) == 0
 a = np.frombuffer(buf, dtype=np.uint64).reshape(n, 8).astype(np.int64)
 a = a[a[:, 0] > 0]
 t0 = a[:, 0].min()

@@ -143,7 +143,8 @@ class BulkOperands:
                     s0[i], s1[i], r0[i], r1[i] = a.data_ptr(), (b.data_ptr() if b is not None else None), a.shape[0], (b.shape[0] if b is not None else 0)
                 cc[i] = a.numel() // a.shape[0]
                 dd[i] = dst.data_ptr()
-                ff[i] = (1 if tr else 0) | (2 if dtype == torch.float32 else 0)
+                ff[i] = ((L.CONSTANTS['WMZ_OPERAND_TRANSPOSE'] if tr else 0)
+                         | (L.CONSTANTS['WMZ_OPERAND_F32'] if dtype == torch.float32 else 0))
             L.call('wmz_operands_refresh', s0, s1, r0, r1, cc, dd, ff, n, L.stream())
         for params, dtype, tag, tr, zf, dst in self.entries:
             ver = (_epoch,) + tuple((p._version, p.data_ptr()) for p in params)

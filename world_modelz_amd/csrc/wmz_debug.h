@@ -32,6 +32,12 @@ int wmz_debug_linear_knobs(int dma);
  * profiler's own per-node cost (rocprofv3 --kernel-trace: ~9 us a node) would distort the very overlap under study. */
 int wmz_debug_stamp(void* buf, int slot, void* stream);
 
+/* In-kernel stage stamps of the direct convolution (csrc/conv_direct.hip, built with -DWMZ_CONV_STAMPS) and of the 256-wide
+ * weight-gradient kernel (csrc/linear_bwd.hip, -DWMZ_W3_STAMPS): copies the n 64-bit words the last launch left into the HOST
+ * array out.  Exported by such builds only (tools/build_variant.py, tools/conv_stamps.py). */
+int wmz_debug_conv_stamps(unsigned long long* out, int n);
+int wmz_debug_w3_stamps(unsigned long long* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

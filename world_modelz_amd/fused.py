@@ -193,7 +193,7 @@ def _chain_pack(head, tail, D, I, M, MC, dt=torch.bfloat16):
         assert stream.shape[0] % sp == 0
         wpack = torch.cat([stream.reshape(-1), stream.new_zeros(3 * sp * 512)]).to(dt).contiguous()
         return wpack, vec
-    return _cast.cached(_boundary_params(head, tail), f'chainpack{D}_{I}_{M}{_sfx(dt)}', build)
+    return _cast.cached(_boundary_params(head, tail), L.half_form(f'chainpack{D}_{I}_{M}', dt), build)
 
 
 def transformer_forward_chain(tr, z):
@@ -215,7 +215,7 @@ def transformer_forward_chain(tr, z):
         xo = torch.empty((B, S, H, W, D), dtype=bf, device=dev) if head is not None else None
         q = torch.empty((B, S, H, W, I), dtype=bf, device=dev) if tail is not None else None
         kv = torch.empty((2, B, S, H, W, I), dtype=bf, device=dev) if tail is not None else None
-        L.call('wmz_layer_chain_fwd_planes' + _sfx(bf), L.ptr(o), L.ptr(x_in), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
+        L.call(L.half_form('wmz_layer_chain_fwd_planes', bf), L.ptr(o), L.ptr(x_in), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
                B, S, S, HW, D, I, M, 1 if head is not None else 0, 1 if tail is not None else 0, 1e-5, L.stream())
         return xo, q, kv
     _, q, kv = launch(None, x, None, layers[0])
@@ -434,10 +434,6 @@ def _chain_layer_backward(packs, l, attn, ff, dy, x_in, q, kv, o, lse, x1, st_at
                                    (dq.reshape(ntok, I), x_in.reshape(ntok, D), False), (dkv.reshape(ntok, 2 * I), xh_attn), True)
 
 
-def _sfx(dt):
-    return '_f16' if dt == torch.float16 else ''
-
-
 def _boundary_params(head, tail):
     """The parameters one forward launch between two attention launches reads: head = (attn, ff) PreNorms of the layer whose
     to_out + feed-forward run -- wout, bout, g2, be2, w1, b1, w2, b2 --, tail = those of the layer whose q | k | v run -- g1, be1,
@@ -468,10 +464,10 @@ def _layer_pack(head, tail, dt=torch.bfloat16):
         dev = ps[0].device
         wpack = torch.empty(nw + _PAD // 2, dtype=dt, device=dev)
         vec = torch.empty(2048, dtype=torch.float32, device=dev)
-        L.call('wmz_layer_fused_pack' + _sfx(dt), *[L.ptr(t) for t in hp], *[L.ptr(t) for t in tp], L.ptr(wpack), L.ptr(vec),
+        L.call(L.half_form('wmz_layer_fused_pack', dt), *[L.ptr(t) for t in hp], *[L.ptr(t) for t in tp], L.ptr(wpack), L.ptr(vec),
                D_, I_, M_, L.stream())
         return wpack, vec
-    return _cast.cached(_boundary_params(head, tail), 'fusedpack' + _sfx(dt), build)
+    return _cast.cached(_boundary_params(head, tail), L.half_form('fusedpack', dt), build)
 
 
 def _layer_pack_bwd(attn, ff):
@@ -587,7 +583,8 @@ class PackSet:
             _cast._cache[_cast._key(params, None, tag)] = (ver, val, tuple(weakref.ref(p) for p in params))
 
 
-X_IN_TILED, X_OUT_TILED, X1_NORMALISED, XRM_NORMALISED = 1, 2, 4, 8      # include/wmz.h WMZ_FUSED_X*
+X_IN_TILED, X_OUT_TILED, X1_NORMALISED, XRM_NORMALISED = (
+    L.CONSTANTS['WMZ_FUSED_' + n] for n in ('X_IN_TILED', 'X_OUT_TILED', 'X1_NORMALISED', 'XRM_NORMALISED'))
 
 
 def layer_fused(o, x, head, tail, eps=1e-5, xflags=0):
@@ -599,7 +596,7 @@ def layer_fused(o, x, head, tail, eps=1e-5, xflags=0):
     xo = torch.empty_like(x) if head is not None else None
     q = torch.empty(lead + (I_,), dtype=x.dtype, device=x.device) if tail is not None else None
     kv = torch.empty((2,) + lead + (I_,), dtype=x.dtype, device=x.device) if tail is not None else None
-    L.call('wmz_layer_fused_fwd_planes' + _sfx(x.dtype), L.ptr(o), L.ptr(x), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
+    L.call(L.half_form('wmz_layer_fused_fwd_planes', x.dtype), L.ptr(o), L.ptr(x), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
            1, 1, 1, ntok, D_, I_, M_, 1 if head is not None else 0, 1 if tail is not None else 0, int(xflags), float(eps),
            L.stream())
     return xo, q, kv
@@ -675,13 +672,12 @@ def _run_chain(tr, z, cone, out):
     tiled = HW % 32 == 0                      # whole 32-token tiles per plane: the stream between layers stays tiled
     from . import config
     dev, bf = z.device, config.get_fused_dtype()          # (bf: bfloat16, or float16 in the precise mode)
-    sfx = _sfx(bf)
     n0 = src[0]
     wpack, vec = _layer_pack(None, layers[0], bf)
     x = torch.empty((B, n0, H, W, D_), dtype=bf, device=dev)
     q = torch.empty((B, n0, H, W, I_), dtype=bf, device=dev)
     kv = torch.empty((2, B, n0, H, W, I_), dtype=bf, device=dev)          # k planes, then v planes
-    L.call('wmz_embed_qkv_fused_fwd_planes' + sfx, L.ptr(z.contiguous()), L.ptr(tr.embedding.weight.detach()),
+    L.call(L.half_form('wmz_embed_qkv_fused_fwd_planes', bf), L.ptr(z.contiguous()), L.ptr(tr.embedding.weight.detach()),
            L.ptr(tr.pos_emb_s.weight.detach()), L.ptr(tr.pos_emb_h.weight.detach()), L.ptr(tr.pos_emb_w.weight.detach()),
            L.ptr(x), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec), B, S, H, W, n0, D_, I_, M_,
            tr.embedding.num_embeddings, X_OUT_TILED if tiled else 0, 1e-5, L.stream())
@@ -698,7 +694,7 @@ def _run_chain(tr, z, cone, out):
         q = torch.empty((B, n_q, H, W, I_), dtype=bf, device=dev) if tail is not None else None
         kv = torch.empty((2, B, n_q, H, W, I_), dtype=bf, device=dev) if tail is not None else None
         xflags = (X_IN_TILED if tiled else 0) | (X_OUT_TILED if tiled and tail is not None else 0)
-        L.call('wmz_layer_fused_fwd_planes' + sfx, L.ptr(o), L.ptr(x), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
+        L.call(L.half_form('wmz_layer_fused_fwd_planes', bf), L.ptr(o), L.ptr(x), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
                B, n_q, n_in, HW, D_, I_, M_, 1, 1 if tail is not None else 0, xflags, 1e-5, L.stream())
         x = xo
     return x

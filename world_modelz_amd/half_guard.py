@@ -14,7 +14,8 @@ import torch
 from . import _lib as L
 from . import config
 
-KINDS = ((1, 'the residual stream'), (2, 'q / k | v'), (4, 'a conv activation'))          # include/wmz.h WMZ_HG_*
+KINDS = ((L.CONSTANTS['WMZ_HG_STREAM'], 'the residual stream'), (L.CONSTANTS['WMZ_HG_QKV'], 'q / k | v'),
+         (L.CONSTANTS['WMZ_HG_CONV'], 'a conv activation'))
 
 _words = {}          # device index -> the bound word (int32[1])
 _tls = threading.local()          # .depth > 0: this thread is inside a guarded call (or suspended)

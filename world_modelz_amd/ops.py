@@ -74,7 +74,7 @@ def linear_fwd(a, weight, bias=None, residual=None, ln=None, ln_eps=1e-5, gelu=F
         mean, rstd = ln_stats
         assert ln is not None and mean.numel() == M and rstd.numel() == M
     # (half operands: the precise fused mode's unit of the same kernel, include/wmz.h)
-    L.call('wmz_linear_fwd_stats' + ('_f16' if a.dtype == torch.float16 else ''), L.ptr(a), lda, L.ptr(weight), L.ptr(bias), L.ptr(residual), ldr, L.ptr(out), ldc,
+    L.call(L.half_form('wmz_linear_fwd_stats', a.dtype), L.ptr(a), lda, L.ptr(weight), L.ptr(bias), L.ptr(residual), ldr, L.ptr(out), ldc,
            M, N, K, L.ptr(g), L.ptr(b), L.ptr(mean), L.ptr(rstd), float(ln_eps),
            (L.WMZ_LIN_GELU if gelu else 0) | (L.WMZ_LIN_GELU_IN if gelu_in else 0), 1 if out_f32 else 0, dt,
            L.stream())
@@ -138,7 +138,7 @@ def linear_fwd_blocks(a, weight, bias=None, out_f32=False):
     N = weight.shape[0]
     assert a.stride(2) == 1 and weight.dtype == a.dtype and weight.is_contiguous() and weight.shape[1] == K
     out = torch.empty((Bk, R, N), dtype=torch.float32 if out_f32 else a.dtype, device=a.device)
-    L.call('wmz_linear_fwd_blocked' + ('_f16' if a.dtype == torch.float16 else ''), L.ptr(a), a.stride(1), R, a.stride(0), L.ptr(weight), L.ptr(bias), L.ptr(out), N,
+    L.call(L.half_form('wmz_linear_fwd_blocked', a.dtype), L.ptr(a), a.stride(1), R, a.stride(0), L.ptr(weight), L.ptr(bias), L.ptr(out), N,
            Bk * R, N, K, 1 if out_f32 else 0, L.dtype_code(a.dtype), L.stream())
     return out
 
@@ -753,7 +753,7 @@ def embed_pos3d_bwd(z, dx, tabs):
 
 # ------------------------------------------------------------------------------------------------ conv AE (NHWC)
 
-STAT_REPLICAS = 8          # include/wmz.h: WMZ_STAT_REPLICAS
+STAT_REPLICAS = L.CONSTANTS['WMZ_STAT_REPLICAS']
 
 
 DIRECT_CONV = True         # tools / tests: False keeps every convolution on the implicit-GEMM kernel (A/B comparisons)
@@ -824,10 +824,9 @@ def conv2d_nhwc(x, w_op, KH, KW, stride, pad, bias=None, scale=None, shift=None,
         raise L.WmzError(f'conv2d_nhwc: no half kernel for B={B} {Hi}x{Wi} Cin={Cin} Cout={Cout} {KH}x{KW}/s{stride}/p{pad}'
                          f'{" + residual" if residual is not None else ""}{" + prologue" if pre is not None else ""} '
                          '(the precise conv route runs a pass in half only when every layer has one: autoencoder.conv_route)')
-    sfx = '_f16' if half else ''
     if fam == 'direct':
         # csrc/conv_direct.hip: the haloed patch by LDS-DMA, decoupled waves (same arithmetic as the implicit-GEMM kernel)
-        L.call('wmz_conv3x3_direct_fwd_strided' + sfx, L.ptr(x), L.ptr(_direct_pack(w_op, Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
+        L.call(L.half_form('wmz_conv3x3_direct_fwd_strided', x.dtype), L.ptr(x), L.ptr(_direct_pack(w_op, Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
                L.ptr(shift), L.ptr(residual), L.ptr(s), L.ptr(q), B, Hi, Wi, Cin, Cout, stride, 1 if leaky else 0, float(slope),
                L.stream())
         return (out, s, q) if stats else out
@@ -841,7 +840,7 @@ def conv2d_nhwc(x, w_op, KH, KW, stride, pad, bias=None, scale=None, shift=None,
             psc, psh = psc.materialize()
     if point:
         # csrc/conv_point.hip: small-K layers (1x1, 2x2 / stride 2, the 3-channel conv_1) as a persistent streaming kernel
-        L.call('wmz_conv_point_fwd_bn' + sfx, L.ptr(x), L.ptr(_point_pack(w_op, KH * KW * Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
+        L.call(L.half_form('wmz_conv_point_fwd_bn', x.dtype), L.ptr(x), L.ptr(_point_pack(w_op, KH * KW * Cin, Cout)), L.ptr(out), L.ptr(bias), L.ptr(scale),
                L.ptr(shift), L.ptr(s), L.ptr(q), L.ptr(psc), L.ptr(psh), ctypes.addressof(pst) if pst is not None else None, float(psl),
                B, Hi, Wi, Cin, Cout, KH, KW, stride, pad, 1 if leaky else 0, float(slope), L.stream())
         return (out, s, q) if stats else out
