@@ -1,4 +1,14 @@
-"""Operand-dtype copies of fp32 parameters, cached per (parameter version, dtype)."""
+"""Operand-dtype copies of fp32 parameters (and anything else built from them), cached until a parameter changes.
+
+An entry is `(stamp, value, weak references to the parameters)` under the key `(tag, dtype, id() of each parameter)`.  It is
+served only while all of this holds (_stamp_of and _current, the one implementation of the rule):
+  - the global epoch has not moved (invalidate(): weights rewritten behind torch's version counters);
+  - every parameter's `_version` is the one the entry was stored at (in-place writes: optimizer step, load_state_dict);
+  - every parameter's `data_ptr()` is (re-allocation: .to(), `p.data = ..`);
+  - the weak references still point at these very objects: the key is made of id()s, and a freed parameter's id (and storage
+    address, and version) can come back with another model's tensor.
+operand() and cached() build a missing or stale entry themselves; stamp() records a value that a bulk refresher (BulkOperands,
+ConvOperands, fused.PackSet) has just rebuilt into its own persistent buffer, so that the getters hit."""
 import weakref
 
 import torch
@@ -11,6 +21,33 @@ def _key(ts, dtype, tag):
     return (tag, dtype) + tuple(id(t) for t in ts)
 
 
+def _stamp_of(params):
+    return (_epoch,) + tuple((p._version, p.data_ptr()) for p in params)
+
+
+def _current(hit, params):
+    """Is this cache hit the value of these very objects, as they are now?"""
+    return hit is not None and hit[0] == _stamp_of(params) and all(r() is p for r, p in zip(hit[2], params))
+
+
+def _store(key, params, value):
+    _sweep()
+    _cache[key] = (_stamp_of(params), value, tuple(weakref.ref(p) for p in params))
+    return value
+
+
+def stamp(params, dtype, tag, value):
+    """Record `value` -- rebuilt from `params` as they are now by someone else's launch, into a buffer that persists -- as the
+    current entry operand(params, dtype, tag, ..) looks up (dtype None: cached(params, tag, ..))."""
+    params = tuple(params)
+    _store(_key(params, dtype, tag), params, value)
+
+
+def held():
+    """The values the cache holds now (tensors or tuples of tensors): what a captured graph keeps strong references to."""
+    return [h[1] for h in _cache.values()]
+
+
 def operand(params, dtype, tag='w', build=None):
     """Return `build(*params)` (default: the single parameter itself) cast to `dtype`, contiguous, cached until
     any of the parameters is modified in place (optimizer step, load_state_dict) or re-allocated (.to())."""
@@ -18,19 +55,24 @@ def operand(params, dtype, tag='w', build=None):
         params = (params,)
     if build is None and len(params) == 1 and params[0].dtype == dtype and params[0].is_contiguous():
         return params[0].detach()
+    return _get(params, dtype, tag, build, True)
+
+
+def cached(params, tag, build):
+    """Like operand(), for values that are not a single cast tensor: `build(*params)` is kept until any parameter changes."""
+    return _get(tuple(params), None, tag, build, False)
+
+
+def _get(params, dtype, tag, build, cast):
     key = _key(params, dtype, tag)
-    ver = (_epoch,) + tuple((p._version, p.data_ptr()) for p in params)
     hit = _cache.get(key)
-    # the key is made of id()s: a freed parameter's id (and storage address, and version) can come back with another
-    # model's parameter, so an entry only counts while its weak references still point at these very objects
-    if hit is not None and hit[0] == ver and all(r() is p for r, p in zip(hit[2], params)):
+    if _current(hit, params):
         return hit[1]
     with torch.no_grad():
-        src = build(*params) if build is not None else params[0]
-        val = src.detach().to(dtype).contiguous()
-    _sweep()
-    _cache[key] = (ver, val, tuple(weakref.ref(p) for p in params))
-    return val
+        val = build(*params) if build is not None else params[0]
+        if cast:
+            val = val.detach().to(dtype).contiguous()
+    return _store(key, params, val)
 
 
 _sweep_at = 256
@@ -45,21 +87,6 @@ def _sweep():
     for k in [k for k, h in _cache.items() if any(r() is None for r in h[2])]:
         del _cache[k]
     _sweep_at = max(256, 2 * len(_cache))
-
-
-def cached(params, tag, build):
-    """Like operand(), for values that are not a single cast tensor: `build(*params)` is kept until any parameter changes."""
-    params = tuple(params)
-    key = _key(params, None, tag)
-    ver = (_epoch,) + tuple((p._version, p.data_ptr()) for p in params)
-    hit = _cache.get(key)
-    if hit is not None and hit[0] == ver and all(r() is p for r, p in zip(hit[2], params)):
-        return hit[1]
-    with torch.no_grad():
-        val = build(*params)
-    _sweep()
-    _cache[key] = (ver, val, tuple(weakref.ref(p) for p in params))
-    return val
 
 
 _scoped = {}       # id(parameter) -> [weakref to it, how often invalidate(params) named it]
@@ -108,9 +135,8 @@ def clear():
 class BulkOperands:
     """Operand copies that are rebuilt together, by ONE launch of wmz_operands_refresh (training: after every optimizer
     step).  Each entry is registered under the same (params, dtype, tag) key the forward / backward code asks operand()
-    for; refresh() fills the persistent destination tensors and stamps the cache entries valid for the current parameter
-    versions, so those operand() calls hit.  Anything not registered, or invalidated in another way, still takes the
-    ordinary per-operand path."""
+    for; refresh() fills the persistent destination tensors and records each with stamp(), so those operand() calls hit.
+    Anything not registered, or invalidated in another way, still takes the ordinary per-operand path."""
 
     def __init__(self):
         self.entries = []          # (params, dtype, tag, transpose, zero_first, dst)
@@ -126,35 +152,29 @@ class BulkOperands:
         return dst
 
     def refresh(self):
-        import ctypes
         from . import _lib as L
+        T, F32 = L.CONSTANTS['WMZ_OPERAND_TRANSPOSE'], L.CONSTANTS['WMZ_OPERAND_F32']
         for i0 in range(0, len(self.entries), 64):
-            ent = self.entries[i0:i0 + 64]
-            n = len(ent)
-            vp, ci = ctypes.c_void_p * n, ctypes.c_int * n
-            s0, s1, r0, r1, cc, dd, ff = vp(), vp(), ci(), ci(), ci(), vp(), ci()
-            for i, (params, dtype, tag, tr, zf, dst) in enumerate(ent):
+            rows = []           # (source 0 | None = zero rows, source 1 | None, rows 0, rows 1, columns, destination, flags)
+            for params, dtype, tag, tr, zf, dst in self.entries[i0:i0 + 64]:
                 a = params[0].detach()
                 b = params[1].detach() if len(params) > 1 else None
                 assert a.dtype == torch.float32 and a.is_contiguous() and (b is None or b.is_contiguous())
                 if zf:
-                    s0[i], s1[i], r0[i], r1[i] = None, a.data_ptr(), a.shape[0], a.shape[0]
+                    src = (None, a.data_ptr(), a.shape[0], a.shape[0])
                 else:
-                    s0[i], s1[i], r0[i], r1[i] = a.data_ptr(), (b.data_ptr() if b is not None else None), a.shape[0], (b.shape[0] if b is not None else 0)
-                cc[i] = a.numel() // a.shape[0]
-                dd[i] = dst.data_ptr()
-                ff[i] = ((L.CONSTANTS['WMZ_OPERAND_TRANSPOSE'] if tr else 0)
-                         | (L.CONSTANTS['WMZ_OPERAND_F32'] if dtype == torch.float32 else 0))
-            L.call('wmz_operands_refresh', s0, s1, r0, r1, cc, dd, ff, n, L.stream())
+                    src = (a.data_ptr(), b.data_ptr() if b is not None else None, a.shape[0], b.shape[0] if b is not None else 0)
+                rows.append(src + (a.numel() // a.shape[0], dst.data_ptr(),
+                                   (T if tr else 0) | (F32 if dtype == torch.float32 else 0)))
+            L.call('wmz_operands_refresh', *L.columns(rows, 'ppiiipi'), len(rows), L.stream())
         for params, dtype, tag, tr, zf, dst in self.entries:
-            ver = (_epoch,) + tuple((p._version, p.data_ptr()) for p in params)
-            _cache[_key(params, dtype, tag)] = (ver, dst, tuple(weakref.ref(p) for p in params))
+            stamp(params, dtype, tag, dst)
 
 
 class ConvOperands:
     """The conv encoder / decoder's GEMM operands (autoencoder.py: tags 'conv' and 'convT'), rebuilt together by ONE launch of
-    wmz_conv_operands_refresh_packed after every optimizer step; refresh() stamps the cache entries valid for the current weights,
-    so the forward / backward's operand() calls hit (built with tensor ops: permute, pad, flip, cast -- ~6 launches per layer).
+    wmz_conv_operands_refresh_packed after every optimizer step; refresh() records each with stamp(), so the forward / backward's
+    operand() calls hit (built with tensor ops otherwise: permute, pad, flip, cast -- ~6 launches per layer).
     bf16: the same launch also writes the fragment-order weight streams of the direct kernels (csrc/conv_direct.hip,
     csrc/conv_point.hip: ops._direct_pack / ops._point_pack, cached per operand tensor) -- 34 pack launches per step otherwise."""
 
@@ -178,23 +198,16 @@ class ConvOperands:
                     self.entries.append((w, 'convp', mode, 2, torch.empty(n, dtype=dtype, device=w.device), op))
 
     def refresh(self):
-        import ctypes
         from . import _lib as L
         for i0 in range(0, len(self.entries), 48):
-            ent = self.entries[i0:i0 + 48]
-            n = len(ent)
-            vp, ci_ = ctypes.c_void_p * n, ctypes.c_int * n
-            ws, ds, cos, cis, kks, ms, pk = vp(), vp(), ci_(), ci_(), ci_(), ci_(), ci_()
-            for i, (w, tag, mode, pack, dst, _op) in enumerate(ent):
+            rows = []           # (weight, destination, C_out, C_in, kh * kw, mode, pack kind)
+            for w, tag, mode, pack, dst, _op in self.entries[i0:i0 + 48]:
                 wd = w.detach()
                 assert wd.dtype == torch.float32 and wd.is_contiguous()
-                ws[i], ds[i] = wd.data_ptr(), dst.data_ptr()
-                cos[i], cis[i], kks[i], ms[i], pk[i] = w.shape[0], w.shape[1], w.shape[2] * w.shape[3], mode, pack
-            L.call('wmz_conv_operands_refresh_packed', ws, ds, cos, cis, kks, ms, pk, n, L.dtype_code(self.dtype), L.stream())
+                rows.append((wd.data_ptr(), dst.data_ptr(), w.shape[0], w.shape[1], w.shape[2] * w.shape[3], mode, pack))
+            L.call('wmz_conv_operands_refresh_packed', *L.columns(rows, 'ppiiiii'), len(rows), L.dtype_code(self.dtype), L.stream())
         for w, tag, mode, pack, dst, op in self.entries:
             if pack == 0:
-                ver = (_epoch, (w._version, w.data_ptr()))
-                _cache[_key((w,), self.dtype, tag)] = (ver, dst, (weakref.ref(w),))
+                stamp((w,), self.dtype, tag, dst)
             else:               # keyed by the operand tensor it re-orders (ops._direct_pack / _point_pack -> cached((op,), tag, ..))
-                ver = (_epoch, (op._version, op.data_ptr()))
-                _cache[_key((op,), None, tag)] = (ver, dst, (weakref.ref(op),))
+                stamp((op,), None, tag, dst)

@@ -151,5 +151,15 @@ def ptr(t):
     return t.data_ptr()
 
 
+_COLUMN = {'p': c_void_p, 'i': c_int, 'l': c_long}
+
+
+def columns(rows, kinds):
+    """The per-problem argument arrays of a batched entry point: rows = one tuple per problem, kinds = one letter per column
+    ('p' pointer: an address or None for NULL, 'i' int, 'l' long) -> one ctypes array of len(rows) per column."""
+    assert all(len(r) == len(kinds) for r in rows)
+    return [(_COLUMN[k] * len(rows))(*[r[j] for r in rows]) for j, k in enumerate(kinds)]
+
+
 def stream():
     return torch.cuda.current_stream().cuda_stream

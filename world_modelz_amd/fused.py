@@ -492,9 +492,9 @@ class PackSet:
     """Every packed weight stream / vector block the fused kernels of one transformer read -- the forward boundaries
     (_layer_pack) and each layer's two backward streams (_layer_pack_bwd) -- rebuilt together by ONE call of
     wmz_fused_pack_table (two launches) instead of a launch pair per stream.  The block descriptors are device-resident
-    tables built once (rebuilt if a parameter moves); refresh() fills the persistent buffers and stamps the very cache
-    entries _layer_pack / _layer_pack_bwd look up, so the forward and backward code is unchanged.  Training calls it after
-    every optimizer step (train.py), next to _cast.BulkOperands.refresh()."""
+    tables built once (rebuilt if a parameter moves); refresh() fills the persistent buffers and records each with _cast.stamp()
+    under the key _layer_pack / _layer_pack_bwd look up, so the forward and backward code is unchanged.  Training calls it
+    after every optimizer step (train.py), next to _cast.BulkOperands.refresh()."""
 
     def __init__(self, tr, backward=True):
         self.tr = tr
@@ -571,7 +571,6 @@ class PackSet:
         self._ptrs = [p.data_ptr() for p in self._params()]
 
     def refresh(self):
-        import weakref
         ps = self._params()
         assert all(p.dtype == torch.float32 and p.is_contiguous() for p in ps)
         if [p.data_ptr() for p in ps] != self._ptrs:
@@ -579,8 +578,7 @@ class PackSet:
         L.call('wmz_fused_pack_table', L.ptr(self.rows), self.nblk, self.total8, L.ptr(self.jobs), self.njobs, D_, I_, M_,
                L.stream())
         for params, tag, val in self.entries:
-            ver = (_cast._epoch,) + tuple((p._version, p.data_ptr()) for p in params)
-            _cast._cache[_cast._key(params, None, tag)] = (ver, val, tuple(weakref.ref(p) for p in params))
+            _cast.stamp(params, None, tag, val)
 
 
 X_IN_TILED, X_OUT_TILED, X1_NORMALISED, XRM_NORMALISED = (
@@ -806,17 +804,8 @@ def _zero_row(dev):
 
 def _ln_affine_grads_batch(probs):
     """wmz_ln_affine_grads_batch on a list of (G, s, W, gamma, beta, dW, dbias | None, dgamma, dbeta, N, K, bias_from)."""
-    import ctypes
-    n = len(probs)
-    vp, ci = ctypes.c_void_p * n, ctypes.c_int * n
-    cols = [vp() for _ in range(9)]
-    Ns, Ks, bf = ci(), ci(), ci()
-    for i, pr in enumerate(probs):
-        for j in range(9):
-            t = pr[j]
-            cols[j][i] = L.ptr(t.detach() if (t is not None and t.requires_grad) else t)
-        Ns[i], Ks[i], bf[i] = pr[9], pr[10], pr[11]
-    L.call('wmz_ln_affine_grads_batch', n, *cols, Ns, Ks, bf, L.stream())
+    rows = [tuple(L.ptr(t) for t in pr[:9]) + tuple(pr[9:12]) for pr in probs]
+    L.call('wmz_ln_affine_grads_batch', len(probs), *L.columns(rows, 'p' * 9 + 'iii'), L.stream())
 
 
 def _layer_weight_grads(attn, ff, ff2, ff1, out, q, kv, chain):

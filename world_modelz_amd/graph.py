@@ -89,7 +89,7 @@ class GraphedForward:
             self.static_out = self.model(self.static_in)
             if self.post is not None:
                 self.post(self.static_out)
-        self._operands = [h[1] for h in _cast._cache.values()]      # strong references (tensors or tuples of tensors)
+        self._operands = _cast.held()           # strong references (tensors or tuples of tensors)
         self.stamp = self._stamp()
 
     def refresh(self):

@@ -433,23 +433,16 @@ def linear_wgrad_batch_ln(problems, side=None):
     """Up to 6 weight gradients, each with an optional LayerNorm prologue, by one launch pair (wmz_linear_wgrad_batch_ln).
     problems: dicts with dc, a (2-D views, row strides ldc / lda), dw, dbias | None, M, N, K, g, b, mean, rstd (None = plain),
     overwrite.  side: the side-stream entry whose workspace to use."""
-    import ctypes
-    n = len(problems)
-    vp, ci, cl = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_long * n
-    pc, pa, pw, pb, pg, pbe, pm, pr = vp(), vp(), vp(), vp(), vp(), vp(), vp(), vp()
-    lc, la, Ms, Ns, Ks, ov = cl(), cl(), ci(), ci(), ci(), ci()
-    need = 0
+    rows, need = [], 0          # rows: one problem's per-problem arguments, in the entry point's order
     dt = L.dtype_code(problems[0]['dc'].dtype)
-    for i, q in enumerate(problems):
+    for q in problems:
         assert L.dtype_code(q['dc'].dtype) == dt and q['a'].dtype == q['dc'].dtype and q['dw'].dtype == torch.float32
-        pc[i], pa[i], pw[i], pb[i] = L.ptr(q['dc']), L.ptr(q['a']), L.ptr(q['dw']), L.ptr(q['dbias'])
-        pg[i], pbe[i], pm[i], pr[i] = L.ptr(q['g']), L.ptr(q['b']), L.ptr(q['mean']), L.ptr(q['rstd'])
-        lc[i], la[i], Ms[i], Ns[i], Ks[i], ov[i] = q['ldc'], q['lda'], q['M'], q['N'], q['K'], 1 if q['overwrite'] else 0
+        rows.append((L.ptr(q['dc']), q['ldc'], L.ptr(q['a']), q['lda'], L.ptr(q['dw']), L.ptr(q['dbias']), q['M'], q['N'], q['K'],
+                     1 if q['overwrite'] else 0, L.ptr(q['g']), L.ptr(q['b']), L.ptr(q['mean']), L.ptr(q['rstd'])))
         need += L.lib().wmz_linear_wgrad_workspace_floats(q['M'], q['N'], q['K'], dt)
     dev = problems[0]['dc'].device
     ws = _workspace(dev, need) if side is None else _side_workspace(side, dev, need)
-    L.call('wmz_linear_wgrad_batch_ln', n, pc, lc, pa, la, pw, pb, Ms, Ns, Ks, ov, pg, pbe, pm, pr, L.ptr(ws), ws.numel(), dt,
-           L.stream())
+    L.call('wmz_linear_wgrad_batch_ln', len(problems), *L.columns(rows, 'plplppiiiipppp'), L.ptr(ws), ws.numel(), dt, L.stream())
 
 
 def _issue_pending_conv():
@@ -457,23 +450,15 @@ def _issue_pending_conv():
     global _pending_conv
     if not _pending_conv:
         return
-    import ctypes
     batch, _pending_conv = _pending_conv[:WGRAD_BATCH], _pending_conv[WGRAD_BATCH:]
     n = len(batch)
-    vp, ci = ctypes.c_void_p * n, ctypes.c_int * n
-    px, pdy, pw, pb = vp(), vp(), vp(), vp()
-    cols = [ci() for _ in range(12)]
-    need = 0
-    for i, q in enumerate(batch):
-        px[i], pdy[i], pw[i], pb[i] = L.ptr(q['x']), L.ptr(q['dy']), L.ptr(q['gw']), L.ptr(q['gb'])
-        for c, v in zip(cols, q['geom']):
-            c[i] = v
-        need += q['need']
+    cols = L.columns([(L.ptr(q['x']), L.ptr(q['dy']), L.ptr(q['gw']), L.ptr(q['gb']), *q['geom']) for q in batch], 'pppp' + 'i' * 12)
+    need = sum(q['need'] for q in batch)
     ent = batch[0]['ent']
     ent[0].wait_event(batch[-1]['fork'])
     with torch.cuda.stream(ent[0]):
         ws = _side_workspace(ent, batch[0]['x'].device, need)
-        L.call('wmz_conv2d_nhwc_wgrad_batch', n, px, pdy, pw, pb, *cols, L.ptr(ws), ws.numel(), batch[0]['dt'], L.stream())
+        L.call('wmz_conv2d_nhwc_wgrad_batch', n, *cols, L.ptr(ws), ws.numel(), batch[0]['dt'], L.stream())
     if _pending_conv:
         _issue_pending_conv()
 
@@ -675,13 +660,9 @@ def linear_wgrad_batch(problems, side=None):
     overwrite[, a_tiled]) tuples with the meaning of linear_wgrad's arguments; a_tiled: `a` is the fused path's tiled stream
     ([M, 256] bf16 in 32-row tiles) instead of row-major.  (Stays on the compute stream: at config 4 these launches fill the
     chip, a side branch measured 1.91 vs 1.90 ms per step.)"""
-    import ctypes
-    n = len(problems)
     dt = L.dtype_code(problems[0][0].dtype)
-    vp, ci, cl = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_long * n
-    pc, pa, pw, pb, lc, la, Ms, Ns, Ks, ov, tl = vp(), vp(), vp(), vp(), cl(), cl(), ci(), ci(), ci(), ci(), ci()
-    keep, need = [], 0
-    for i, prob in enumerate(problems):
+    rows, keep, need = [], [], 0        # rows: one problem's per-problem arguments, in the entry point's order
+    for prob in problems:
         dc, a, dw, dbias, overwrite = prob[:5]
         tiled = len(prob) > 5 and bool(prob[5])
         dc, M, ldc = _rows(dc)
@@ -694,12 +675,11 @@ def linear_wgrad_batch(problems, side=None):
         assert dw.dtype == torch.float32 and dw.is_contiguous()
         N, K = dw.shape
         keep.append((dc, a))
-        pc[i], pa[i], pw[i], pb[i] = L.ptr(dc), L.ptr(a), L.ptr(dw), L.ptr(dbias)
-        lc[i], la[i], Ms[i], Ns[i], Ks[i], ov[i], tl[i] = ldc, lda, M, N, K, 1 if overwrite else 0, 1 if tiled else 0
+        rows.append((L.ptr(dc), ldc, L.ptr(a), lda, L.ptr(dw), L.ptr(dbias), M, N, K, 1 if overwrite else 0, 1 if tiled else 0))
         need += L.lib().wmz_linear_wgrad_workspace_floats(M, N, K, dt)
     dev = problems[0][0].device
     ws = _workspace(dev, need) if side is None else _side_workspace(side, dev, need)
-    L.call('wmz_linear_wgrad_batch', n, pc, lc, pa, la, pw, pb, Ms, Ns, Ks, ov, tl, L.ptr(ws), ws.numel(), dt, L.stream())
+    L.call('wmz_linear_wgrad_batch', len(problems), *L.columns(rows, 'plplppiiiii'), L.ptr(ws), ws.numel(), dt, L.stream())
 
 
 def layernorm_stats(x, eps=1e-5):
