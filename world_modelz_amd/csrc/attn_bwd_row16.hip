@@ -42,22 +42,6 @@ template <int DH, int KC_ = 8> struct BImg {
   static_assert(IMG % 1024 == 0, "image must be whole 1 KB DMA pieces");
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// byte offset (relative to plane row `base`) of the 16 bytes this lane fetches for DMA piece `piece`: slab row r = 16 t + w
-// is plane row base + 2 t, column w; pad chunks fetch chunk 0; rows past the plane are redirected to row_lim (never read)
-template <int DH>
-__device__ __forceinline__ unsigned bpiece_voff(int piece, int lane, unsigned ld_bytes, int row_lim) {
-  constexpr int ROWP = DH * 2 + 32;
-  const int off = piece * 1024 + lane * 16;
-  const int r = off / ROWP;
-  int c = (off - r * ROWP) >> 4;
-  c = c < DH / 8 ? c : 0;
-  const int prow = min(2 * (r >> 4), row_lim);
-  return (unsigned)((prow << 4) + (r & 15)) * ld_bytes + (unsigned)c * 16u;
-}
-
 // Epilogue store of an owner row's accumulators acc[mt][r] = G^T[feature 16 mt + 4 g + r][owner li] (times mul) as bf16: lanes
 // g and g ^ 1 exchange halves (v_permlane16_swap) so that every lane stores 16 contiguous bytes -- per wave instruction 64
 // contiguous bytes per owner row instead of 32, half as many stores (the forward kernel's epilogue, attn_fwd_row16.hip).
@@ -144,7 +128,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
     }
   };
 
-  // ---- slab geometry (as in attn_fwd_row16.hip)
+  // ---- slab geometry and walk (as in attn_fwd_row16.hip; stated once and pinned on the host: attn_slab_walk.h)
   const int my_lo = max(h - eHv, 0), my_hi = min(h + eHv, H - 1);
   const int t_lo = max(h0 - eHv, 0), t_hi = min(min(h0 + NW - 1, H - 1) + eHv, H - 1);
   const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
@@ -156,8 +140,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
   if constexpr (ALIGNED) {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      vo1[i] = bpiece_voff<DH>(wave + NW * i, lane, ld1_b, CH - 2);
-      vo2[i] = bpiece_voff<DH>(wave + NW * i, lane, ld2_b, CH - 2);
+      vo1[i] = piece_voff<DH, BImg<DH>::ROWP, 2>(wave + NW * i, lane, ld1_b, CH - 2);
+      vo2[i] = piece_voff<DH, BImg<DH>::ROWP, 2>(wave + NW * i, lane, ld2_b, CH - 2);
     }
   }
   const unsigned rs1 = 16u * ld1_b, rs2 = 16u * ld2_b;
@@ -199,7 +183,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
       if (i * NW + NW <= I::PIECES || piece < I::PIECES) {
         unsigned a, c;
         if constexpr (ALIGNED) { a = vo1[i]; c = vo2[i]; }
-        else { a = bpiece_voff<DH>(piece, lane, ld1_b, dlim); c = bpiece_voff<DH>(piece, lane, ld2_b, dlim); }
+        else { a = piece_voff<DH, BImg<DH>::ROWP, 2>(piece, lane, ld1_b, dlim); c = piece_voff<DH, BImg<DH>::ROWP, 2>(piece, lane, ld2_b, dlim); }
         __builtin_amdgcn_global_load_lds((gptr_t)(y1p + a), (lptr_t)(dbuf + piece * 1024), 16, 0, 0);
         __builtin_amdgcn_global_load_lds((gptr_t)(y2p + c), (lptr_t)(dbuf + I::IMG + piece * 1024), 16, 0, 0);
       }
@@ -500,7 +484,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_kvplane_kernel(RBwdPtrs P, Attn
   const int h = h0 + wave;                               // H % 16 == 0: every wave owns a key row
   const long NH = (long)G.B * G.S * HW * G.heads;
 
-  // ---- slab geometry (as above)
+  // ---- slab geometry and walk (as above, without the clamps: attn_slab_walk.h, CLAMP = false)
   const int my_lo = max(h - G.eH, 0), my_hi = min(h + G.eH, H - 1);
   const int t_lo = max(h0 - G.eH, 0), t_hi = min(h0 + NW - 1 + G.eH, H - 1);
   const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
@@ -570,7 +554,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_kvplane_kernel(RBwdPtrs P, Attn
 #pragma unroll
     for (int i = 0; i < NP; ++i)
       *reinterpret_cast<unsigned*>(smem + TAB + (wave * NP + i) * 256 + lane * 4) =
-          SAME_LD ? bpiece_voff<DH>(wave + NW * i, lane, ld1_b, 14) : bpiece_voff<DH>(wave + NW * i, lane, 256u, 14);
+          SAME_LD ? piece_voff<DH, BImg<DH>::ROWP, 2>(wave + NW * i, lane, ld1_b, 14) : piece_voff<DH, BImg<DH>::ROWP, 2>(wave + NW * i, lane, 256u, 14);
   }
   next_state();
   if (nslab > 0) issue();

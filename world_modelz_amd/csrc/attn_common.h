@@ -6,8 +6,14 @@
 // Window membership of (query, key) is decided from packed (h<<16 | w) coordinates with packed-u16 math.
 #pragma once
 #include "wmz_common.h"
+#include "attn_slab_walk.h"
 
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+
+namespace {       // address-space pointer types of the LDS-DMA builtin (attn_fwd_row16.hip, attn_bwd_row16.hip)
+typedef const __attribute__((address_space(1))) void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+}  // namespace
 
 struct AttnGeom {
   int B, S, H, W, heads, dh;

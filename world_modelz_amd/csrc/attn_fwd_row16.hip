@@ -88,23 +88,6 @@ constexpr int kSched[8][6] = {
     {0, 0, 1, 1, 3, 3},   // 7
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// Byte offset (inside a key plane, relative to plane row `base`) of the 16 bytes this lane fetches for DMA piece `piece` of
-// a padded image: the lane landing on (slab row, 16-byte chunk) fetches that chunk of plane row base + 2 * (slab row / 16),
-// key column slab row % 16; pad chunks fetch chunk 0 (never read).  `row_lim`: rows past the plane are redirected to the
-// last valid one (never read either).
-template <int DH, int ROWP, int RS>
-__device__ __forceinline__ unsigned piece_voff(int piece, int lane, unsigned ld_bytes, int row_lim) {
-  const int off = piece * 1024 + lane * 16;
-  const int r = off / ROWP;
-  int c = (off - r * ROWP) >> 4;
-  c = c < DH / 8 ? c : 0;
-  const int prow = min(RS * (r >> 4), row_lim);
-  return (unsigned)((prow << 4) + (r & 15)) * ld_bytes + (unsigned)c * 16u;
-}
-
 // W8: planes 8 wide.  A plane [H, 8] (H even) IS a plane [H / 2, 16] in memory: tile row R = plane rows 2R, 2R + 1, tile column
 // c = 8 (row & 1) + w.  Staging, fragments, Q / O rows are those of a 16-wide plane with H / 2 rows (G.H holds H / 2); what changes
 // is the window: key tile row R + D is visited for |D| <= eHv = ceil(eH / 2), the column mask compares c & 7, and in the two
@@ -169,7 +152,8 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
   const int kbase = li * I::KROW + g * 16;
   const int vbase = I::KIMG + (4 * g + (li >> 2)) * I::VROW + (li & 3) * 8;
   const int my_lo = max(hq - eHv, 0), my_hi = min(hq + eHv, H - 1);
-  // key rows the workgroup stages
+  // key rows the workgroup stages (this geometry, the plane order and next_state() / advance() below: attn_slab_walk.h states them
+  // once and tests/test_attn_slab_walk_cpu.py pins them -- keep the two in step)
   const int t_lo = max(h0 - eHv, 0), t_hi = min(min(h0 + NW - 1, H - 1) + eHv, H - 1);
   const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
   const int c_first = t_lo >> LOG_CH, c_last = t_hi >> LOG_CH;

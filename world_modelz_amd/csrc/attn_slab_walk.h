@@ -1,0 +1,94 @@
+// The slab walk of the attention row kernels (attn_fwd_row16.hip and both kernels of attn_bwd_row16.hip), stated once: which key /
+// visitor rows a workgroup stages, in which order, and which bytes a lane's LDS-DMA pieces fetch.  Plain integer code without HIP
+// and without pointers (a caller keeps its own and moves them by the walker's plane deltas): tests/attn_slab_walk_host.cpp runs it on
+// the host and tests/test_attn_slab_walk_cpu.py says what it promises.  The kernels take piece_voff from here; the geometry and the
+// walker they still write out by hand, expression for expression as below (with the walker in their place every row kernel compiled
+// to other scalar code: profiles/attn_slab_walk/README.md) -- a change to the walk is made here first, under the test, then there.
+#pragma once
+#ifdef __HIPCC__
+#define WMZ_HD __host__ __device__ __forceinline__
+#else
+#define WMZ_HD inline
+#endif
+
+WMZ_HD int slab_min(int a, int b) { return a < b ? a : b; }
+WMZ_HD int slab_max(int a, int b) { return a > b ? a : b; }
+constexpr int slab_log2(int n) { return n <= 1 ? 0 : 1 + slab_log2(n >> 1); }
+
+// What a workgroup (NW owner rows from h0, query / owner plane s) stages: rows [t_lo, t_hi] of the planes [sk_lo, sk_hi], i.e.
+// nch slabs per plane from chunk c_first on, nslab in all.
+struct SlabGeom { int H, s_last, t_lo, t_hi, sk_lo, sk_hi, c_first, nch, nslab; };      // (s_last = S - 1)
+
+// Key planes are walked in a ROTATED order: at its t-th plane every workgroup reads the plane p = t (mod 2 eS + 1) of its
+// window, so the 2 eS + 1 workgroups that need plane p (query planes p - eS .. p + eS, one per CU of the same XCD, started
+// together and in step) stage it at the same time: one of them misses in L2, the others hit.  Walking s - eS .. s + eS in
+// order instead, a plane is read at 2 eS + 1 different times and has left the 4 MiB L2 (the clip's K / V alone fill it) in
+// between.  The softmax is order-independent (online), the logits probe records the plane it actually visits.
+// (The phase counts planes from the END of the clip: the trailing-planes entry point hands over only the last planes of a
+// clip, and its visiting order -- hence every rounding -- must be the full grid's.)
+WMZ_HD int slab_first_plane(const SlabGeom& g, int eS, int s) {
+  const int nwin = 2 * eS + 1;
+  int p_first = s - eS;
+  { const int a = (((g.s_last - p_first) % nwin) + nwin) % nwin; p_first += a; }         // first plane of the window with S-1-p = 0 (mod nwin)
+  if (p_first > g.sk_hi || p_first < g.sk_lo) p_first = g.sk_lo;
+  return p_first;
+}
+
+// A plane is cut into chunks of CH rows, a slab holds every RS-th row of a chunk (KC = CH / RS rows: plane row = base + RS * slab
+// row).  eHv: the window's row extent in tile rows.  CLAMP = false is the whole-plane form (H % CH == 0 and NW == CH: no owner row
+// and no slab row lies past the plane), which carries none of the clamps.  (The inner min of t_hi changes no value -- both forms
+// give min(h0 + NW - 1 + eHv, H - 1) -- and dlim stays CH - RS without CLAMP: they are the kernels' own expressions, kept so that
+// this code and theirs can be held side by side.)
+template <int CH, int KC, bool CLAMP = true>
+WMZ_HD SlabGeom slab_geom(int H, int S, int eS, int eHv, int h0, int NW, int s) {
+  constexpr int RS = CH / KC, LOG_CH = slab_log2(CH);
+  static_assert(KC * RS == CH && (1 << LOG_CH) == CH && (1 << slab_log2(RS)) == RS, "a slab is one phase of a chunk of 2^n rows");
+  SlabGeom g;
+  g.H = H;
+  g.t_lo = slab_max(h0 - eHv, 0);
+  g.t_hi = slab_min((CLAMP ? slab_min(h0 + NW - 1, H - 1) : h0 + NW - 1) + eHv, H - 1);
+  g.sk_lo = slab_max(0, s - eS); g.s_last = S - 1; g.sk_hi = slab_min(g.s_last, s + eS);
+  g.c_first = g.t_lo >> LOG_CH;
+  g.nch = ((g.t_hi >> LOG_CH) - g.c_first + 1) * RS;        // slabs per plane: (chunk) x (row phase)
+  g.nslab = (g.sk_hi - g.sk_lo + 1) * g.nch;
+  return g;
+}
+
+// The slab being prefetched: plane (from sk_lo), slab in the plane, first row, index; and where its DMA may read: bsafe, the
+// row the fetch starts from, and dlim, the last row offset piece_voff may add to it.
+template <int CH, int KC, bool CLAMP = true> struct SlabWalk {
+  static constexpr int RS = CH / KC, LOG_RS = slab_log2(RS), LOG_CH = slab_log2(CH);
+  int pl, rem = 0, base = 0, j = 0, bsafe = 0, dlim = CH - RS;
+  WMZ_HD SlabWalk(const SlabGeom& g, int p_first) : pl(p_first - g.sk_lo) {}
+  WMZ_HD void next_state(const SlabGeom& g) {                                // descriptors of slab (pl, rem)
+    base = ((g.c_first + (rem >> LOG_RS)) << LOG_CH) + (rem & (RS - 1));
+    // (a one-row plane has no row of phase 1: that slab -- which no wave reads -- is fetched from the last row instead of from
+    //  behind the plane; found by tools/guard_overread.py: a read past the end of the K / V tensor for H = 1)
+    bsafe = CLAMP ? slab_min(base, g.H - 1) : base;
+    if (CLAMP) dlim = slab_max(g.H - 1 - base, 0);
+  }
+  // step (pl, rem) to the following slab; move_planes(d) moves the caller's plane pointers by d planes: +1, or back to the
+  // window's first plane behind its last
+  template <typename Move> WMZ_HD void advance(const SlabGeom& g, Move move_planes) {
+    ++j;
+    if (++rem == g.nch) {
+      rem = 0;
+      if (g.sk_lo + pl == g.sk_hi) { move_planes(-(long)pl); pl = 0; }
+      else { ++pl; move_planes(1); }
+    }
+  }
+};
+
+// Byte offset (inside a plane, relative to plane row `base`) of the 16 bytes this lane fetches for DMA piece `piece` of a padded
+// image (rows of ROWP bytes): the lane landing on (slab row, 16-byte chunk) fetches that chunk of plane row base + RS * (slab row
+// / 16), column slab row % 16; pad chunks fetch chunk 0 (never read).  `row_lim`: rows past the plane are redirected to the last
+// valid one (never read either).
+template <int DH, int ROWP, int RS>
+WMZ_HD unsigned piece_voff(int piece, int lane, unsigned ld_bytes, int row_lim) {
+  const int off = piece * 1024 + lane * 16;
+  const int r = off / ROWP;
+  int c = (off - r * ROWP) >> 4;
+  c = c < DH / 8 ? c : 0;
+  const int prow = slab_min(RS * (r >> 4), row_lim);
+  return (unsigned)((prow << 4) + (r & 15)) * ld_bytes + (unsigned)c * 16u;
+}
