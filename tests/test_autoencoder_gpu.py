@@ -461,11 +461,12 @@ def test_small_k_conv_equals_the_implicit_gemm_kernel(wmz, geom):
 
 
 @pytest.mark.parametrize('C,dtype', [(128, torch.bfloat16), (128, torch.float32), (16, torch.bfloat16), (24, torch.bfloat16),
-                                     (512, torch.float32), (2048, torch.bfloat16)])
+                                     (512, torch.float32), (2048, torch.bfloat16), (24, torch.float32)])
 def test_training_elementwise_kernels_vector_and_scalar_forms(wmz, C, dtype):
-    """BatchNorm(+LeakyReLU) backward (reduce + apply), channel statistics and bilinear x2 forward / adjoint against fp32 torch
-    formulas on the same (rounded) inputs.  C = 24 is not a vector-form shape (its 3 channel groups do not divide the workgroup):
-    the scalar kernels; the others run the 16-byte kernels, C = 2048 with several channels per reducing thread."""
+    """BatchNorm(+LeakyReLU) backward (reduce + apply), channel statistics, the two-operand affine + LeakyReLU and bilinear x2 forward /
+    adjoint against fp32 torch formulas on the same (rounded) inputs.  C = 24 is not a vector-form shape (its 3 / 6 channel groups do
+    not divide the workgroup): the scalar kernels; the others run the 16-byte kernels, C = 2048 with several channels per reducing
+    thread."""
     from world_modelz_amd import ops
     torch.manual_seed(13)
     B, H, W = 2, 5, 7
@@ -514,6 +515,10 @@ def test_training_elementwise_kernels_vector_and_scalar_forms(wmz, C, dtype):
             assert rel(dx2.reshape(M2, C), xin.grad) < tol
             assert rel(dgamma2, gin.grad) < (1e-4 if dtype == torch.float32 else 2e-3)
             assert rel(dbeta2, bin_.grad) < (1e-4 if dtype == torch.float32 else 2e-3)
+    # y = LeakyReLU(x sa + ta + (dy sb + tb)): one rounding of the fp32 result
+    sa, ta, sb, tb = (torch.randn(C, device='cuda') for _ in range(4))
+    aff = ops.affine_act_nhwc(x, sa, ta, dy, sb, tb, leaky=True, slope=0.01)
+    assert aff.dtype == dtype and rel(aff, torch.nn.functional.leaky_relu(xf * sa + ta + (dyf * sb + tb), 0.01)) < tol
     # bilinear x2 and its adjoint
     up = ops.bilinear2x_nhwc(x)
     up_ref = torch.nn.functional.interpolate(xf.permute(0, 3, 1, 2), scale_factor=2, mode='bilinear', align_corners=False)

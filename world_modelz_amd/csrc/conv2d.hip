@@ -31,52 +31,6 @@ struct ConvParams {
   const float* in_scale; const float* in_shift; float in_slope;
 };
 
-__device__ __forceinline__ int swz128(int r) { return ((r >> 1) << 4) & 112; }
-
-template <typename T> __device__ __forceinline__ void chunk_to_f32(const i32x4& c, float* f);
-template <> __device__ __forceinline__ void chunk_to_f32<float>(const i32x4& c, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) f[i] = __int_as_float(c[i]);
-}
-template <> __device__ __forceinline__ void chunk_to_f32<bf16_t>(const i32x4& c, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(((unsigned)c[i]) << 16);
-    f[2 * i + 1] = __uint_as_float(((unsigned)c[i]) & 0xFFFF0000u);
-  }
-}
-// IEEE half by name (the precise mode's inference route: channel_stats / affine_act / bilinear2x take WMZ_F16); this unit's
-// bfloat16 forms stay on the unit's primitives
-template <> __device__ __forceinline__ void chunk_to_f32<_Float16>(const i32x4& c, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    // (through a scalar copy: a bit_cast straight from the vector element c[i] read element 0 for every i)
-    const unsigned w = (unsigned)c[i];
-    const f32x2 v = __builtin_convertvector(__builtin_bit_cast(f16x2_t, w), f32x2);
-    f[2 * i] = v[0];
-    f[2 * i + 1] = v[1];
-  }
-}
-template <typename T> __device__ __forceinline__ i32x4 f32_to_chunk(const float* f);
-template <> __device__ __forceinline__ i32x4 f32_to_chunk<float>(const float* f) {
-  i32x4 c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = __float_as_int(f[i]);
-  return c;
-}
-template <> __device__ __forceinline__ i32x4 f32_to_chunk<bf16_t>(const float* f) {
-  i32x4 c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = (int)((unsigned)f32_to_bf16_bits(f[2 * i]) | ((unsigned)f32_to_bf16_bits(f[2 * i + 1]) << 16));
-  return c;
-}
-template <> __device__ __forceinline__ i32x4 f32_to_chunk<_Float16>(const float* f) {
-  i32x4 c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = (int)__builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){f[2 * i], f[2 * i + 1]}, f16x2_t));
-  return c;
-}
-
 // TALL = false: output tile 128 x 128, the four waves as 2 x 2.  TALL = true (Cout <= 64: conv_1, the 1x1 and the 2x2
 // down-sampling convolutions): output tile 256 x 64, the waves stacked -- no MFMA or weight-slab traffic spent on columns
 // that do not exist, and twice the rows per workgroup behind each (short: K = 72 .. 256) reduction and epilogue.
@@ -118,13 +72,13 @@ __global__ __launch_bounds__(NT, 2) void conv2d_kernel(ConvParams P) {
   i32x4 ra[AI], rb[BI];
   auto pre = [&](i32x4 v, int k) {          // k = first input channel of the chunk (1x1 conv: k IS the channel)
     float f[EPC];
-    chunk_to_f32<T>(v, f);
+    Elem<T>::unpack(v, f);
 #pragma unroll
     for (int e = 0; e < EPC; ++e) {
       const float y = fmaf(f[e], P.in_scale[k + e], P.in_shift[k + e]);
       f[e] = y > 0.f ? y : y * P.in_slope;
     }
-    return f32_to_chunk<T>(f);
+    return Elem<T>::pack(f);
   };
   auto fetch = [&](int k0) {
     const int k = k0 + cc * EPC;
@@ -251,7 +205,7 @@ __global__ __launch_bounds__(NT, 2) void conv2d_kernel(ConvParams P) {
             float f[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
             if (R) {
               float r8[8];
-              chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(R + (long)row * P.Cout + col), r8);
+              Elem<T>::unpack(*reinterpret_cast<const i32x4*>(R + (long)row * P.Cout + col), r8);
 #pragma unroll
               for (int e = 0; e < 8; ++e) f[e] += r8[e];
             }
@@ -259,11 +213,11 @@ __global__ __launch_bounds__(NT, 2) void conv2d_kernel(ConvParams P) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) f[e] = f[e] > 0.f ? f[e] : f[e] * P.slope;
             }
-            const i32x4 pk = f32_to_chunk<T>(f);
+            const i32x4 pk = Elem<T>::pack(f);
             *reinterpret_cast<i32x4*>(O + (long)row * P.Cout + col) = pk;
             if (P.stat_sum != nullptr) {
               float q[8];
-              chunk_to_f32<T>(pk, q);                                 // statistics of what the next stage will read
+              Elem<T>::unpack(pk, q);                                 // statistics of what the next stage will read
 #pragma unroll
               for (int e = 0; e < 8; ++e) { s1[e] += q[e]; s2[e] += q[e] * q[e]; }
             }
@@ -472,12 +426,12 @@ __global__ __launch_bounds__(256) void affine_act_vec_kernel(const T* __restrict
   typename EwGuard<T>::type hg;
   auto finish = [&](const i32x4& va, const i32x4& vb, long at) {
     float f[VW];
-    chunk_to_f32<T>(va, f);
+    Elem<T>::unpack(va, f);
 #pragma unroll
     for (int e = 0; e < VW; ++e) f[e] = fmaf(f[e], s1[e], t1[e]);
     if (b) {
       float u[VW];
-      chunk_to_f32<T>(vb, u);
+      Elem<T>::unpack(vb, u);
 #pragma unroll
       for (int e = 0; e < VW; ++e) f[e] += fmaf(u[e], s2[e], t2[e]);
     }
@@ -485,7 +439,7 @@ __global__ __launch_bounds__(256) void affine_act_vec_kernel(const T* __restrict
 #pragma unroll
       for (int e = 0; e < VW; ++e) f[e] = f[e] > 0.f ? f[e] : f[e] * slope;
     }
-    const i32x4 out = f32_to_chunk<T>(f);
+    const i32x4 out = Elem<T>::pack(f);
     if (hg.on()) hg.see(out);
     *reinterpret_cast<i32x4*>(y + at * VW) = out;
   };
@@ -671,8 +625,8 @@ __global__ __launch_bounds__(RED_NT) void bn_act_bwd_reduce_vec_kernel(const T* 
     tab_row<VW>(ew_tab, C, 2, c0, ms); tab_row<VW>(ew_tab, C, 3, c0, mt);
     auto take = [&](const i32x4& vg, const i32x4& vx) {
       float g[VW], xv[VW];
-      chunk_to_f32<T>(vg, g);
-      chunk_to_f32<T>(vx, xv);
+      Elem<T>::unpack(vg, g);
+      Elem<T>::unpack(vx, xv);
 #pragma unroll
       for (int e = 0; e < VW; ++e) {
         if (fmaf(xv[e], ms[e], mt[e]) <= 0.f) g[e] *= slope;
@@ -694,23 +648,23 @@ __global__ __launch_bounds__(RED_NT) void bn_act_bwd_reduce_vec_kernel(const T* 
   } else {
     auto take = [&](const i32x4& vg, const i32x4& vy, const i32x4& vx, long at) {
       float g[VW];
-      chunk_to_f32<T>(vg, g);
+      Elem<T>::unpack(vg, g);
       if (leaky) {
         float yv[VW];
-        chunk_to_f32<T>(vy, yv);
+        Elem<T>::unpack(vy, yv);
 #pragma unroll
         for (int e = 0; e < VW; ++e) g[e] = yv[e] <= 0.f ? g[e] * slope : g[e];
       }
       if (g_out) {
-        const i32x4 gv = f32_to_chunk<T>(g);
+        const i32x4 gv = Elem<T>::pack(g);
         *reinterpret_cast<i32x4*>(g_out + at * VW) = gv;
-        chunk_to_f32<T>(gv, g);                           // the sums see what was stored (as the scalar kernel's do)
+        Elem<T>::unpack(gv, g);                           // the sums see what was stored (as the scalar kernel's do)
       }
 #pragma unroll
       for (int e = 0; e < VW; ++e) s1[e] += g[e];
       if (x) {
         float xv[VW];
-        chunk_to_f32<T>(vx, xv);
+        Elem<T>::unpack(vx, xv);
 #pragma unroll
         for (int e = 0; e < VW; ++e) s2[e] += g[e] * (xv[e] - mu[e]) * rs[e];
       }
@@ -772,8 +726,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const T* __restri
   tab_row<VW>(ew_tab, C, 3, c0, q); tab_row<VW>(ew_tab, C, 4, c0, ms); tab_row<VW>(ew_tab, C, 5, c0, mt);
   auto finish = [&](const i32x4& vx, const i32x4& vg, const i32x4& va, long at) {
     float xv[VW], gv[VW];
-    chunk_to_f32<T>(vx, xv);
-    chunk_to_f32<T>(vg, gv);
+    Elem<T>::unpack(vx, xv);
+    Elem<T>::unpack(vg, gv);
 #pragma unroll
     for (int e = 0; e < VW; ++e) {
       if (fmaf(xv[e], ms[e], mt[e]) <= 0.f) gv[e] *= slope;
@@ -781,11 +735,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const T* __restri
     }
     if (add) {
       float av[VW];
-      chunk_to_f32<T>(va, av);
+      Elem<T>::unpack(va, av);
 #pragma unroll
       for (int e = 0; e < VW; ++e) gv[e] += av[e];
     }
-    *reinterpret_cast<i32x4*>(dx + at * VW) = f32_to_chunk<T>(gv);
+    *reinterpret_cast<i32x4*>(dx + at * VW) = Elem<T>::pack(gv);
   };
   for (; i + stride < nvec; i += 2 * stride) {
     i32x4 x0 = ld16(x, i), x1 = ld16(x, i + stride), g0 = ld16(g, i), g1 = ld16(g, i + stride);
@@ -813,7 +767,7 @@ __global__ __launch_bounds__(RED_NT) void channel_stats_vec_kernel(const T* __re
   for (int e = 0; e < VW; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
   auto take = [&](const i32x4& vx) {
     float v[VW];
-    chunk_to_f32<T>(vx, v);
+    Elem<T>::unpack(vx, v);
 #pragma unroll
     for (int e = 0; e < VW; ++e) { s1[e] += v[e]; s2[e] = fmaf(v[e], v[e], s2[e]); }
   };
@@ -856,16 +810,16 @@ __global__ __launch_bounds__(256) void bilinear2x_vec_kernel(const T* __restrict
     const float lh = sh - h0, lw = sw - w0;
     const T* p = x + (long)b * H * W * C + c;
     float v00[VW], v01[VW], v10[VW], v11[VW], o[VW];
-    chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(p + ((long)h0 * W + w0) * C), v00);
-    chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(p + ((long)h0 * W + w1) * C), v01);
-    chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(p + ((long)h1 * W + w0) * C), v10);
-    chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(p + ((long)h1 * W + w1) * C), v11);
+    Elem<T>::unpack(*reinterpret_cast<const i32x4*>(p + ((long)h0 * W + w0) * C), v00);
+    Elem<T>::unpack(*reinterpret_cast<const i32x4*>(p + ((long)h0 * W + w1) * C), v01);
+    Elem<T>::unpack(*reinterpret_cast<const i32x4*>(p + ((long)h1 * W + w0) * C), v10);
+    Elem<T>::unpack(*reinterpret_cast<const i32x4*>(p + ((long)h1 * W + w1) * C), v11);
 #pragma unroll
     for (int e = 0; e < VW; ++e) {
       const float top = (1.f - lw) * v00[e] + lw * v01[e], bot = (1.f - lw) * v10[e] + lw * v11[e];
       o[e] = (1.f - lh) * top + lh * bot;
     }
-    *reinterpret_cast<i32x4*>(y + i * VW) = f32_to_chunk<T>(o);
+    *reinterpret_cast<i32x4*>(y + i * VW) = Elem<T>::pack(o);
   }
 }
 
@@ -897,13 +851,13 @@ __global__ __launch_bounds__(256) void bilinear2x_bwd_vec_kernel(const T* __rest
         const float ww = (w0 == w ? 1.f - lw : 0.f) + (w1 == w ? lw : 0.f);
         if (ww != 0.f) {
           float v[VW];
-          chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(dy + (((long)b * Ho + ho) * Wo + wo) * C + c), v);
+          Elem<T>::unpack(*reinterpret_cast<const i32x4*>(dy + (((long)b * Ho + ho) * Wo + wo) * C + c), v);
 #pragma unroll
           for (int e = 0; e < VW; ++e) acc[e] += wh * ww * v[e];
         }
       }
     }
-    *reinterpret_cast<i32x4*>(dx + i * VW) = f32_to_chunk<T>(acc);
+    *reinterpret_cast<i32x4*>(dx + i * VW) = Elem<T>::pack(acc);
   }
 }
 
@@ -956,13 +910,10 @@ extern "C" int wmz_conv2d_nhwc_fwd_pre(const void* x, const void* w, void* out, 
   P.in_scale = in_scale; P.in_shift = in_shift; P.in_slope = in_slope;
   dim3 grid((unsigned)(wmz_cdiv(P.M, BMl) * P.nbn)), block(NT);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16) {
-    if (tall) hipLaunchKernelGGL((conv2d_kernel<bf16_t, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((conv2d_kernel<bf16_t, false>), grid, block, 0, st, P);
-  } else {
-    if (tall) hipLaunchKernelGGL((conv2d_kernel<float, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((conv2d_kernel<float, false>), grid, block, 0, st, P);
-  }
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    if (tall) hipLaunchKernelGGL((conv2d_kernel<T, true>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((conv2d_kernel<T, false>), grid, block, 0, st, P);
+  });
   WMZ_LAUNCH_CHECK("wmz_conv2d_nhwc_fwd_pre");
   return WMZ_OK;
 }
@@ -974,17 +925,17 @@ extern "C" int wmz_channel_stats_nhwc(const void* x, long M, int C, float* sum, 
     const int VW = dtype == WMZ_F32 ? 4 : 8;
     const long nvec = M * C / VW;
     const int gridv = grid_for(nvec, RED_NT * 4, 256);
-    if (dtype == WMZ_F16) hipLaunchKernelGGL(channel_stats_vec_kernel<_Float16>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const _Float16*)x, nvec, C, sum, sq);
-    else if (dtype == WMZ_BF16) hipLaunchKernelGGL(channel_stats_vec_kernel<bf16_t>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const bf16_t*)x, nvec, C, sum, sq);
-    else hipLaunchKernelGGL(channel_stats_vec_kernel<float>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const float*)x, nvec, C, sum, sq);
+    wmz_by_dtype3(dtype, [&](auto e) { typedef decltype(e) T;
+      hipLaunchKernelGGL(channel_stats_vec_kernel<T>, dim3(gridv), dim3(RED_NT), 0, (hipStream_t)stream, (const T*)x, nvec, C, sum, sq);
+    });
     WMZ_LAUNCH_CHECK("wmz_channel_stats_nhwc");
     return WMZ_OK;
   }
   dim3 grid((unsigned)grid_for(M, 64, 512), (unsigned)wmz_cdiv(C, 64));
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_F16) hipLaunchKernelGGL(channel_stats_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16*)x, M, C, sum, sq);
-  else if (dtype == WMZ_BF16) hipLaunchKernelGGL(channel_stats_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, M, C, sum, sq);
-  else hipLaunchKernelGGL(channel_stats_kernel<float>, grid, dim3(256), 0, st, (const float*)x, M, C, sum, sq);
+  wmz_by_dtype3(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(channel_stats_kernel<T>, grid, dim3(256), 0, st, (const T*)x, M, C, sum, sq);
+  });
   WMZ_LAUNCH_CHECK("wmz_channel_stats_nhwc");
   return WMZ_OK;
 }
@@ -1022,23 +973,18 @@ extern "C" int wmz_affine_act_nhwc_bn(const void* a, const float* sa, const floa
     // every thread keeps its channel group: the grid stride (grid * 256 vectors) is a multiple of C / VW since 256 is
     const long nvec = total / VW;
     const int gridv = grid_for(nvec, 256, EW_GRID);
-    if (dtype == WMZ_F16)
-      hipLaunchKernelGGL(affine_act_vec_kernel<_Float16>, dim3(gridv), dim3(256), (size_t)4 * C * sizeof(float), st, (const _Float16*)a, sa, ta, (const _Float16*)b, sb, tb, (_Float16*)y, nvec, C, leaky, slope, bn_stats_from(bna), bn_stats_from(bnb));
-    else if (dtype == WMZ_BF16)
-      hipLaunchKernelGGL(affine_act_vec_kernel<bf16_t>, dim3(gridv), dim3(256), (size_t)4 * C * sizeof(float), st, (const bf16_t*)a, sa, ta, (const bf16_t*)b, sb, tb, (bf16_t*)y, nvec, C, leaky, slope, bn_stats_from(bna), bn_stats_from(bnb));
-    else
-      hipLaunchKernelGGL(affine_act_vec_kernel<float>, dim3(gridv), dim3(256), (size_t)4 * C * sizeof(float), st, (const float*)a, sa, ta, (const float*)b, sb, tb, (float*)y, nvec, C, leaky, slope, bn_stats_from(bna), bn_stats_from(bnb));
+    wmz_by_dtype3(dtype, [&](auto e) { typedef decltype(e) T;
+      hipLaunchKernelGGL(affine_act_vec_kernel<T>, dim3(gridv), dim3(256), (size_t)4 * C * sizeof(float), st, (const T*)a, sa, ta, (const T*)b, sb, tb,
+                         (T*)y, nvec, C, leaky, slope, bn_stats_from(bna), bn_stats_from(bnb));
+    });
     WMZ_LAUNCH_CHECK("wmz_affine_act_nhwc");
     return WMZ_OK;
   }
   WMZ_REQUIRE(bna == nullptr && bnb == nullptr, "wmz_affine_act_nhwc_bn: raw BatchNorm statistics need the 16-byte kernel (wmz_affine_act_bn_supported, 16-byte aligned tensors)");
   const int grid = grid_for(total, 1024, 4096);
-  if (dtype == WMZ_F16)
-    hipLaunchKernelGGL(affine_act_kernel<_Float16>, dim3(grid), dim3(256), 0, st, (const _Float16*)a, sa, ta, (const _Float16*)b, sb, tb, (_Float16*)y, total, C, leaky, slope);
-  else if (dtype == WMZ_BF16)
-    hipLaunchKernelGGL(affine_act_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)a, sa, ta, (const bf16_t*)b, sb, tb, (bf16_t*)y, total, C, leaky, slope);
-  else
-    hipLaunchKernelGGL(affine_act_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)a, sa, ta, (const float*)b, sb, tb, (float*)y, total, C, leaky, slope);
+  wmz_by_dtype3(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(affine_act_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)a, sa, ta, (const T*)b, sb, tb, (T*)y, total, C, leaky, slope);
+  });
   WMZ_LAUNCH_CHECK("wmz_affine_act_nhwc");
   return WMZ_OK;
 }
@@ -1060,8 +1006,9 @@ extern "C" int wmz_dilate_nhwc(const void* dy, void* dz, int B, int Ho, int Wo, 
   const int cv = C / VW;
   dim3 grid((unsigned)wmz_cdiv(Wz * cv, 256), (unsigned)Hz, (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16) hipLaunchKernelGGL(dilate_vec_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)dz, Ho, Wo, cv, Hz, Wz, stride);
-  else hipLaunchKernelGGL(dilate_vec_kernel<float>, grid, dim3(256), 0, st, (const float*)dy, (float*)dz, Ho, Wo, cv, Hz, Wz, stride);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(dilate_vec_kernel<T>, grid, dim3(256), 0, st, (const T*)dy, (T*)dz, Ho, Wo, cv, Hz, Wz, stride);
+  });
   WMZ_LAUNCH_CHECK("wmz_dilate_nhwc");
   return WMZ_OK;
 }
@@ -1073,17 +1020,17 @@ extern "C" int wmz_bilinear2x_nhwc(const void* x, void* y, int B, int H, int W, 
   if (vec_ok(C, dtype, {x, y})) {
     const int VW = dtype == WMZ_F32 ? 4 : 8;
     const int gridv = grid_for(total / VW, 256, 8192);
-    if (dtype == WMZ_F16) hipLaunchKernelGGL(bilinear2x_vec_kernel<_Float16>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, (_Float16*)y, B, H, W, C);
-    else if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_vec_kernel<bf16_t>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
-    else hipLaunchKernelGGL(bilinear2x_vec_kernel<float>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, B, H, W, C);
+    wmz_by_dtype3(dtype, [&](auto e) { typedef decltype(e) T;
+      hipLaunchKernelGGL(bilinear2x_vec_kernel<T>, dim3(gridv), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C);
+    });
     WMZ_LAUNCH_CHECK("wmz_bilinear2x_nhwc");
     return WMZ_OK;
   }
   const int grid = grid_for(total, 256, 8192);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_F16) hipLaunchKernelGGL(bilinear2x_kernel<_Float16>, dim3(grid), dim3(256), 0, st, (const _Float16*)x, (_Float16*)y, B, H, W, C);
-  else if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
-  else hipLaunchKernelGGL(bilinear2x_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C);
+  wmz_by_dtype3(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(bilinear2x_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, (T*)y, B, H, W, C);
+  });
   WMZ_LAUNCH_CHECK("wmz_bilinear2x_nhwc");
   return WMZ_OK;
 }
@@ -1100,18 +1047,18 @@ extern "C" int wmz_bn_act_bwd_reduce(const void* x, const void* y, const void* d
     const int VW = dtype == WMZ_BF16 ? 8 : 4;
     const long nvec = M * C / VW;
     const int gridv = grid_for(nvec, RED_NT * 4, 256);                 // (a multiple of C / VW vectors per sweep: 256 is)
-    if (dtype == WMZ_BF16)
-      hipLaunchKernelGGL(bn_act_bwd_reduce_vec_kernel<bf16_t>, dim3(gridv), dim3(RED_NT), red_lds(C, 8), st, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, (bf16_t*)g_out, sum_g, sum_gx, nvec, C, leaky, slope, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL(bn_act_bwd_reduce_vec_kernel<float>, dim3(gridv), dim3(RED_NT), red_lds(C, 4), st, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, (float*)g_out, sum_g, sum_gx, nvec, C, leaky, slope, nullptr, nullptr);
+    wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+      hipLaunchKernelGGL(bn_act_bwd_reduce_vec_kernel<T>, dim3(gridv), dim3(RED_NT), red_lds(C, VW), st, (const T*)x, (const T*)y, (const T*)dy, mean, rstd,
+                         (T*)g_out, sum_g, sum_gx, nvec, C, leaky, slope, nullptr, nullptr);
+    });
     WMZ_LAUNCH_CHECK("wmz_bn_act_bwd_reduce");
     return WMZ_OK;
   }
   dim3 grid((unsigned)grid_for(M, 64, 512), (unsigned)wmz_cdiv(C, 64));
-  if (dtype == WMZ_BF16)
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, (bf16_t*)g_out, sum_g, sum_gx, M, C, leaky, slope);
-  else
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, (float*)g_out, sum_g, sum_gx, M, C, leaky, slope);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)x, (const T*)y, (const T*)dy, mean, rstd, (T*)g_out, sum_g, sum_gx,
+                       M, C, leaky, slope);
+  });
   WMZ_LAUNCH_CHECK("wmz_bn_act_bwd_reduce");
   return WMZ_OK;
 }
@@ -1126,18 +1073,17 @@ extern "C" int wmz_bn_bwd_apply_add(const void* x, const void* g, const float* m
     const int VW = dtype == WMZ_BF16 ? 8 : 4;
     const long nvec = M * C / VW;
     const int gridv = grid_for(nvec, 256, EW_GRID);
-    if (dtype == WMZ_BF16)
-      hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<bf16_t>, dim3(gridv), dim3(256), (size_t)6 * C * sizeof(float), st, (const bf16_t*)x, (const bf16_t*)g, mean, rstd, gamma, sum_g, sum_gx, (bf16_t*)dx, nvec, C, 1.f / (float)M, nullptr, nullptr, 1.f, (const bf16_t*)add);
-    else
-      hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<float>, dim3(gridv), dim3(256), (size_t)6 * C * sizeof(float), st, (const float*)x, (const float*)g, mean, rstd, gamma, sum_g, sum_gx, (float*)dx, nvec, C, 1.f / (float)M, nullptr, nullptr, 1.f, (const float*)add);
+    wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+      hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<T>, dim3(gridv), dim3(256), (size_t)6 * C * sizeof(float), st, (const T*)x, (const T*)g, mean, rstd, gamma,
+                         sum_g, sum_gx, (T*)dx, nvec, C, 1.f / (float)M, nullptr, nullptr, 1.f, (const T*)add);
+    });
     WMZ_LAUNCH_CHECK("wmz_bn_bwd_apply_add");
     return WMZ_OK;
   }
   const int grid = grid_for(M * C, 256, 4096);
-  if (dtype == WMZ_BF16)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)g, mean, rstd, gamma, sum_g, sum_gx, (bf16_t*)dx, M, C, (const bf16_t*)add);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, (const float*)g, mean, rstd, gamma, sum_g, sum_gx, (float*)dx, M, C, (const float*)add);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, (const T*)g, mean, rstd, gamma, sum_g, sum_gx, (T*)dx, M, C, (const T*)add);
+  });
   WMZ_LAUNCH_CHECK("wmz_bn_bwd_apply_add");
   return WMZ_OK;
 }
@@ -1158,13 +1104,12 @@ extern "C" int wmz_bn_leaky_bwd(const void* x, const void* dy, const float* scal
   const int VW = dtype == WMZ_BF16 ? 8 : 4;
   const long nvec = M * C / VW;
   const int gridr = grid_for(nvec, RED_NT * 4, 256), grida = grid_for(nvec, 256, EW_GRID);
-  if (dtype == WMZ_BF16) {
-    hipLaunchKernelGGL(bn_act_bwd_reduce_vec_kernel<bf16_t>, dim3(gridr), dim3(RED_NT), red_lds(C, 8), st, (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)dy, mean, rstd, (bf16_t*)nullptr, sum_g, sum_gx, nvec, C, 1, slope, scale, shift);
-    hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<bf16_t>, dim3(grida), dim3(256), (size_t)6 * C * sizeof(float), st, (const bf16_t*)x, (const bf16_t*)dy, mean, rstd, gamma, sum_g, sum_gx, (bf16_t*)dx, nvec, C, 1.f / (float)M, scale, shift, slope, (const bf16_t*)add);
-  } else {
-    hipLaunchKernelGGL(bn_act_bwd_reduce_vec_kernel<float>, dim3(gridr), dim3(RED_NT), red_lds(C, 4), st, (const float*)x, (const float*)nullptr, (const float*)dy, mean, rstd, (float*)nullptr, sum_g, sum_gx, nvec, C, 1, slope, scale, shift);
-    hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<float>, dim3(grida), dim3(256), (size_t)6 * C * sizeof(float), st, (const float*)x, (const float*)dy, mean, rstd, gamma, sum_g, sum_gx, (float*)dx, nvec, C, 1.f / (float)M, scale, shift, slope, (const float*)add);
-  }
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(bn_act_bwd_reduce_vec_kernel<T>, dim3(gridr), dim3(RED_NT), red_lds(C, VW), st, (const T*)x, (const T*)nullptr, (const T*)dy, mean, rstd,
+                       (T*)nullptr, sum_g, sum_gx, nvec, C, 1, slope, scale, shift);
+    hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<T>, dim3(grida), dim3(256), (size_t)6 * C * sizeof(float), st, (const T*)x, (const T*)dy, mean, rstd, gamma,
+                       sum_g, sum_gx, (T*)dx, nvec, C, 1.f / (float)M, scale, shift, slope, (const T*)add);
+  });
   WMZ_LAUNCH_CHECK("wmz_bn_leaky_bwd");
   return WMZ_OK;
 }
@@ -1177,14 +1122,16 @@ extern "C" int wmz_bilinear2x_nhwc_bwd(const void* dy, void* dx, int B, int H, i
   if (vec_ok(C, dtype, {dy, dx})) {
     const int VW = dtype == WMZ_BF16 ? 8 : 4;
     const int gridv = grid_for(total / VW, 256, 8192);
-    if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_bwd_vec_kernel<bf16_t>, dim3(gridv), dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C);
-    else hipLaunchKernelGGL(bilinear2x_bwd_vec_kernel<float>, dim3(gridv), dim3(256), 0, st, (const float*)dy, (float*)dx, B, H, W, C);
+    wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+      hipLaunchKernelGGL(bilinear2x_bwd_vec_kernel<T>, dim3(gridv), dim3(256), 0, st, (const T*)dy, (T*)dx, B, H, W, C);
+    });
     WMZ_LAUNCH_CHECK("wmz_bilinear2x_nhwc_bwd");
     return WMZ_OK;
   }
   const int grid = grid_for(total, 256, 8192);
-  if (dtype == WMZ_BF16) hipLaunchKernelGGL(bilinear2x_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C);
-  else hipLaunchKernelGGL(bilinear2x_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, (float*)dx, B, H, W, C);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(bilinear2x_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)dy, (T*)dx, B, H, W, C);
+  });
   WMZ_LAUNCH_CHECK("wmz_bilinear2x_nhwc_bwd");
   return WMZ_OK;
 }

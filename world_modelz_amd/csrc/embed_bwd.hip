@@ -23,15 +23,6 @@ namespace {
 constexpr int EB_D = 256;
 constexpr int EB_MAXC = CS_MAXC;
 
-__device__ __forceinline__ f32x4 bf4_to_f32(const i32x2& p) {
-  f32x4 v;
-  v[0] = __builtin_bit_cast(float, p[0] << 16);
-  v[1] = __builtin_bit_cast(float, p[0] & 0xffff0000);
-  v[2] = __builtin_bit_cast(float, p[1] << 16);
-  v[3] = __builtin_bit_cast(float, p[1] & 0xffff0000);
-  return v;
-}
-
 // A: per-plane partial sums of the three position tables -- written to the workspace, NOT added to the tables: all B*S planes
 // add into the same H + 16 rows, and 256-deep chains of same-address float atomics cost ~70 us however little data they
 // carry (measured: this kernel with the atomics, and nothing else, ran 72-74 us).  part[plane][0] = plane sum, [1 + h] = plane
@@ -61,7 +52,8 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_hist_kernel(const int64_t* 
     f32x4 ah = (f32x4)(0.f);
 #pragma unroll
     for (int w = 0; w < 16; ++w) {
-      const f32x4 f = bf4_to_f32(v[buf][w]);
+      const f32x2 lo = op16_unpack2((unsigned)v[buf][w][0]), hi = op16_unpack2((unsigned)v[buf][w][1]);
+      const f32x4 f = {lo[0], lo[1], hi[0], hi[1]};
       aw[w] += f;
       ah += f;
     }
@@ -159,7 +151,10 @@ __global__ __launch_bounds__(256) void embed_bwd_gather_kernel(const i32x2* __re
       acc = (f32x4)(0.f);
       cur = c;
     }
-    if (c >= 0) acc += bf4_to_f32(v[i]);
+    if (c >= 0) {
+      const f32x2 lo = op16_unpack2((unsigned)v[i][0]), hi = op16_unpack2((unsigned)v[i][1]);
+      acc += (f32x4){lo[0], lo[1], hi[0], hi[1]};
+    }
   }
   if (cur >= 0) flush(cur);
 }

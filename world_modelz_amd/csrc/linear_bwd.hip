@@ -12,35 +12,6 @@ namespace {
 
 constexpr int NT = 256;
 
-__device__ __forceinline__ float gelu_erf(float v) { return wmz_gelu(v); }
-
-template <typename T> __device__ __forceinline__ void unpack_chunk(const i32x4& c, float* f);
-template <> __device__ __forceinline__ void unpack_chunk<float>(const i32x4& c, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) f[i] = __int_as_float(c[i]);
-}
-template <> __device__ __forceinline__ void unpack_chunk<bf16_t>(const i32x4& c, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(((unsigned)c[i]) << 16);
-    f[2 * i + 1] = __uint_as_float(((unsigned)c[i]) & 0xFFFF0000u);
-  }
-}
-template <typename T> __device__ __forceinline__ i32x4 pack_chunk(const float* f);
-template <> __device__ __forceinline__ i32x4 pack_chunk<float>(const float* f) {
-  i32x4 c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = __float_as_int(f[i]);
-  return c;
-}
-template <> __device__ __forceinline__ i32x4 pack_chunk<bf16_t>(const float* f) {
-  i32x4 c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    c[i] = (int)((unsigned)f32_to_bf16_bits(f[2 * i]) | ((unsigned)f32_to_bf16_bits(f[2 * i + 1]) << 16));
-  return c;
-}
-
 // ------------------------------------------------------------------------------------------------ wgrad
 // Output tile 128 (n) x 128 (k') per workgroup, reduction over a slice of M.  Both operands are "m-major" in memory, so both
 // tiles are staged row = m and read as TRANSPOSED fragments (8 consecutive m of one column): bf16 through ds_read_b64_tr_b16
@@ -196,7 +167,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgBatch B, float* __restr
       if constexpr (PRO == 1 || PRO == 2) {
         if (k0 + c * EPC < P.K && (PRO != 1 || has_ln)) {
           float f[EPC];
-          unpack_chunk<T>(v, f);
+          Elem<T>::unpack(v, f);
           if constexpr (PRO == 1) {
             const float rs = lrs[S][it], mr = -lmu[S][it] * rs;
 #pragma unroll
@@ -204,9 +175,9 @@ __global__ __launch_bounds__(NT, 2) void wgrad2_kernel(WgBatch B, float* __restr
           } else {
             // bf16: the fitted GELU of the fused forward (2.6e-5 abs from the erf form, two orders below bf16 resolution)
 #pragma unroll
-            for (int e = 0; e < EPC; ++e) f[e] = sizeof(T) == 2 ? wmz_gelu_fast(f[e]) : gelu_erf(f[e]);
+            for (int e = 0; e < EPC; ++e) f[e] = sizeof(T) == 2 ? wmz_gelu_fast(f[e]) : wmz_gelu(f[e]);
           }
-          v = pack_chunk<T>(f);
+          v = Elem<T>::pack(f);
         }
       }
       *reinterpret_cast<i32x4*>(Cs + off) = rcs[S][it];
@@ -688,31 +659,6 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
-template <typename T> __device__ __forceinline__ void load4(const T* p, float (&f)[4]);
-template <> __device__ __forceinline__ void load4<float>(const float* p, float (&f)[4]) {
-  const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) f[e] = v[e];
-}
-template <> __device__ __forceinline__ void load4<bf16_t>(const bf16_t* p, float (&f)[4]) {
-  const s16x4 v = *reinterpret_cast<const s16x4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) f[e] = bf16_bits_to_f32((unsigned short)v[e]);
-}
-template <typename T> __device__ __forceinline__ void store4(T* p, const float (&f)[4]);
-template <> __device__ __forceinline__ void store4<float>(float* p, const float (&f)[4]) {
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = f[e];
-  *reinterpret_cast<f32x4*>(p) = v;
-}
-template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, const float (&f)[4]) {
-  s16x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = (short)f32_to_bf16_bits(f[e]);
-  *reinterpret_cast<s16x4*>(p) = v;
-}
-
 // one wave per row; lanes own interleaved 4-element column groups
 template <typename T>
 __global__ __launch_bounds__(NT) void ln_stats_kernel(const T* __restrict__ X, long ldx, float* __restrict__ mean,
@@ -724,7 +670,7 @@ __global__ __launch_bounds__(NT) void ln_stats_kernel(const T* __restrict__ X, l
     float s = 0.f;
     for (int k = lane * 4; k < K; k += 256) {
       float f[4];
-      load4<T>(x + k, f);
+      Elem<T>::load4(x + k, f);
       s += (f[0] + f[1]) + (f[2] + f[3]);
     }
     s = wave_sum(s);
@@ -732,7 +678,7 @@ __global__ __launch_bounds__(NT) void ln_stats_kernel(const T* __restrict__ X, l
     float q = 0.f;
     for (int k = lane * 4; k < K; k += 256) {
       float f[4];
-      load4<T>(x + k, f);
+      Elem<T>::load4(x + k, f);
 #pragma unroll
       for (int e = 0; e < 4; ++e) { const float d = f[e] - mu; q += d * d; }
     }
@@ -782,16 +728,16 @@ __global__ __launch_bounds__(1024 / KG) void ln_bwd_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < 4; ++e) { xv[u][c][e] = 0.f; dy[u][c][e] = 0.f; sk[u][c][e] = 0.f; }
         if (k0 < K) {
-          load4<T>(X + (long)mr[u] * ldx + k0, xv[u][c]);
-          load4<T>(DY + (long)mr[u] * lddy + k0, dy[u][c]);
+          Elem<T>::load4(X + (long)mr[u] * ldx + k0, xv[u][c]);
+          Elem<T>::load4(DY + (long)mr[u] * lddy + k0, dy[u][c]);
           if (!live[u]) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) dy[u][c][e] = 0.f;
           }
-          if (SKIP) load4<T>(SKIP + (long)mr[u] * ldskip + k0, sk[u][c]);
+          if (SKIP) Elem<T>::load4(SKIP + (long)mr[u] * ldskip + k0, sk[u][c]);
           if (SKIP2) {
             float s2[4];
-            load4<T>(SKIP2 + (long)mr[u] * ldskip2 + k0, s2);
+            Elem<T>::load4(SKIP2 + (long)mr[u] * ldskip2 + k0, s2);
 #pragma unroll
             for (int e = 0; e < 4; ++e) sk[u][c][e] += s2[e];
           }
@@ -842,7 +788,7 @@ __global__ __launch_bounds__(1024 / KG) void ln_bwd_kernel(const T* __restrict__
             float out[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) out[e] = rs * (gam[c][e] * dy[u][c][e] - c1 - xv[u][c][e] * c2) + sk[u][c][e];
-            store4<T>(DX + (long)mr[u] * lddx + k0, out);
+            Elem<T>::store4(DX + (long)mr[u] * lddx + k0, out);
           }
         }
       }
@@ -1292,8 +1238,9 @@ extern "C" int wmz_layernorm_stats(const void* x, long ldx, float* mean, float* 
   WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_layernorm_stats: bad dtype %d", dtype);
   const int grid = wmz_cdiv(M, 4) < 2048 ? wmz_cdiv(M, 4) : 2048;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16) hipLaunchKernelGGL(ln_stats_kernel<bf16_t>, dim3(grid), dim3(NT), 0, st, (const bf16_t*)x, ldx, mean, rstd, M, K, eps);
-  else hipLaunchKernelGGL(ln_stats_kernel<float>, dim3(grid), dim3(NT), 0, st, (const float*)x, ldx, mean, rstd, M, K, eps);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(ln_stats_kernel<T>, dim3(grid), dim3(NT), 0, st, (const T*)x, ldx, mean, rstd, M, K, eps);
+  });
   WMZ_LAUNCH_CHECK("wmz_layernorm_stats");
   return WMZ_OK;
 }

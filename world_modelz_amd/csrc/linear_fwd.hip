@@ -47,37 +47,6 @@ template <typename T> __device__ __forceinline__ const T* a_row(const LinParams&
   return A + (long)blk * P.bstride + (long)(m - blk * P.rpb) * P.lda;
 }
 
-__device__ __forceinline__ int swz128(int r) { return ((r >> 1) << 4) & 112; }
-
-__device__ __forceinline__ float gelu_erf(float v) { return wmz_gelu(v); }
-
-template <typename T> __device__ __forceinline__ void chunk_to_f32(const i32x4& c, float* f);
-template <> __device__ __forceinline__ void chunk_to_f32<float>(const i32x4& c, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) f[i] = __int_as_float(c[i]);
-}
-template <> __device__ __forceinline__ void chunk_to_f32<bf16_t>(const i32x4& c, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = bf16_bits_to_f32((unsigned short)((unsigned)c[i] & 0xFFFFu));          // (the unit's 16-bit format: wmz_common.h)
-    f[2 * i + 1] = bf16_bits_to_f32((unsigned short)((unsigned)c[i] >> 16));
-  }
-}
-template <typename T> __device__ __forceinline__ i32x4 f32_to_chunk(const float* f);
-template <> __device__ __forceinline__ i32x4 f32_to_chunk<float>(const float* f) {
-  i32x4 c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = __float_as_int(f[i]);
-  return c;
-}
-template <> __device__ __forceinline__ i32x4 f32_to_chunk<bf16_t>(const float* f) {
-  i32x4 c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    c[i] = (int)((unsigned)f32_to_bf16_bits(f[2 * i]) | ((unsigned)f32_to_bf16_bits(f[2 * i + 1]) << 16));
-  return c;
-}
-
 // PRO: 0 = A as is, 1 = LayerNorm(A) over K, 2 = GELU(A) (FeedForward second GEMM reading the saved pre-activation)
 // BM = 128: 4 waves as 2 x 2, each 64 x 64.  BM = 64 (small-M GEMMs that would otherwise leave CUs idle: the last-frame logits,
 // M = B*H*W; config 5's 3 072 rows per GPU): 4 waves side by side, each 64 rows x 32 columns.
@@ -122,7 +91,7 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
         const T* row = a_row<T>(P, gm);
         for (int c = sub; c * EPC < K; c += 8) {
           float f[EPC];
-          chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(row + c * EPC), f);
+          Elem<T>::unpack(*reinterpret_cast<const i32x4*>(row + c * EPC), f);
 #pragma unroll
           for (int i = 0; i < EPC; ++i) sum += f[i];
         }
@@ -134,7 +103,7 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
         const T* row = a_row<T>(P, gm);
         for (int c = sub; c * EPC < K; c += 8) {
           float f[EPC];
-          chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(row + c * EPC), f);
+          Elem<T>::unpack(*reinterpret_cast<const i32x4*>(row + c * EPC), f);
 #pragma unroll
           for (int i = 0; i < EPC; ++i) { const float d = f[i] - mean; sq += d * d; }
         }
@@ -190,21 +159,21 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
       i32x4 va = ras[S][i < AI ? i : 0];
       if constexpr (LN) {
         float f[EPC];
-        chunk_to_f32<T>(va, f);
+        Elem<T>::unpack(va, f);
         const float mu = mean_s[r], rs = rstd_s[r];
 #pragma unroll
         for (int e = 0; e < EPC; ++e) f[e] = (f[e] - mu) * rs * lng[S][e >> 2][e & 3] + lnb[S][e >> 2][e & 3];
-        va = f32_to_chunk<T>(f);
+        va = Elem<T>::pack(f);
         // (training: the rows as normalised here are what the weight gradient multiplies -- column tile 0 keeps them, so the
         //  backward's GEMM reads a plain operand instead of re-normalising per output tile)
         if (P.An != nullptr && bn == 0 && kok && m0 + r < P.M)
           *reinterpret_cast<i32x4*>(reinterpret_cast<T*>(P.An) + (long)(m0 + r) * P.ldan + k) = va;
       } else if constexpr (PRO == 2) {
         float f[EPC];
-        chunk_to_f32<T>(va, f);
+        Elem<T>::unpack(va, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) f[e] = gelu_erf(f[e]);
-        va = f32_to_chunk<T>(f);
+        for (int e = 0; e < EPC; ++e) f[e] = wmz_gelu(f[e]);
+        va = Elem<T>::pack(f);
       }
       *reinterpret_cast<i32x4*>(As + off) = va;
     }
@@ -385,7 +354,7 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
               for (int reg = 0; reg < 16; ++reg) {
                 const int rl = (BM == 64 ? 0 : 32 * i) + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
                 float v = acc[i][j][reg] + bv;
-                if (gelu) v = gelu_erf(v);
+                if (gelu) v = wmz_gelu(v);
                 stage[rl * BN + cl] = v;
               }
             }
@@ -416,18 +385,18 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
           if (col + 8 <= P.N) {
             if (R) {
               float r8[8];
-              chunk_to_f32<T>(*reinterpret_cast<const i32x4*>(R + (long)row * P.ldr + col), r8);
+              Elem<T>::unpack(*reinterpret_cast<const i32x4*>(R + (long)row * P.ldr + col), r8);
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 if (dgelu) f[e] *= wmz_dgelu(r8[e]);
                 else f[e] += r8[e];
               }
             }
-            *reinterpret_cast<i32x4*>(dst) = f32_to_chunk<T>(f);
+            *reinterpret_cast<i32x4*>(dst) = Elem<T>::pack(f);
             if (P.C2) {                                                // the activation next to the pre-activation
 #pragma unroll
-              for (int e = 0; e < 8; ++e) f[e] = gelu_erf(f[e]);
-              *reinterpret_cast<i32x4*>(reinterpret_cast<T*>(P.C2) + (long)row * P.ldc2 + col) = f32_to_chunk<T>(f);
+              for (int e = 0; e < 8; ++e) f[e] = wmz_gelu(f[e]);
+              *reinterpret_cast<i32x4*>(reinterpret_cast<T*>(P.C2) + (long)row * P.ldc2 + col) = Elem<T>::pack(f);
             }
           } else {
             for (int e = 0; e < 8 && col + e < P.N; ++e) {
@@ -438,7 +407,7 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
                 else v += rv;
               }
               dst[e] = Elem<T>::from_f32(v);
-              if (P.C2) reinterpret_cast<T*>(P.C2)[(long)row * P.ldc2 + col + e] = Elem<T>::from_f32(gelu_erf(v));
+              if (P.C2) reinterpret_cast<T*>(P.C2)[(long)row * P.ldc2 + col + e] = Elem<T>::from_f32(wmz_gelu(v));
             }
           }
         }
@@ -458,7 +427,7 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
         const int row = m0 + wr + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
         if (row >= P.M) continue;
         float v = acc[i][j][reg] + bv;
-        if (gelu) v = gelu_erf(v);
+        if (gelu) v = wmz_gelu(v);
         if (R) {
           const float rv = Elem<T>::to_f32(R[(long)row * P.ldr + col]);
           if (dgelu) {   // rv is the saved pre-activation z: multiply by gelu'(z)
@@ -469,7 +438,7 @@ __global__ __launch_bounds__(NT, 2) void linear_kernel(LinParams P) {
         }
         if (P.out_f32) reinterpret_cast<float*>(P.C)[(long)row * P.ldc + col] = v;
         else reinterpret_cast<T*>(P.C)[(long)row * P.ldc + col] = Elem<T>::from_f32(v);
-        if (P.C2) reinterpret_cast<T*>(P.C2)[(long)row * P.ldc2 + col] = Elem<T>::from_f32(gelu_erf(v));
+        if (P.C2) reinterpret_cast<T*>(P.C2)[(long)row * P.ldc2 + col] = Elem<T>::from_f32(wmz_gelu(v));
       }
     }
 }

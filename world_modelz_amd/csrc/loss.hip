@@ -4,29 +4,9 @@
 //   wmz_ce_fwd / _bwd   main.py:266-274  CrossEntropyLoss(reduction='none') over the last-frame logits and its gradient,
 //                                        written directly in the GEMM operand dtype
 #include "wmz_common.h"
+#include "wmz_philox.h"
 
 namespace {
-
-// Philox4x32-10 (Salmon et al. 2011): counter = (index, stream), key = seed
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-  const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-  const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-  const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ __forceinline__ void philox4(unsigned long long idx, unsigned long long seed, unsigned long long stream, float (&u)[4]) {
-  unsigned c[4] = {(unsigned)idx, (unsigned)(idx >> 32), (unsigned)stream, (unsigned)(stream >> 32)};
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) u[i] = (float)(c[i] >> 8) * (1.0f / 16777216.0f);   // [0, 1)
-}
 
 // one thread per last-frame position.  a = 0.1 r: with probability a redraw uniformly over the C codes, else keep the
 // token (== multinomial(lerp(one_hot, 1/C, a))); then positions with u < r become the mask token C.
@@ -42,7 +22,7 @@ __global__ __launch_bounds__(256) void corrupt_kernel(const int64_t* __restrict_
     const int p = (int)(i - (long)b * HW);
     const int64_t tok = z_last[b * clip_stride + p];
     float u[4];
-    philox4((unsigned long long)i, seed, stream, u);
+    philox4_unit((unsigned long long)i, stream, seed, u);
     const float rb = r[b];
     int64_t d = tok;
     if (u[0] < rb * 0.1f) { int k = (int)(u[1] * (float)C); d = k < C ? k : C - 1; }
@@ -53,7 +33,7 @@ __global__ __launch_bounds__(256) void corrupt_kernel(const int64_t* __restrict_
 }
 
 // One step of the sampler loop between two forward passes (main.py:76-104: top-k filter -> softmax -> multinomial -> re-mask):
-// one wave per row of logits, everything in registers, both uniforms from one Philox call.  Lane l holds the NV consecutive
+// one wave per row of logits, everything in registers, both uniforms from one Philox call (wmz_philox.h).  Lane l holds the NV consecutive
 // classes l * NV .. (classes past C are -inf).
 //   * top-k: the k-th largest logit by a 32-step bitwise search on order-preserving integer keys (count of keys >= candidate
 //     by wave ballots); logits below it are dropped, ties with it kept (the reference's `logits < v[:, -1]`);
@@ -122,7 +102,7 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
     const float total = __shfl(inc, 63);
     const float base = inc - part;
     float u[4];
-    philox4((unsigned long long)row, seed, (unsigned long long)ctr, u);
+    philox4_unit((unsigned long long)row, (unsigned long long)ctr, seed, u);
     const float xq = u[0] * total;
     int below = 0;
 #pragma unroll
@@ -178,20 +158,6 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
   }
 }
 
-template <typename T> __device__ __forceinline__ void ce_store4(T* p, const float (&f)[4]);
-template <> __device__ __forceinline__ void ce_store4<float>(float* p, const float (&f)[4]) {
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = f[e];
-  *reinterpret_cast<f32x4*>(p) = v;
-}
-template <> __device__ __forceinline__ void ce_store4<bf16_t>(bf16_t* p, const float (&f)[4]) {
-  s16x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = (short)f32_to_bf16_bits(f[e]);
-  *reinterpret_cast<s16x4*>(p) = v;
-}
-
 // Both of the above in ONE pass: a wave holds its row in registers (NCH float4 per lane, C <= 256 NCH), so the [R, C] logits
 // are read once instead of three times (max / sum-exp / gradient) and every access is 16 bytes (8 for the 16-bit gradient).
 template <typename T, int NCH>
@@ -240,7 +206,7 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const float* __restrict__
 #pragma unroll
       for (int e = 0; e < 4; ++e) o4[e] = (__expf(v[q][e] - l) - (c + e == tt ? 1.f : 0.f)) * g;
       if (c + 4 <= C && (C & 3) == 0) {
-        ce_store4<T>(d + c, o4);
+        Elem<T>::store4(d + c, o4);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) if (c + e < C) d[c + e] = Elem<T>::from_f32(o4[e]);
@@ -317,12 +283,11 @@ extern "C" int wmz_ce_fwd_bwd(const float* logits, long ld, const int64_t* targe
   }
   const int grid = (int)((R + 3) / 4 < 4096 ? (R + 3) / 4 : 4096);
   hipStream_t st = (hipStream_t)stream;
-#define WMZ_CEF(T, NCH) hipLaunchKernelGGL((ce_fused_kernel<T, NCH>), dim3(grid), dim3(256), 0, st, logits, ld, target, loss, lse, \
-                                           grad_rows, (T*)dlogits, R, C)
-#define WMZ_CEF_T(T) do { if (C <= 1024) WMZ_CEF(T, 4); else if (C <= 2048) WMZ_CEF(T, 8); else if (C <= 4096) WMZ_CEF(T, 16); \
-                          else WMZ_CEF(T, 32); } while (0)
-  if (dtype == WMZ_BF16) WMZ_CEF_T(bf16_t); else WMZ_CEF_T(float);
-#undef WMZ_CEF_T
+#define WMZ_CEF(NCH) hipLaunchKernelGGL((ce_fused_kernel<T, NCH>), dim3(grid), dim3(256), 0, st, logits, ld, target, loss, lse, \
+                                        grad_rows, (T*)dlogits, R, C)
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    if (C <= 1024) WMZ_CEF(4); else if (C <= 2048) WMZ_CEF(8); else if (C <= 4096) WMZ_CEF(16); else WMZ_CEF(32);
+  });
 #undef WMZ_CEF
   WMZ_LAUNCH_CHECK("wmz_ce_fwd_bwd");
   return WMZ_OK;
@@ -335,8 +300,9 @@ extern "C" int wmz_ce_bwd(const float* logits, long ld, const int64_t* target, c
   const long total = R * C;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16) hipLaunchKernelGGL(ce_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, logits, ld, target, lse, grad_rows, (bf16_t*)dlogits, R, C);
-  else hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, logits, ld, target, lse, grad_rows, (float*)dlogits, R, C);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, logits, ld, target, lse, grad_rows, (T*)dlogits, R, C);
+  });
   WMZ_LAUNCH_CHECK("wmz_ce_bwd");
   return WMZ_OK;
 }

@@ -19,28 +19,9 @@
 // Deterministic in (seed, stream id, device counter): a hipGraph replay with the counter advanced draws a fresh context.
 #include "wmz_common.h"
 #include "wmz_internal.h"
+#include "wmz_philox.h"
 
 namespace {
-
-__device__ __forceinline__ void sc_philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-  const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-  const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-  const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-// Philox4x32-10 (Salmon et al. 2011), as loss.hip: counter = (index, stream), key = seed
-__device__ __forceinline__ void sc_philox4(unsigned long long idx, unsigned long long seed, unsigned long long stream, unsigned (&c)[4]) {
-  c[0] = (unsigned)idx; c[1] = (unsigned)(idx >> 32); c[2] = (unsigned)stream; c[3] = (unsigned)(stream >> 32);
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    sc_philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-__device__ __forceinline__ float sc_unit(unsigned v) { return (float)(v >> 8) * (1.0f / 16777216.0f); }   // [0, 1)
 
 constexpr int SC_THREADS = 1024;
 constexpr unsigned long long SC_KEY_DOMAIN = 1ull << 63;      // stream-id bits that separate the three uses of the generator
@@ -77,8 +58,8 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) 
     if (P.o != nullptr) o = fminf(fmaxf(P.o[b], 0.f), 1.f - 1e-5f);
     else {
       unsigned c[4];
-      sc_philox4((unsigned long long)b, P.seed, stream | SC_WIN_DOMAIN, c);
-      o = sc_unit(c[0]);
+      philox4((unsigned long long)b, stream | SC_WIN_DOMAIN, P.seed, c);
+      o = philox_unit(c[0]);
     }
     const float first = floorf(o * ((float)P.S - frames + 1.f));
     win[0] = (int)first;
@@ -95,7 +76,7 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) 
   // ---- pass 1: histogram of the keys' top 11 bits
   for (int q = tid; q < nq; q += SC_THREADS) {
     unsigned c[4];
-    sc_philox4(kbase + q, P.seed, stream | SC_KEY_DOMAIN, c);
+    philox4(kbase + q, stream | SC_KEY_DOMAIN, P.seed, c);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (4 * q + e < Wn) atomicAdd(&hist[c[e] >> 21], 1u);
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) 
   // ---- pass 2: the candidates (every key up to that bin: >= n of them, <= n + one bin's worth), regenerated and compacted
   for (int q = tid; q < nq; q += SC_THREADS) {
     unsigned c[4];
-    sc_philox4(kbase + q, P.seed, stream | SC_KEY_DOMAIN, c);
+    philox4(kbase + q, stream | SC_KEY_DOMAIN, P.seed, c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * q + e;
@@ -155,10 +136,10 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) 
     const long pos = (long)wpos + (long)first * P.HW;
     const int64_t tok = P.z[b * P.clip_stride + pos];
     unsigned c[4];
-    sc_philox4((unsigned long long)b * P.n + i, P.seed, stream, c);
+    philox4((unsigned long long)b * P.n + i, stream, P.seed, c);
     int64_t d = tok;
-    if (sc_unit(c[0]) < rb * P.p_uniform) { const int kk = (int)(sc_unit(c[1]) * (float)P.C); d = kk < P.C ? kk : P.C - 1; }
-    if (sc_unit(c[2]) < rb) d = P.C;
+    if (philox_unit(c[0]) < rb * P.p_uniform) { const int kk = (int)(philox_unit(c[1]) * (float)P.C); d = kk < P.C ? kk : P.C - 1; }
+    if (philox_unit(c[2]) < rb) d = P.C;
     const long at = (long)b * P.n + i;
     P.indices[at] = pos;
     P.target[at] = tok;
@@ -196,8 +177,8 @@ __global__ __launch_bounds__(256) void categorical_scatter_kernel(const float* _
     }
     const float total = __shfl(incl, 63);
     unsigned cc[4];
-    sc_philox4((unsigned long long)row, seed, stream, cc);
-    const float want = sc_unit(cc[0]) * total;
+    philox4((unsigned long long)row, stream, seed, cc);
+    const float want = philox_unit(cc[0]) * total;
     // the owning lane: the first whose inclusive prefix exceeds `want` (the last lane if rounding leaves none)
     const unsigned long long owners = __ballot(incl > want);
     const int owner = owners ? (int)__builtin_ctzll(owners) : 63;

@@ -22,17 +22,6 @@ namespace {
 constexpr int VL_THREADS = 256;
 constexpr int VL_MAX_BLOCKS = 1024;
 
-template <typename T> __device__ __forceinline__ float vl_load(const T* p);
-template <> __device__ __forceinline__ float vl_load<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float vl_load<bf16_t>(const bf16_t* p) {
-  return bf16_bits_to_f32(*reinterpret_cast<const unsigned short*>(p));
-}
-template <typename T> __device__ __forceinline__ void vl_store(T* p, float v);
-template <> __device__ __forceinline__ void vl_store<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void vl_store<bf16_t>(bf16_t* p, float v) {
-  *reinterpret_cast<unsigned short*>(p) = f32_to_bf16_bits(v);
-}
-
 // sum over the workgroup (VL_THREADS = 4 waves), result in thread 0
 __device__ __forceinline__ float vl_block_sum(float v, float* scratch) {
   v = wave_sum(v);
@@ -64,7 +53,7 @@ __global__ __launch_bounds__(VL_THREADS) void vq_tail_fwd_kernel(const float* __
       acc = fmaf(d, d, acc);
       v = xv + d;                                            // the reference's own two roundings (vq.py:70)
     }
-    vl_store<TO>(st + i, v);
+    st[i] = Elem<TO>::from_f32(v);
   }
   const float s = vl_block_sum(acc, scratch);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
@@ -102,9 +91,9 @@ __global__ __launch_bounds__(VL_THREADS) void vq_tail_bwd_kernel(const TO* __res
   for (long i = (long)blockIdx.x * VL_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * VL_THREADS) {
     const long n = i / E;
     const int e = (int)(i - n * E);
-    float g = dst != nullptr ? vl_load<TO>(dst + n * Ep + e) : 0.f;
+    float g = dst != nullptr ? Elem<TO>::to_f32(*(dst + n * Ep + e)) : 0.f;
     g = fmaf(gl, x[i] - q[i], g);
-    vl_store<TI>(dx + i, g);
+    dx[i] = Elem<TI>::from_f32(g);
   }
 }
 
@@ -138,11 +127,11 @@ __global__ __launch_bounds__(VL_THREADS) void recon_loss_kernel(const T* __restr
     float out = 0.f;
     if (c < C) {
       const long b = px / HW, p = px - b * HW;
-      const float d = vl_load<T>(y + i) - t[(b * C + c) * HW + p];
+      const float d = Elem<T>::to_f32(y[i]) - t[(b * C + c) * HW + p];
       if constexpr (BWD) out = gs * recon_dloss_of(d, kind);
       else acc += recon_loss_of(d, kind);
     }
-    if constexpr (BWD) vl_store<T>(dy + i, out);
+    if constexpr (BWD) dy[i] = Elem<T>::from_f32(out);
   }
   if constexpr (!BWD) {
     const float s = vl_block_sum(acc, scratch);
@@ -167,8 +156,9 @@ extern "C" int wmz_vq_tail_fwd(const float* x, const float* q, const float* coun
   WMZ_REQUIRE(out_dtype == WMZ_F32 || out_dtype == WMZ_BF16, "wmz_vq_tail_fwd: bad dtype %d", out_dtype);
   hipStream_t s = (hipStream_t)stream;
   const int nb = vl_blocks(N * Ep);
-  if (out_dtype == WMZ_F32) hipLaunchKernelGGL(vq_tail_fwd_kernel<float>, dim3(nb), dim3(VL_THREADS), 0, s, x, q, (float*)st, N, E, Ep, partial);
-  else hipLaunchKernelGGL(vq_tail_fwd_kernel<bf16_t>, dim3(nb), dim3(VL_THREADS), 0, s, x, q, (bf16_t*)st, N, E, Ep, partial);
+  wmz_by_dtype2(out_dtype, [&](auto e) { typedef decltype(e) TO;
+    hipLaunchKernelGGL(vq_tail_fwd_kernel<TO>, dim3(nb), dim3(VL_THREADS), 0, s, x, q, (TO*)st, N, E, Ep, partial);
+  });
   WMZ_LAUNCH_CHECK("wmz_vq_tail_fwd");
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(VL_THREADS), 0, s, (const float*)partial, nb, 1.f / ((float)N * (float)E), loss,
                      counts, C, 1.f / (float)N, perplexity);
@@ -184,12 +174,9 @@ extern "C" int wmz_vq_tail_bwd(const void* d_st, const float* x, const float* q,
   hipStream_t s = (hipStream_t)stream;
   const int nb = vl_blocks(N * E);
   const float coef = 2.f / ((float)N * (float)E);
-#define VL_BWD(TI, TO) hipLaunchKernelGGL((vq_tail_bwd_kernel<TI, TO>), dim3(nb), dim3(VL_THREADS), 0, s, (const TO*)d_st, x, q, g_loss, coef, (TI*)d_x, N, E, Ep)
-  if (in_dtype == WMZ_F32 && st_dtype == WMZ_F32) VL_BWD(float, float);
-  else if (in_dtype == WMZ_F32) VL_BWD(float, bf16_t);
-  else if (st_dtype == WMZ_F32) VL_BWD(bf16_t, float);
-  else VL_BWD(bf16_t, bf16_t);
-#undef VL_BWD
+  wmz_by_dtype2(in_dtype, [&](auto ei) { wmz_by_dtype2(st_dtype, [&](auto eo) { typedef decltype(ei) TI; typedef decltype(eo) TO;
+    hipLaunchKernelGGL((vq_tail_bwd_kernel<TI, TO>), dim3(nb), dim3(VL_THREADS), 0, s, (const TO*)d_st, x, q, g_loss, coef, (TI*)d_x, N, E, Ep);
+  }); });
   WMZ_LAUNCH_CHECK("wmz_vq_tail_bwd");
   return WMZ_OK;
 }
@@ -201,12 +188,10 @@ extern "C" int wmz_recon_loss_fwd(const void* y, const float* target, float* par
   WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_recon_loss_fwd: bad dtype %d", dtype);
   hipStream_t s = (hipStream_t)stream;
   const int nb = vl_blocks(B * HW * Cp);
-  if (dtype == WMZ_F32)
-    hipLaunchKernelGGL((recon_loss_kernel<float, false>), dim3(nb), dim3(VL_THREADS), 0, s, (const float*)y, target, B, HW, C, Cp, kind, partial,
-                       (const float*)nullptr, 0.f, (float*)nullptr);
-  else
-    hipLaunchKernelGGL((recon_loss_kernel<bf16_t, false>), dim3(nb), dim3(VL_THREADS), 0, s, (const bf16_t*)y, target, B, HW, C, Cp, kind, partial,
-                       (const float*)nullptr, 0.f, (bf16_t*)nullptr);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL((recon_loss_kernel<T, false>), dim3(nb), dim3(VL_THREADS), 0, s, (const T*)y, target, B, HW, C, Cp, kind, partial,
+                       (const float*)nullptr, 0.f, (T*)nullptr);
+  });
   WMZ_LAUNCH_CHECK("wmz_recon_loss_fwd");
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(VL_THREADS), 0, s, (const float*)partial, nb,
                      1.f / ((float)B * (float)HW * (float)C), loss, (const float*)nullptr, 0, 0.f, (float*)nullptr);
@@ -222,12 +207,10 @@ extern "C" int wmz_recon_loss_bwd(const void* y, const float* target, const floa
   hipStream_t s = (hipStream_t)stream;
   const int nb = vl_blocks(B * HW * Cp);
   const float scale = 1.f / ((float)B * (float)HW * (float)C);
-  if (dtype == WMZ_F32)
-    hipLaunchKernelGGL((recon_loss_kernel<float, true>), dim3(nb), dim3(VL_THREADS), 0, s, (const float*)y, target, B, HW, C, Cp, kind,
-                       (float*)nullptr, g_loss, scale, (float*)d_y);
-  else
-    hipLaunchKernelGGL((recon_loss_kernel<bf16_t, true>), dim3(nb), dim3(VL_THREADS), 0, s, (const bf16_t*)y, target, B, HW, C, Cp, kind,
-                       (float*)nullptr, g_loss, scale, (bf16_t*)d_y);
+  wmz_by_dtype2(dtype, [&](auto e) { typedef decltype(e) T;
+    hipLaunchKernelGGL((recon_loss_kernel<T, true>), dim3(nb), dim3(VL_THREADS), 0, s, (const T*)y, target, B, HW, C, Cp, kind,
+                       (float*)nullptr, g_loss, scale, (T*)d_y);
+  });
   WMZ_LAUNCH_CHECK("wmz_recon_loss_bwd");
   return WMZ_OK;
 }

@@ -215,28 +215,116 @@ struct HalfGuardNone {
 typedef HalfGuardNone HalfGuard;
 #endif
 
+// ---- element types and their conversions to and from fp32, defined here ONCE for every unit: one element (to_f32 / from_f32),
+// four (load4 / store4: one 16- or 8-byte access) and a 16-byte chunk held in registers (unpack / pack: kPerChunk elements).
+// The two 16-bit tags mean different things:
+//   bf16_t    the UNIT's 16-bit operand format -- bfloat16, or IEEE half in a unit compiled with WMZ_OP16_F16 -- always through
+//             bf16_bits_to_f32 / f32_to_bf16_bits above (in a bfloat16 unit those ARE the shift and the rounding cast);
+//   _Float16  IEEE half BY NAME, whatever the unit's format: the element-wise kernels that take a WMZ_F16 dtype argument next to
+//             WMZ_BF16 in one (bfloat16) unit -- conv2d.hip's channel_stats / affine_act / bilinear2x, wmz_nchw_to_nhwc8's output.
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int kDtype = WMZ_F32;
   static constexpr int kPerChunk = 4;                  // elements per 16-byte chunk
   __device__ static __forceinline__ float to_f32(float v) { return v; }
   __device__ static __forceinline__ float from_f32(float v) { return v; }
+  __device__ static __forceinline__ void load4(const float* p, float (&f)[4]) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f[e] = v[e];
+  }
+  __device__ static __forceinline__ void store4(float* p, const float (&f)[4]) {
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = f[e];
+    *reinterpret_cast<f32x4*>(p) = v;
+  }
+  __device__ static __forceinline__ void unpack(const i32x4& c, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = __int_as_float(c[i]);
+  }
+  __device__ static __forceinline__ i32x4 pack(const float* f) {
+    i32x4 c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = __float_as_int(f[i]);
+    return c;
+  }
 };
 template <> struct Elem<bf16_t> {
   static constexpr int kDtype = WMZ_BF16;
   static constexpr int kPerChunk = 8;
   __device__ static __forceinline__ float to_f32(bf16_t v) { return bf16_bits_to_f32(__builtin_bit_cast(unsigned short, v)); }
   __device__ static __forceinline__ bf16_t from_f32(float v) { return __builtin_bit_cast(bf16_t, f32_to_bf16_bits(v)); }
+  __device__ static __forceinline__ void load4(const bf16_t* p, float (&f)[4]) {
+    const s16x4 v = *reinterpret_cast<const s16x4*>(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f[e] = bf16_bits_to_f32((unsigned short)v[e]);
+  }
+  __device__ static __forceinline__ void store4(bf16_t* p, const float (&f)[4]) {
+    s16x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (short)f32_to_bf16_bits(f[e]);
+    *reinterpret_cast<s16x4*>(p) = v;
+  }
+  __device__ static __forceinline__ void unpack(const i32x4& c, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = bf16_bits_to_f32((unsigned short)((unsigned)c[i] & 0xFFFFu));
+      f[2 * i + 1] = bf16_bits_to_f32((unsigned short)((unsigned)c[i] >> 16));
+    }
+  }
+  __device__ static __forceinline__ i32x4 pack(const float* f) {
+    i32x4 c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      c[i] = (int)((unsigned)f32_to_bf16_bits(f[2 * i]) | ((unsigned)f32_to_bf16_bits(f[2 * i + 1]) << 16));
+    return c;
+  }
 };
-
-// IEEE half by name, whatever the unit's 16-bit operand format: the element-wise kernels that take a WMZ_F16 dtype argument next to
-// WMZ_BF16 in one (bfloat16) unit -- conv2d.hip's, wmz_nchw_to_nhwc8's output
 template <> struct Elem<_Float16> {
   static constexpr int kDtype = WMZ_F16;
   static constexpr int kPerChunk = 8;
   __device__ static __forceinline__ float to_f32(_Float16 v) { return (float)v; }
   __device__ static __forceinline__ _Float16 from_f32(float v) { return (_Float16)v; }
+  __device__ static __forceinline__ void load4(const _Float16* p, float (&f)[4]) {
+    const f32x4 v = __builtin_convertvector(*reinterpret_cast<const f16x4_t*>(p), f32x4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f[e] = v[e];
+  }
+  __device__ static __forceinline__ void store4(_Float16* p, const float (&f)[4]) {
+    *reinterpret_cast<f16x4_t*>(p) = __builtin_convertvector((f32x4){f[0], f[1], f[2], f[3]}, f16x4_t);
+  }
+  __device__ static __forceinline__ void unpack(const i32x4& c, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      // (through a scalar copy: a bit_cast straight from the vector element c[i] read element 0 for every i)
+      const unsigned w = (unsigned)c[i];
+      const f32x2 v = __builtin_convertvector(__builtin_bit_cast(f16x2_t, w), f32x2);
+      f[2 * i] = v[0];
+      f[2 * i + 1] = v[1];
+    }
+  }
+  __device__ static __forceinline__ i32x4 pack(const float* f) {
+    i32x4 c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = (int)__builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){f[2 * i], f[2 * i + 1]}, f16x2_t));
+    return c;
+  }
 };
+
+// ---- host: a runtime dtype argument -> the element type.  f is a generic lambda taking a value of the type (`[&](auto e) {
+// typedef decltype(e) T; ... kernel<T> ... }`), so a kernel's launch is written once.  Two widths, because a lambda is instantiated
+// for every type its dispatcher names: wmz_by_dtype2 for entry points built for fp32 and the unit's 16-bit format, wmz_by_dtype3
+// for those that also take IEEE half by name.  The caller has checked dtype (WMZ_REQUIRE) before.
+template <typename F> static inline void wmz_by_dtype2(int dtype, F&& f) {
+  if (dtype == WMZ_BF16) f(bf16_t()); else f(float());
+}
+template <typename F> static inline void wmz_by_dtype3(int dtype, F&& f) {
+  if (dtype == WMZ_F16) f(_Float16()); else wmz_by_dtype2(dtype, f);
+}
+
+// byte offset XOR of row r in a 128-byte-row LDS image (rows swizzled in pairs): conflict-free ds_read_b128 fragment reads
+__device__ __forceinline__ int swz128(int r) { return ((r >> 1) << 4) & 112; }
 
 // An MFMA operand fragment of 8 consecutive k-elements (lane-local).
 template <typename T> struct Frag8;
