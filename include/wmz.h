@@ -258,7 +258,8 @@ int wmz_vq_ema_update(float* embedding, float* cluster_size, float* activation_c
  * W2 columns 32c..32c+31, then Wq, Wk', Wv' -- as 1 KB MFMA 32x32x16 A operands in (16-deep k-step, 32-feature block)
  * order, followed by 64 KB of padding; the LayerNorm affines are folded in (W1' = W1 diag(g2), Wk' = Wk diag(g1), ..).
  * vec: 2048 fp32: bout[D] b1'[M] b2[D] bk'[I] bv'[I] (b1' = b1 + W1 be2, bk' = Wk be1, bv' = bv + Wv be1), zero padded.
- * world_modelz_amd/fused.py (_pack_w, _layer_pack) builds both and documents the exact element order.  Built for
+ * wmz_layer_fused_pack builds both; csrc/fused_pack_rows.h owns the block order (W1' runs one chunk AHEAD of W2 in the stream:
+ * W1'[0], W1'[1], W2[0], .., W1'[7], W2[6], W2[7]), world_modelz_amd/fused.py::_pack_w states a block's element order.  Built for
  * D = 256, I = 128, M = 256; other widths return WMZ_ERR_UNSUPPORTED and callers use the per-op entry points above. */
 int wmz_layer_fused_fwd(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
                         const float* vec, int ntok, int D, int I, int M, int has_head, int has_tail, float eps,
@@ -403,8 +404,14 @@ int wmz_operands_refresh(const void* const* src0, const void* const* src1, const
 int wmz_conv_operands_refresh_packed(const void* const* weight, void* const* dst, const int* co, const int* ci, const int* kk,
                                      const int* mode, const int* pack, int n, int dtype, void* stream);
 
-/* Builds the packed weight stream and the vector block of wmz_layer_fused_fwd* from the layer's fp32 parameters in one
- * launch (the LayerNorm affines g2/be2 -- the feed-forward's norm -- and g1/be1 -- the NEXT layer's attention norm -- are
+/* ---- the weight streams of the fused per-token kernels.  ONE place says which blocks a stream holds, in which order and with
+ * which strides and ownership groups: csrc/fused_pack_rows.h (plain C++, checked on the host by tests/test_fused_pack_rows_cpu.py).
+ * wmz_layer_fused_pack and wmz_layer_fused_bwd_pack pack one boundary's / one layer's streams from it (rows by value: no copy to
+ * the device, usable under a graph capture); wmz_fused_pack_rows hands out the same rows for wmz_fused_pack_table, which packs
+ * every stream of a model from a device table.
+ *
+ * wmz_layer_fused_pack: the packed weight stream and the vector block of wmz_layer_fused_fwd* from the layer's fp32 parameters in
+ * one launch pair (the LayerNorm affines g2/be2 -- the feed-forward's norm -- and g1/be1 -- the NEXT layer's attention norm -- are
  * folded in).  Head parameters (wout .. b2) NULL: tail-only stream; tail parameters (g1 .. bv) NULL: head-only.
  * wpack: (weights + 32 768) bf16, vec: 2048 fp32. */
 int wmz_layer_fused_pack(const float* wout, const float* bout, const float* g2, const float* be2, const float* w1,
@@ -419,9 +426,17 @@ int wmz_layer_fused_pack(const float* wout, const float* bout, const float* g2, 
  * bf16 to dst in the kernels' piece order; start8 = index of the block's first 8-element group in the launch (row nblk:
  * total8).  vec_jobs: DEVICE array of nvec rows of ten pointers { bout, b1, w1, be2, b2, wk, wv, be1, bv, vec } (the
  * inputs and output of wmz_layer_fused_pack's vector block; absent parts NULL).  The streams' zero padding is the caller's
- * (allocate the buffers zeroed once).  world_modelz_amd/fused.py::PackSet builds the tables. */
+ * (allocate the buffers zeroed once).  world_modelz_amd/fused.py::PackSet builds the tables, the rows with wmz_fused_pack_rows. */
 int wmz_fused_pack_table(const void* block_rows, int nblk, long total8, const void* vec_jobs, int nvec, int D, int I, int M,
                          void* stream);
+/* The block rows of ONE stream in wmz_fused_pack_table's format, written to the HOST buffer rows_out (host only: no launch, no
+ * stream; the layout does not depend on the operand format, so there is no _f16 form).  kind 0: a forward boundary -- params =
+ * wmz_layer_fused_pack's fourteen parameter pointers in its order, the head's or the tail's NULL as there; at most 20 rows --,
+ * 1 / 2: a layer's backward qkv / feed-forward stream -- params = wmz_layer_fused_bwd_pack's eight; 3 / 10 rows.  dst: the
+ * stream's first element, start8: the launch's 8-element groups in front of this stream; the next stream's start8 is the last
+ * row's start8 + N K / 8.  Returns the number of rows written, or -WMZ_ERR_ARG (wmz_last_error says why: a missing parameter,
+ * widths other than 256 / 128 / 256). */
+int wmz_fused_pack_rows(int kind, const void* const* params, void* dst, long start8, int D, int I, int M, void* rows_out);
 
 /* Training forward on the same kernels (replaces the five per-op GEMM launches per layer of the training forward).
  * Besides the inference outputs they write what the backward (wmz_linear_wgrad_ws, wmz_layernorm_bwd, wmz_local3d_attn_bwd

@@ -204,6 +204,46 @@ def test_pack_set_equals_the_per_stream_packers():
             assert a.shape == b.shape and torch.equal(a, b)
 
 
+def _pack_w_groups(w, gn, gk):
+    """fused._pack_w with ownership groups: [N, K] -> 1 KB MFMA 32x32x16 A operands in (16-deep k-step s, 32-feature block b) order,
+    lane 32 h + r, 8 elements W[f][k .. k + 7]: within every group of gn features (gk contraction indices) lane half 0 owns the
+    first half and lane half 1 the second -- f = (b // (gn/32)) gn + ho gn/2 + 16 (b % (gn/32)) + i with (ho, i) the lane half /
+    accumulator register MFMA row r lands in, k = (s // (gk/16)) gk + h gk/2 + 8 (s % (gk/16)).  gn = N, gk = K is _pack_w."""
+    N, K = w.shape
+    dev = w.device
+    r, b, s = torch.arange(32, device=dev), torch.arange(N // 32, device=dev), torch.arange(K // 16, device=dev)
+    bpg, spg = gn // 32, gk // 16
+    f = ((b // bpg) * gn + (b % bpg) * 16)[:, None] + (((r >> 2) & 1) * (gn // 2) + (r & 3) + 4 * (r >> 3))[None, :]        # [b, r]
+    k = (((s // spg) * gk + (s % spg) * 8)[:, None, None] + (torch.arange(2, device=dev) * (gk // 2))[None, :, None]
+         + torch.arange(8, device=dev)[None, None, :])                                                                   # [s, h, j]
+    return w[f][:, :, k].permute(2, 0, 3, 1, 4).reshape(-1)                    # [b, r, s, h, j] -> [s, b, h, r, j]
+
+
+def test_backward_stream_packer_matches_the_documented_order(layer):
+    """wmz_layer_fused_bwd_pack against the tensor-op statement of its two streams (include/wmz.h, csrc/fused_pack_rows.h): the
+    TRANSPOSED blocks Wk'^T | Wv'^T | Wq^T in groups of 128 / 128, and W2^T[c] (32 / 128) | W1'^T (128 / 32) | Wout^T (128 / 128),
+    the LayerNorm weights folded into the rows -- bit-exact, 64 KB of zeros behind each."""
+    from world_modelz_amd import _cast, fused
+    attn, ff = layer
+    bf = lambda w: w.to(torch.bfloat16)  # noqa: E731
+    with torch.no_grad():
+        w = torch.randn(64, 96, device='cuda')
+        assert torch.equal(_pack_w_groups(w, 64, 96), fused._pack_w(w))          # the generalisation is _pack_w where it has to be
+        g1, g2 = attn.norm.weight, ff.norm.weight
+        wq, wk, wv, wout = attn.fn.to_q.weight, attn.fn.to_k.weight, attn.fn.to_v.weight, attn.fn.to_out[0].weight
+        w1, w2 = ff.fn.net[0].weight, ff.fn.net[3].weight
+        ref_qkv = torch.cat([_pack_w_groups(bf(wk * g1[None, :]).t(), 128, 128), _pack_w_groups(bf(wv * g1[None, :]).t(), 128, 128),
+                             _pack_w_groups(bf(wq).t(), 128, 128)])
+        ref_ff = torch.cat([_pack_w_groups(bf(w2[:, c * 32:(c + 1) * 32]).t(), 32, 128) for c in range(M // 32)]
+                           + [_pack_w_groups(bf(w1 * g2[None, :]).t(), 128, 32), _pack_w_groups(bf(wout).t(), 128, 128)])
+    _cast.clear()
+    wpack_qkv, wpack_ff = fused._layer_pack_bwd(attn, ff)
+    assert ref_qkv.numel() == 3 * D * I == 98304 and ref_ff.numel() == 2 * M * D + D * I == 163840
+    for got, ref in ((wpack_qkv, ref_qkv), (wpack_ff, ref_ff)):
+        assert got.numel() == ref.numel() + 32768
+        assert torch.equal(got[:ref.numel()], ref) and (got[ref.numel():] == 0).all()
+
+
 def test_linear_wgrad_batch_vs_torch():
     """wmz_linear_wgrad_batch: several weight gradients of different shapes by one launch pair; accumulate vs overwrite,
     with and without a bias gradient, against fp32 torch on the same bf16 operands."""

@@ -71,10 +71,11 @@ def test_guard_entry_points_are_declared_exported_and_bound():
 
 # (VGPRs incl. AGPRs, scratch bytes) of every kernel of the half denoiser units in the PARENT commit's build (dee100e), taken with
 # the extraction below (hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only) before the guard went into the sources
+# (the three pack kernels whose argument types csrc/fused_pack_rows.h renamed keep that build's figures under their new names)
 PARENT = {
-    ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_117fused_pack_kernelENS_10PackParamsE'): (36, 0),
-    ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_121fused_pack_vec_kernelENS_10PackParamsE'): (14, 0),
-    ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_123fused_pack_table_kernelEPKNS_8PackRowGEil'): (37, 0),
+    ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_117fused_pack_kernelENS_8PackRowsE'): (36, 0),
+    ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_121fused_pack_vec_kernelENS_7VecJobGEiii'): (14, 0),
+    ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_123fused_pack_table_kernelEPK12FusedPackRowil'): (37, 0),
     ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_127fused_pack_vec_table_kernelEPKNS_7VecJobGEiii'): (14, 0),
     ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_118layer_fused_kernelILi256ELi128ELi256ELb1ELb1EEEvNS_11FusedParamsE'): (254, 0),
     ('layer_fused_f16.hip', '_ZN12_GLOBAL__N_118layer_fused_kernelILi256ELi128ELi256ELb1ELb0EEEvNS_11FusedParamsE'): (254, 0),

@@ -22,6 +22,7 @@
 //   * the feed-forward is walked 32 hidden units at a time (W1 rows -> GELU -> W2 columns), so its activation never
 //     exists in full and the chunk's accumulator (16 registers) is converted in place to the next operand.
 #include "fused_common.h"
+#include "fused_pack_rows.h"
 #include "wmz_debug.h"
 
 namespace {
@@ -390,6 +391,15 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
 }  // namespace
 
 static int fused_launch(FusedParams& P, int ntok, int D, int I, int M, int has_head, int has_tail, void* stream);
+// What every launch sets; everything optional off: no embedding (z NULL), identity rows (rows_out 0), row-major streams (xflags 0),
+// none of the training outputs (NULL; kv as k rows then v rows), no probes (fused_launch sets dbg / ts).
+static FusedParams fused_params(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                                const float* vec, int ntok, float eps) {
+  FusedParams P = {};
+  P.o = (const bf16_t*)o; P.x = (const bf16_t*)x; P.xo = (bf16_t*)x_out; P.q = (bf16_t*)q_out; P.kv = (bf16_t*)kv_out;
+  P.wpack = (const char*)wpack; P.vec = vec; P.ntok = ntok; P.eps = eps;
+  return P;
+}
 static long long* g_fused_ts = nullptr;
 static int g_fused_dbg = 0;       // ablation switches (wmz_debug_fused_knobs): 1 = skip the MFMA loops, 2 = skip the weight DMA + waits
 #ifndef WMZ_OP16_F16
@@ -405,55 +415,65 @@ extern "C" int WMZ_FN(wmz_layer_fused_fwd)(const void* o, const void* x, void* x
                                     eps, stream);
 }
 
-
-// ---- weight stream packer (host side of the kernel above used to be ~60 small torch launches per layer) ----------
+// ---- weight stream packers (the host side of the kernel above used to be ~60 small torch launches per layer) ----------
+// Which blocks a stream holds and in which order: fused_pack_rows.h.  The rows reach the device by value -- wmz_layer_fused_pack,
+// wmz_layer_fused_bwd_pack: one stream per launch, its rows in the kernel arguments, no copy to the device, so a cache miss during
+// a graph capture can still pack -- or by table -- wmz_fused_pack_table: every stream and vector block of a model in TWO launches
+// (training, after each optimizer step: a launch pair per stream is 13 + 5 launches of ~7 us per config-4 step) from DEVICE rows
+// built once by the host (fused.PackSet; one extra row = the end) and vector jobs of ten 64-bit fields (VecJobG).
 namespace {
-// element (f, k) of a block = w[f * rs + k * ks] (* gamma[k]) (* rgamma[f]); N output features, K contraction length.
-// gn / gk: ownership groups -- within every group of gn output features (gk contraction indices) lane half 0 owns the
-// first half and lane half 1 the second (forward: gn = N, gk = K: a lane owns one contiguous half row; the backward
-// kernels use groups of 128, the width of an LDS-staged row tile, and of 32 for the hidden axis walked in chunks).
-struct PackBlock { const float* w; long rs, ks; int N, K, gn, gk; const float* gamma; const float* rgamma; long dst; };
-struct PackParams {
-  PackBlock blk[24]; int nblk; long total;          // total bf16 elements of the stream (without the padding)
-  bf16_t* wpack; long padded;
-  // vec: bout | b1 + W1 be2 | b2 | Wk be1 | bv + Wv be1   (2048 floats, zero padded)
-  const float *bout, *b1, *w1, *be2, *b2, *wk, *wv, *be1, *bv; float* vec; int D, I, M;
-};
-__global__ __launch_bounds__(256) void fused_pack_kernel(PackParams P) {
-  const long e8 = ((long)blockIdx.x * 256 + threadIdx.x) * 8;          // 8 consecutive stream elements = one lane's fragment
-  if (e8 < P.total) {
+struct PackRows { FusedPackRow row[24]; int n; long total8, padded8; };     // groups of 8 elements: of the stream, with its zero padding
+struct VecJobG { const float *bout, *b1, *w1, *be2, *b2, *wk, *wv, *be1, *bv; float* vec; };
+static_assert(sizeof(VecJobG) == 80, "table layouts are part of the C ABI");
+
+// group g of block B: 8 consecutive stream elements = one lane's fragment of one 1 KB piece
+__device__ __forceinline__ void pack_group(const FusedPackRow& B, long g) {
+  const long e = g * 8;
+  const int NB = (int)B.N / 32;
+  const int piece = (int)(e / 512), lane = (int)((e % 512) / 8);
+  const int s = piece / NB, b = piece % NB;
+  const int r = lane & 31, h = lane >> 5;
+  const int bpg = (int)B.gn / 32, spg = (int)B.gk / 16;
+  // output feature of MFMA row r of block b (row r lands in lane half (r >> 2) & 1, accumulator register (r & 3) + 4 (r >> 3))
+  const int f = (b / bpg) * (int)B.gn + ((r >> 2) & 1) * ((int)B.gn / 2) + (b % bpg) * 16 + (r & 3) + 4 * (r >> 3);
+  const int k0 = (s / spg) * (int)B.gk + h * ((int)B.gk / 2) + (s % spg) * 8;
+  const float rg = B.rgamma ? B.rgamma[f] : 1.f;
+  s16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float x = B.w[(long)f * B.rs + (long)(k0 + j) * B.ks] * rg;
+    if (B.gamma) x *= B.gamma[k0 + j];
+    v[j] = (short)f32_to_bf16_bits(x);
+  }
+  *reinterpret_cast<s16x8*>(B.dst + e) = v;
+}
+__global__ __launch_bounds__(256) void fused_pack_kernel(PackRows P) {
+  const long g8 = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g8 < P.total8) {
     int bi = 0;
 #pragma unroll 1
-    for (int i = 1; i < P.nblk; ++i) if (e8 >= P.blk[i].dst) bi = i;
-    const PackBlock B = P.blk[bi];
-    const long e = e8 - B.dst;
-    const int NB = B.N / 32;
-    const int piece = (int)(e / 512), lane = (int)((e % 512) / 8);
-    const int s = piece / NB, b = piece % NB;
-    const int r = lane & 31, h = lane >> 5;
-    const int bpg = B.gn / 32, spg = B.gk / 16;
-    // output feature of MFMA row r of block b (row r lands in lane half (r >> 2) & 1, accumulator register (r & 3) + 4 (r >> 3))
-    const int f = (b / bpg) * B.gn + ((r >> 2) & 1) * (B.gn / 2) + (b % bpg) * 16 + (r & 3) + 4 * (r >> 3);
-    const int k0 = (s / spg) * B.gk + h * (B.gk / 2) + (s % spg) * 8;
-    s16x8 v;
-    const float rg = B.rgamma ? B.rgamma[f] : 1.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float x = B.w[(long)f * B.rs + (long)(k0 + j) * B.ks] * rg;
-      if (B.gamma) x *= B.gamma[k0 + j];
-      v[j] = (short)f32_to_bf16_bits(x);
-    }
-    *reinterpret_cast<s16x8*>(P.wpack + e8) = v;
-  } else if (e8 < P.padded) {
-    *reinterpret_cast<s16x8*>(P.wpack + e8) = (s16x8)(0);
+    for (int i = 1; i < P.n; ++i) if (g8 >= P.row[i].start8) bi = i;
+    const FusedPackRow& B = P.row[bi];
+    pack_group(B, g8 - B.start8);
+  } else if (g8 < P.padded8) {
+    *reinterpret_cast<s16x8*>(P.row[0].dst + g8 * 8) = (s16x8)(0);
   }
 }
-// the vector block: bout | b1 + W1 be2 | b2 | Wk be1 | bv + Wv be1.  One wave per entry: plain entries are a copy, the
-// matrix-vector entries a coalesced 256-long dot (4 floats per lane) + wave reduction.
-__global__ __launch_bounds__(256) void fused_pack_vec_kernel(PackParams P) {
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (t >= 2048) return;
-  const int D = P.D, I = P.I, M = P.M;
+__global__ __launch_bounds__(256) void fused_pack_table_kernel(const FusedPackRow* __restrict__ rows, int nblk, long total8) {
+  const long g8 = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g8 >= total8) return;
+  int lo = 0, hi = nblk - 1;                             // last block with start8 <= g8
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (rows[mid].start8 <= g8) lo = mid; else hi = mid - 1;
+  }
+  const FusedPackRow B = rows[lo];
+  pack_group(B, g8 - B.start8);
+}
+
+// entry t of the vector block bout | b1 + W1 be2 | b2 | Wk be1 | bv + Wv be1 (2048 floats, zero padded), one wave per entry: plain
+// entries are a copy, the matrix-vector entries a coalesced 256-long dot (4 floats per lane) + wave reduction.
+__device__ __forceinline__ void pack_vec_entry(const VecJobG& P, int t, int lane, int D, int I, int M) {
   const float* row = nullptr; const float* vecb = nullptr; float base = 0.f;
   if (t < D) base = P.bout ? P.bout[t] : 0.f;
   else if (t < D + M) { if (P.b1) { base = P.b1[t - D]; row = P.w1 + (long)(t - D) * D; vecb = P.be2; } }
@@ -468,6 +488,22 @@ __global__ __launch_bounds__(256) void fused_pack_vec_kernel(PackParams P) {
   }
   if (lane == 0) P.vec[t] = base + acc;
 }
+__global__ __launch_bounds__(256) void fused_pack_vec_kernel(VecJobG P, int D, int I, int M) {
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (t < 2048) pack_vec_entry(P, t, lane, D, I, M);
+}
+__global__ __launch_bounds__(256) void fused_pack_vec_table_kernel(const VecJobG* __restrict__ jobs, int D, int I, int M) {
+  const VecJobG P = jobs[blockIdx.y];
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (t < 2048) pack_vec_entry(P, t, lane, D, I, M);
+}
+
+// one stream by value: P.row[0 .. P.n) written from group 0 on, + 64 KB of zeros behind the stream
+void fused_pack_launch(PackRows& P, hipStream_t stream) {
+  P.total8 = fused_rows_groups(P.row, P.n);
+  P.padded8 = P.total8 + 65536 / 2 / 8;
+  hipLaunchKernelGGL(fused_pack_kernel, dim3((unsigned)wmz_cdiv(P.padded8, 256)), dim3(256), 0, stream, P);
+}
 }  // namespace
 
 extern "C" int WMZ_FN(wmz_layer_fused_pack)(const float* wout, const float* bout, const float* g2, const float* be2, const float* w1,
@@ -479,98 +515,16 @@ extern "C" int WMZ_FN(wmz_layer_fused_pack)(const float* wout, const float* bout
   WMZ_REQUIRE(D == 256 && I == 128 && M == 256, "wmz_layer_fused_pack: built for dim 256 / inner 128 / mlp 256");
   WMZ_REQUIRE(!head || (bout && g2 && be2 && w1 && b1 && w2 && b2), "wmz_layer_fused_pack: head parameters missing");
   WMZ_REQUIRE(!tail || (g1 && be1 && wk && wv && bv), "wmz_layer_fused_pack: tail parameters missing");
-  PackParams P;
-  int n = 0;
-  long off = 0;
-  auto add = [&](const float* w, long rs, int N, int K, const float* gamma) {
-    P.blk[n].w = w; P.blk[n].rs = rs; P.blk[n].ks = 1; P.blk[n].N = N; P.blk[n].K = K; P.blk[n].gn = N; P.blk[n].gk = K;
-    P.blk[n].gamma = gamma; P.blk[n].rgamma = nullptr; P.blk[n].dst = off;
-    off += (long)N * K; ++n;
-  };
-  constexpr int MCH = 32;
-  if (head) {
-    add(wout, I, D, I, nullptr);
-    add(w1, D, MCH, D, g2);                                              // W1[0]
-    for (int c = 1; c < M / MCH; ++c) {
-      add(w1 + (long)c * MCH * D, D, MCH, D, g2);                        // W1[c]
-      add(w2 + (c - 1) * MCH, M, D, MCH, nullptr);                       // W2[:, c-1]
-    }
-    add(w2 + (M / MCH - 1) * MCH, M, D, MCH, nullptr);
-  }
-  if (tail) {
-    add(wq, D, I, D, nullptr);
-    add(wk, D, I, D, g1);
-    add(wv, D, I, D, g1);
-  }
-  P.nblk = n; P.total = off; P.padded = off + 65536 / 2;                 // + 64 KB of zeros behind the stream
-  P.wpack = (bf16_t*)wpack;
-  P.bout = head ? bout : nullptr; P.b1 = head ? b1 : nullptr; P.w1 = w1; P.be2 = be2; P.b2 = head ? b2 : nullptr;
-  P.wk = tail ? wk : nullptr; P.wv = tail ? wv : nullptr; P.be1 = be1; P.bv = bv; P.vec = vec; P.D = D; P.I = I; P.M = M;
-  hipLaunchKernelGGL(fused_pack_kernel, dim3((unsigned)wmz_cdiv(P.padded / 8, 256)), dim3(256), 0, (hipStream_t)stream, P);
-  hipLaunchKernelGGL(fused_pack_vec_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, P);
+  const float* const p[14] = {wout, bout, g2, be2, w1, b1, w2, b2, g1, be1, wq, wk, wv, bv};
+  PackRows P;
+  P.n = fused_fwd_rows(P.row, p, (unsigned short*)wpack, 0);
+  fused_pack_launch(P, (hipStream_t)stream);
+  const VecJobG J{head ? bout : nullptr, head ? b1 : nullptr, w1, be2, head ? b2 : nullptr,
+                  tail ? wk : nullptr, tail ? wv : nullptr, be1, bv, vec};
+  hipLaunchKernelGGL(fused_pack_vec_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, J, D, I, M);
   WMZ_LAUNCH_CHECK("wmz_layer_fused_pack");
   return WMZ_OK;
 }
-
-// ---- every weight stream and vector block of a whole model in TWO launches (training: after each optimizer step) ----------
-// The per-boundary entry points above cost a launch pair per stream (13 + 5 launches of ~7 us per config-4 step).  Here the
-// block descriptors live in DEVICE memory, built once by the host (fused.PackSet): table rows of eleven 64-bit fields
-//   { w, rs, ks, N, K, gn, gk, gamma, rgamma, dst, start8 }      (PackBlock above; dst = the block's first stream element,
-//                                                                  start8 = first 8-element group of the block in the
-//                                                                  launch's global numbering; one extra row = the end)
-// and vector jobs of ten 64-bit fields { bout, b1, w1, be2, b2, wk, wv, be1, bv, vec } (fused_pack_vec_kernel's inputs).
-namespace {
-struct PackRowG { const float* w; long rs, ks, N, K, gn, gk; const float* gamma; const float* rgamma; bf16_t* dst; long start8; };
-struct VecJobG { const float *bout, *b1, *w1, *be2, *b2, *wk, *wv, *be1, *bv; float* vec; };
-static_assert(sizeof(PackRowG) == 88 && sizeof(VecJobG) == 80, "table layouts are part of the C ABI");
-
-__global__ __launch_bounds__(256) void fused_pack_table_kernel(const PackRowG* __restrict__ rows, int nblk, long total8) {
-  const long g8 = (long)blockIdx.x * 256 + threadIdx.x;
-  if (g8 >= total8) return;
-  int lo = 0, hi = nblk - 1;                             // last block with start8 <= g8
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rows[mid].start8 <= g8) lo = mid; else hi = mid - 1;
-  }
-  const PackRowG B = rows[lo];
-  const long e = (g8 - B.start8) * 8;
-  const int NB = (int)B.N / 32;
-  const int piece = (int)(e / 512), lane = (int)((e % 512) / 8);
-  const int s = piece / NB, b = piece % NB;
-  const int r = lane & 31, h = lane >> 5;
-  const int bpg = (int)B.gn / 32, spg = (int)B.gk / 16;
-  const int f = (b / bpg) * (int)B.gn + ((r >> 2) & 1) * ((int)B.gn / 2) + (b % bpg) * 16 + (r & 3) + 4 * (r >> 3);
-  const int k0 = (s / spg) * (int)B.gk + h * ((int)B.gk / 2) + (s % spg) * 8;
-  const float rg = B.rgamma ? B.rgamma[f] : 1.f;
-  s16x8 v;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float x = B.w[(long)f * B.rs + (long)(k0 + j) * B.ks] * rg;
-    if (B.gamma) x *= B.gamma[k0 + j];
-    v[j] = (short)f32_to_bf16_bits(x);
-  }
-  *reinterpret_cast<s16x8*>(B.dst + e) = v;
-}
-
-__global__ __launch_bounds__(256) void fused_pack_vec_table_kernel(const VecJobG* __restrict__ jobs, int D, int I, int M) {
-  const VecJobG P = jobs[blockIdx.y];
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (t >= 2048) return;
-  const float* row = nullptr; const float* vecb = nullptr; float base = 0.f;
-  if (t < D) base = P.bout ? P.bout[t] : 0.f;
-  else if (t < D + M) { if (P.b1) { base = P.b1[t - D]; row = P.w1 + (long)(t - D) * D; vecb = P.be2; } }
-  else if (t < 2 * D + M) base = P.b2 ? P.b2[t - D - M] : 0.f;
-  else if (t < 2 * D + M + I) { if (P.wk) { row = P.wk + (long)(t - 2 * D - M) * D; vecb = P.be1; } }
-  else if (t < 2 * D + M + 2 * I) { if (P.wv) { base = P.bv[t - 2 * D - M - I]; row = P.wv + (long)(t - 2 * D - M - I) * D; vecb = P.be1; } }
-  float acc = 0.f;
-  if (row != nullptr) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(row + lane * 4), b = *reinterpret_cast<const f32x4*>(vecb + lane * 4);
-    acc = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-    acc = wave_sum(acc);
-  }
-  if (lane == 0) P.vec[t] = base + acc;
-}
-}  // namespace
 
 extern "C" int WMZ_FN(wmz_fused_pack_table)(const void* block_rows, int nblk, long total8, const void* vec_jobs, int nvec, int D, int I,
                                     int M, void* stream) {
@@ -579,7 +533,7 @@ extern "C" int WMZ_FN(wmz_fused_pack_table)(const void* block_rows, int nblk, lo
   WMZ_REQUIRE(D == 256 && I == 128 && M == 256, "wmz_fused_pack_table: built for dim 256 / inner 128 / mlp 256");
   if (nblk > 0)
     hipLaunchKernelGGL(fused_pack_table_kernel, dim3((unsigned)wmz_cdiv(total8, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const PackRowG*)block_rows, nblk, total8);
+                       (const FusedPackRow*)block_rows, nblk, total8);
   if (nvec > 0)
     hipLaunchKernelGGL(fused_pack_vec_table_kernel, dim3(512, (unsigned)nvec), dim3(256), 0, (hipStream_t)stream,
                        (const VecJobG*)vec_jobs, D, I, M);
@@ -588,10 +542,8 @@ extern "C" int WMZ_FN(wmz_fused_pack_table)(const void* block_rows, int nblk, lo
 }
 
 #ifndef WMZ_OP16_F16      // (training forward + backward streams: the bf16 unit only)
-// Weight streams of the fused BACKWARD kernels (layer_fused_bwd.hip), TRANSPOSED blocks in consumption order:
-//   wpack_qkv:  Wk'^T | Wv'^T | Wq^T          ([D x I] each; ' = the attention LayerNorm's gamma folded in: rows scaled)
-//   wpack_ff:   W2^T[c] (c = 0 .. M/32-1: [32 x D]) | W1'^T [D x M] | Wout^T [I x D]
-// Either may be NULL.  Each stream is followed by 64 KB of zeros (the kernels' prefetch runs past the end).
+// Weight streams of the fused BACKWARD kernels (layer_fused_bwd.hip): fused_bwd_qkv_rows / fused_bwd_ff_rows.  Either destination
+// may be NULL.  Each stream is followed by 64 KB of zeros (the kernels' prefetch runs past the end).
 extern "C" int wmz_layer_fused_bwd_pack(const float* wq, const float* wk, const float* wv, const float* g1, const float* wout,
                                         const float* w1, const float* g2, const float* w2, void* wpack_qkv, void* wpack_ff,
                                         int D, int I, int M, void* stream) {
@@ -599,34 +551,28 @@ extern "C" int wmz_layer_fused_bwd_pack(const float* wq, const float* wk, const 
   WMZ_REQUIRE(wpack_qkv || wpack_ff, "wmz_layer_fused_bwd_pack: nothing to do");
   WMZ_REQUIRE(!wpack_qkv || (wq && wk && wv && g1), "wmz_layer_fused_bwd_pack: attention parameters missing");
   WMZ_REQUIRE(!wpack_ff || (wout && w1 && g2 && w2), "wmz_layer_fused_bwd_pack: feed-forward parameters missing");
-  for (int which = 0; which < 2; ++which) {
-    void* dst = which == 0 ? wpack_qkv : wpack_ff;
-    if (dst == nullptr) continue;
-    PackParams P;
-    int n = 0;
-    long off = 0;
-    // element (f, k) = w[f + k * ld]: the transpose of a row-major [K, ld] matrix
-    auto addT = [&](const float* w, long ld, int N, int K, int gn, int gk, const float* rgamma) {
-      P.blk[n].w = w; P.blk[n].rs = 1; P.blk[n].ks = ld; P.blk[n].N = N; P.blk[n].K = K; P.blk[n].gn = gn; P.blk[n].gk = gk;
-      P.blk[n].gamma = nullptr; P.blk[n].rgamma = rgamma; P.blk[n].dst = off;
-      off += (long)N * K; ++n;
-    };
-    if (which == 0) {
-      addT(wk, D, D, I, 128, 128, g1);
-      addT(wv, D, D, I, 128, 128, g1);
-      addT(wq, D, D, I, 128, 128, nullptr);
-    } else {
-      for (int c = 0; c < M / 32; ++c) addT(w2 + c * 32, M, 32, D, 32, 128, nullptr);     // dg_c = W2[:, c]^T dy
-      addT(w1, D, D, M, 128, 32, g2);                                                      // dxhat = W1'^T dz
-      addT(wout, I, I, D, 128, 128, nullptr);                                              // do = Wout^T dx1
-    }
-    P.nblk = n; P.total = off; P.padded = off + 65536 / 2;
-    P.wpack = (bf16_t*)dst;
-    P.bout = P.b1 = P.w1 = P.be2 = P.b2 = P.wk = P.wv = P.be1 = P.bv = nullptr; P.vec = nullptr; P.D = D; P.I = I; P.M = M;
-    hipLaunchKernelGGL(fused_pack_kernel, dim3((unsigned)wmz_cdiv(P.padded / 8, 256)), dim3(256), 0, (hipStream_t)stream, P);
-  }
+  const float* const p[8] = {wq, wk, wv, g1, wout, w1, g2, w2};
+  PackRows P;
+  if (wpack_qkv) { P.n = fused_bwd_qkv_rows(P.row, p, (unsigned short*)wpack_qkv, 0); fused_pack_launch(P, (hipStream_t)stream); }
+  if (wpack_ff) { P.n = fused_bwd_ff_rows(P.row, p, (unsigned short*)wpack_ff, 0); fused_pack_launch(P, (hipStream_t)stream); }
   WMZ_LAUNCH_CHECK("wmz_layer_fused_bwd_pack");
   return WMZ_OK;
+}
+
+// The rows of one stream for wmz_fused_pack_table, written to the HOST buffer rows_out (no launch): what the per-stream packers
+// above hand their kernel.  Returns the row count, or -WMZ_ERR_ARG.
+extern "C" int wmz_fused_pack_rows(int kind, const void* const* params, void* dst, long start8, int D, int I, int M, void* rows_out) {
+  const float* const* p = (const float* const*)params;
+  FusedPackRow* rows = (FusedPackRow*)rows_out;
+  const bool have = !p ? false
+      : kind == FUSED_STREAM_FWD ? (p[0] || p[10]) && (!p[0] || (p[2] && p[4] && p[6])) && (!p[10] || (p[8] && p[11] && p[12]))
+      : kind == FUSED_STREAM_BWD_QKV ? p[0] && p[1] && p[2] && p[3] : kind == FUSED_STREAM_BWD_FF && p[4] && p[5] && p[6] && p[7];
+  const char* bad = !(have && dst && rows && start8 >= 0) ? "wmz_fused_pack_rows: bad arguments"
+      : !(D == 256 && I == 128 && M == 256) ? "wmz_fused_pack_rows: built for dim 256 / inner 128 / mlp 256" : nullptr;
+  if (bad != nullptr) { wmz_set_error("%s", bad); return -WMZ_ERR_ARG; }
+  return kind == FUSED_STREAM_FWD ? fused_fwd_rows(rows, p, (unsigned short*)dst, start8)
+       : kind == FUSED_STREAM_BWD_QKV ? fused_bwd_qkv_rows(rows, p, (unsigned short*)dst, start8)
+                                      : fused_bwd_ff_rows(rows, p, (unsigned short*)dst, start8);
 }
 
 extern "C" int wmz_layer_fused_fwd_train(const void* o, const void* x, void* x_out, void* x_out_rowmajor, void* x1_out,
@@ -641,11 +587,7 @@ extern "C" int wmz_layer_fused_fwd_train(const void* o, const void* x, void* x_o
   WMZ_REQUIRE(!(xflags & WMZ_FUSED_XRM_NORMALISED) || (has_tail && x_out_rowmajor && (xflags & WMZ_FUSED_X_OUT_TILED)),
               "wmz_layer_fused_fwd_train: WMZ_FUSED_XRM_NORMALISED needs the tail, x_rm_out and a tiled x_out (the raw stream must survive somewhere)");
   WMZ_REQUIRE(!(xflags & WMZ_FUSED_X1_NORMALISED) || (has_head && x1_out), "wmz_layer_fused_fwd_train: WMZ_FUSED_X1_NORMALISED needs the head and x1_out");
-  FusedParams P;
-  P.o = (const bf16_t*)o; P.x = (const bf16_t*)x; P.xo = (bf16_t*)x_out; P.q = (bf16_t*)q_out; P.kv = (bf16_t*)kv_out;
-  P.wpack = (const char*)wpack; P.vec = vec; P.ntok = ntok; P.eps = eps;
-  P.z = nullptr; P.emb = P.pos_s = P.pos_h = P.pos_w = nullptr; P.S = P.H = P.W = P.num_classes = 0;
-  P.rows_out = P.rows_in = P.row0 = 0;
+  FusedParams P = fused_params(o, x, x_out, q_out, kv_out, wpack, vec, ntok, eps);
   P.xflags = xflags;
   P.x1o = (bf16_t*)x1_out; P.xo_rm = (bf16_t*)x_out_rowmajor; P.kv_combined = 1;
   P.st_ff = ln_ff_stats; P.st_attn = has_tail ? ln_attn_stats : nullptr;
@@ -664,14 +606,11 @@ extern "C" int wmz_embed_qkv_fused_fwd_train(const int64_t* z, const float* emb,
   WMZ_REQUIRE((xflags & ~(WMZ_FUSED_X_OUT_TILED | WMZ_FUSED_XRM_NORMALISED)) == 0 && (xflags == 0 || ((long)S * H * W) % 32 == 0), "wmz_embed_qkv_fused_fwd_train: bad layout flags");
   WMZ_REQUIRE(!(xflags & WMZ_FUSED_XRM_NORMALISED) || (x_out_rowmajor && (xflags & WMZ_FUSED_X_OUT_TILED)),
               "wmz_embed_qkv_fused_fwd_train: WMZ_FUSED_XRM_NORMALISED needs x_out_rowmajor and a tiled x_out");
-  FusedParams P;
-  P.o = nullptr; P.x = nullptr; P.xo = (bf16_t*)x_out; P.q = (bf16_t*)q_out; P.kv = (bf16_t*)kv_out;
-  P.wpack = (const char*)wpack; P.vec = vec; P.ntok = B * S * H * W; P.eps = eps;
-  P.rows_out = P.rows_in = P.row0 = 0;
+  FusedParams P = fused_params(nullptr, nullptr, x_out, q_out, kv_out, wpack, vec, B * S * H * W, eps);
   P.z = z; P.emb = emb; P.pos_s = pos_s; P.pos_h = pos_h; P.pos_w = pos_w; P.S = S; P.H = H; P.W = W; P.num_classes = num_classes;
   P.xflags = xflags;
-  P.x1o = nullptr; P.xo_rm = (bf16_t*)x_out_rowmajor; P.kv_combined = 1;
-  P.st_ff = nullptr; P.st_attn = ln_attn_stats; P.zt = nullptr;
+  P.xo_rm = (bf16_t*)x_out_rowmajor; P.kv_combined = 1;
+  P.st_attn = ln_attn_stats;
   return fused_launch(P, P.ntok, D, I, M, 0, 1, stream);
 }
 
@@ -691,15 +630,9 @@ extern "C" int WMZ_FN(wmz_layer_fused_fwd_planes)(const void* o, const void* x, 
   WMZ_REQUIRE(has_head || has_tail, "wmz_layer_fused_fwd: nothing to do");
   WMZ_REQUIRE(!has_head || (o && x_out), "wmz_layer_fused_fwd: head needs o and x_out");
   WMZ_REQUIRE(!has_tail || (q_out && kv_out), "wmz_layer_fused_fwd: tail needs q_out and kv_out");
-  FusedParams P;
-  P.o = (const bf16_t*)o; P.x = (const bf16_t*)x; P.xo = (bf16_t*)x_out; P.q = (bf16_t*)q_out; P.kv = (bf16_t*)kv_out;
-  P.wpack = (const char*)wpack; P.vec = vec; P.ntok = ntok; P.eps = eps;
-  P.z = nullptr; P.emb = P.pos_s = P.pos_h = P.pos_w = nullptr; P.S = P.H = P.W = P.num_classes = 0;
-  P.rows_out = P.rows_in = P.row0 = 0;
+  FusedParams P = fused_params(o, x, x_out, q_out, kv_out, wpack, vec, ntok, eps);
   if (planes_out != planes_in) { P.rows_out = planes_out * HW; P.rows_in = planes_in * HW; P.row0 = (planes_in - planes_out) * HW; }
   P.xflags = xflags;
-  P.x1o = nullptr; P.xo_rm = nullptr; P.kv_combined = 0;
-  P.st_ff = P.st_attn = nullptr; P.zt = nullptr;
   return fused_launch(P, ntok, D, I, M, has_head, has_tail, stream);
 }
 
@@ -721,15 +654,10 @@ extern "C" int WMZ_FN(wmz_embed_qkv_fused_fwd_planes)(const int64_t* z, const fl
   WMZ_REQUIRE((long)B * S * H * W < (1L << 31), "wmz_embed_qkv_fused_fwd: token count overflows int");
   WMZ_REQUIRE(z && emb && pos_s && pos_h && pos_w && x_out && q_out && kv_out && wpack && vec, "wmz_embed_qkv_fused_fwd: null tensor");
   WMZ_REQUIRE(B > 0 && S > 0 && H > 0 && W > 0 && num_classes > 0, "wmz_embed_qkv_fused_fwd: bad shape");
-  FusedParams P;
-  P.o = nullptr; P.x = nullptr; P.xo = (bf16_t*)x_out; P.q = (bf16_t*)q_out; P.kv = (bf16_t*)kv_out;
-  P.wpack = (const char*)wpack; P.vec = vec; P.ntok = B * planes_out * H * W; P.eps = eps;
-  P.rows_out = P.rows_in = P.row0 = 0;
+  FusedParams P = fused_params(nullptr, nullptr, x_out, q_out, kv_out, wpack, vec, B * planes_out * H * W, eps);
   if (planes_out != S) { P.rows_out = planes_out * H * W; P.rows_in = S * H * W; P.row0 = (S - planes_out) * H * W; }
   P.z = z; P.emb = emb; P.pos_s = pos_s; P.pos_h = pos_h; P.pos_w = pos_w; P.S = S; P.H = H; P.W = W; P.num_classes = num_classes;
   P.xflags = xflags;
-  P.x1o = nullptr; P.xo_rm = nullptr; P.kv_combined = 0;
-  P.st_ff = P.st_attn = nullptr; P.zt = nullptr;
   return fused_launch(P, P.ntok, D, I, M, 0, 1, stream);
 }
 

@@ -8,7 +8,7 @@ from . import _lib as L
 
 D_, I_, M_ = 256, 128, 256
 _PAD = 4 * 16384        # >= RING-1 slabs the kernel's LDS-DMA prefetch runs past the last real slab
-MC_ = 32
+_PACK_FWD, _PACK_BWD_QKV, _PACK_BWD_FF, _PACK_ROWS_MAX = 0, 1, 2, 20   # wmz_fused_pack_rows: stream kinds, most rows it writes (include/wmz.h)
 
 
 def _pack_w(w):
@@ -161,33 +161,48 @@ def _chain_pieces(w, pad_value=0):
     return t
 
 
+def _chain_fwd_stages(p, D, I, M, MC):
+    """The weight stages of one chain forward launch (csrc/layer_chain.hip) in consumption order, as (weight, LayerNorm weight folded
+    into its columns | None, piece count | None: every piece, padded to whole slabs): to_out | MC-wide feed-forward chunks (W1' rows,
+    then W2 columns; no padding inside a chunk: its two GEMMs share slabs) | q | k | v.  p: the boundary's fourteen operands (_fourteen)
+    -- anything that slices like a matrix: the parameters' values (_chain_pack) or their index matrices (ChainPackSet)."""
+    wout, _, g2, _, w1, _, w2, _, g1, _, wq, wk, wv, _ = p
+    if wout is not None:
+        yield wout, None, None
+        for c in range(M // MC):
+            yield w1[c * MC:(c + 1) * MC], g2, (MC // 16) * (D // 32)
+            yield w2[:, c * MC:(c + 1) * MC], None, (D // 16) * (MC // 32)
+    if wq is not None:
+        yield wq, None, None
+        yield wk, g1, None
+        yield wv, g1, None
+
+
+def _chain_vec_slots(p, D, I, M):
+    """The vector block of the same launch, bout | b1' | b2 | bk' | bv' with the LayerNorm biases folded in (b1' = b1 + W1 be2;
+    to_k / to_v likewise with the next layer's norm), as (first element, bias | None, (W, beta) | None) per slot that is present:
+    slot = bias + W @ beta."""
+    wout, bout, _, be2, w1, b1, _, b2, _, be1, wq, wk, wv, bv = p
+    if wout is not None:
+        yield 0, bout, None
+        yield D, b1, (w1, be2)
+        yield D + M, b2, None
+    if wq is not None:
+        yield 2 * D + M, None, (wk, be1)
+        yield 2 * D + M + I, bv, (wv, be1)
+
+
 def _chain_pack(head, tail, D, I, M, MC, dt=torch.bfloat16):
-    """(wpack in dt -- bf16, or half for the _f16 unit --, vec fp32) for one launch of wmz_layer_chain_fwd_planes: stages to_out | MC-wide feed-forward chunks (W1'
-    rows, then W2 columns) | q | k | v, LayerNorm affines folded in (W1' = W1 diag(g2), b1' = b1 + W1 be2; to_k / to_v likewise
-    with the next layer's norm); vec = bout | b1' | b2 | bk' | bv'.  Cached per parameter version."""
+    """(wpack in dt -- bf16, or half for the _f16 unit --, vec fp32) for one launch of wmz_layer_chain_fwd_planes: the stages of
+    _chain_fwd_stages with the LayerNorm weights folded in (W1' = W1 diag(g2), ..) and the vector block of _chain_vec_slots.
+    Cached per parameter version."""
     def build(*ps):
-        ps = [p.detach().float() for p in ps]
-        dev = ps[0].device
-        parts = []
-        vec = torch.zeros(2 * D + M + 2 * I, dtype=torch.float32, device=dev)
-        if head is not None:
-            wout, bout, g2, be2, w1, b1, w2, b2 = ps[:8]
-            parts.append(_chain_pieces(wout))
-            w1f = w1 * g2[None, :]
-            vec[:D] = bout
-            vec[D:D + M] = b1 + w1 @ be2
-            vec[D + M:2 * D + M] = b2
-            for c in range(M // MC):
-                parts.append(_chain_pieces(w1f[c * MC:(c + 1) * MC]))
-                parts[-1] = parts[-1][:(MC // 16) * (D // 32)]                   # (no padding inside a chunk: its two GEMMs share slabs)
-                parts.append(_chain_pieces(w2[:, c * MC:(c + 1) * MC])[:(D // 16) * (MC // 32)])
-        if tail is not None:
-            g1, be1, wq, wk, wv, bv = ps[-6:]
-            parts.append(_chain_pieces(wq))
-            parts.append(_chain_pieces(wk * g1[None, :]))
-            parts.append(_chain_pieces(wv * g1[None, :]))
-            vec[2 * D + M:2 * D + M + I] = wk @ be1
-            vec[2 * D + M + I:] = bv + wv @ be1
+        p = _fourteen([t.detach().float() for t in ps], head, tail)
+        vec = torch.zeros(2 * D + M + 2 * I, dtype=torch.float32, device=ps[0].device)
+        parts = [_chain_pieces(w if g is None else w * g[None, :])[:n] for w, g, n in _chain_fwd_stages(p, D, I, M, MC)]
+        for o, b, mv in _chain_vec_slots(p, D, I, M):
+            v = b if mv is None else (mv[0] @ mv[1] if b is None else b + mv[0] @ mv[1])
+            vec[o:o + v.numel()] = v
         stream = torch.cat(parts, 0)
         sp = L.lib().wmz_layer_chain_slab_pieces()
         assert stream.shape[0] % sp == 0
@@ -252,7 +267,6 @@ class ChainPackSet:
         def cols(vec_p, like):                           # index matrix of gamma[k] broadcast over the rows of a [N, K] weight
             return idx(vec_p)[None, :].expand(like.shape[0], -1)
         sp = L.lib().wmz_layer_chain_slab_pieces()
-        one = torch.full((1, 1), -1, dtype=torch.int64, device=dev)                   # scale index -1 = no scale
 
         def pieces(w_idx, s_idx=None, n=None):
             """(source indices, scale indices) of the pieces of an index matrix, optionally only its first n pieces."""
@@ -272,27 +286,18 @@ class ChainPackSet:
             pos += w.numel()
         nvec = 2 * D + M + 2 * I
         vidx = torch.full((nl + 1, nvec), -1, dtype=torch.int64, device=dev)
+        folded = {}                                      # first element of a vec slot -> [(launch, W, beta)]: slot += W @ beta
         for l in range(nl + 1):
             head = layers[l - 1] if l > 0 else None
             tail = layers[l] if l < nl else None
-            parts = []
-            if head is not None:
-                attn, ff = head
-                w1, w2 = idx(ff.fn.net[0].weight), idx(ff.fn.net[3].weight)
-                g1 = cols(ff.norm.weight, w1)
-                parts.append(pieces(idx(attn.fn.to_out[0].weight)))
-                for c in range(M // MC):
-                    parts.append(pieces(w1[c * MC:(c + 1) * MC], g1[c * MC:(c + 1) * MC], (MC // 16) * (D // 32)))
-                    parts.append(pieces(w2[:, c * MC:(c + 1) * MC], None, (D // 16) * (MC // 32)))
-                vidx[l, :D] = idx(attn.fn.to_out[0].bias)
-                vidx[l, D:D + M] = idx(ff.fn.net[0].bias)
-                vidx[l, D + M:2 * D + M] = idx(ff.fn.net[3].bias)
-            if tail is not None:
-                an = tail[0]
-                wk, wv = idx(an.fn.to_k.weight), idx(an.fn.to_v.weight)
-                parts += [pieces(idx(an.fn.to_q.weight)), pieces(wk, cols(an.norm.weight, wk)), pieces(wv, cols(an.norm.weight, wv))]
-                vidx[l, 2 * D + M + I:] = idx(an.fn.to_v.bias)
-            add(('fwd', l), parts)
+            p = _fourteen(_boundary_params(head, tail), head, tail)
+            add(('fwd', l), [pieces(w, None if g is None else g[None, :].expand(w.shape[0], -1), n)
+                             for w, g, n in _chain_fwd_stages([t if t is None else idx(t) for t in p], D, I, M, MC)])
+            for o, b, mv in _chain_vec_slots(p, D, I, M):
+                if b is not None:
+                    vidx[l, o:o + b.numel()] = idx(b)
+                if mv is not None:
+                    folded.setdefault(o, []).append((l,) + mv)
         for l, (attn, ff) in enumerate(layers):
             # backward streams: the TRANSPOSED weights, the norms' weights folded in on the side that faces the normalised rows
             w1, w2 = idx(ff.fn.net[0].weight), idx(ff.fn.net[3].weight)
@@ -330,19 +335,16 @@ class ChainPackSet:
             st = o[1] - o[0] if len(o) > 1 else 0
             if any(o[i + 1] - o[i] != st for i in range(len(o) - 1)):
                 return None
-            n = ps[0].numel()
             inner = (shape[1], 1) if len(shape) == 2 else (1, 1)
             return torch.as_strided(self.flat, (len(ps),) + tuple(shape), (st,) + inner, o[0])
-        W1 = strided([ff.fn.net[0].weight for _, ff in layers], (M, D))
-        bff = strided([ff.norm.bias for _, ff in layers], (D, 1))
-        Wk = strided([a.fn.to_k.weight for a, _ in layers], (I, D))
-        Wv = strided([a.fn.to_v.weight for a, _ in layers], (I, D))
-        bat = strided([a.norm.bias for a, _ in layers], (D, 1))
-        if any(t is None for t in (W1, bff, Wk, Wv, bat)):
-            # (frozen or re-ordered layers: no strided view of the arena holds them -- the caller trains op by op instead)
-            raise ChainLayoutError('the transformer layers are not laid out at one stride in the parameter arena')
-        self._mv = [(W1, bff, self.vec[1:, D:D + M]), (Wk, bat, self.vec[:nl, 2 * D + M:2 * D + M + I]),
-                    (Wv, bat, self.vec[:nl, 2 * D + M + I:])]
+        self._mv = []
+        for o, terms in sorted(folded.items()):
+            ls, Ws, betas = zip(*terms)
+            W, beta = strided(Ws, tuple(Ws[0].shape)), strided(betas, (betas[0].numel(), 1))
+            if W is None or beta is None:
+                # (frozen or re-ordered layers: no strided view of the arena holds them -- the caller trains op by op instead)
+                raise ChainLayoutError('the transformer layers are not laid out at one stride in the parameter arena')
+            self._mv.append((W, beta, self.vec[ls[0]:ls[-1] + 1, o:o + Ws[0].shape[0]]))
         self.refresh()
 
     def refresh(self):
@@ -449,34 +451,41 @@ def _boundary_params(head, tail):
     return params
 
 
+def _fourteen(ps, head, tail):
+    """_boundary_params' list (or one value per parameter of it) spread over the fourteen slots of wmz_layer_fused_pack -- wout, bout,
+    g2, be2, w1, b1, w2, b2 | g1, be1, wq, wk, wv, bv --, an absent head's or tail's None."""
+    return (list(ps[:8]) if head is not None else [None] * 8) + (list(ps[-6:]) if tail is not None else [None] * 6)
+
+
 def _layer_pack(head, tail, dt=torch.bfloat16):
     """head / tail: (attn PreNorm, ff PreNorm) of the layer whose to_out+FF run, and of the layer whose q|k|v run.
-    Returns (wpack bf16, vec fp32) built by ONE launch of wmz_layer_fused_pack from the fp32 parameters: the weights in
-    the kernel's streaming order (see _pack_w for the element order; W1 rows one chunk ahead of the W2 columns:
-    W1[0], W1[1], W2[0], W1[2], W2[1], .., W1[7], W2[6], W2[7]) with the LayerNorm affines folded in (W1' = W1 diag(g2),
-    b1' = b1 + W1 be2; same for to_k / to_v with the next layer's norm), and bout | b1' | b2 | bk' | bv'."""
+    Returns (wpack bf16, vec fp32) built by ONE call of wmz_layer_fused_pack from the fp32 parameters: the weights in the
+    kernel's streaming order -- which blocks and in which order: csrc/fused_pack_rows.h; a block's element order: _pack_w --
+    with the LayerNorm affines folded in (W1' = W1 diag(g2), b1' = b1 + W1 be2; same for to_k / to_v with the next layer's
+    norm), and bout | b1' | b2 | bk' | bv'."""
     def build(*ps):
         ps = [p.detach() for p in ps]
         assert all(p.dtype == torch.float32 and p.is_contiguous() for p in ps)
-        hp = ps[:8] if head is not None else [None] * 8
-        tp = ps[-6:] if tail is not None else [None] * 6
         nw = (D_ * I_ + 2 * M_ * D_ if head is not None else 0) + (3 * I_ * D_ if tail is not None else 0)
         dev = ps[0].device
         wpack = torch.empty(nw + _PAD // 2, dtype=dt, device=dev)
         vec = torch.empty(2048, dtype=torch.float32, device=dev)
-        L.call(L.half_form('wmz_layer_fused_pack', dt), *[L.ptr(t) for t in hp], *[L.ptr(t) for t in tp], L.ptr(wpack), L.ptr(vec),
-               D_, I_, M_, L.stream())
+        L.call(L.half_form('wmz_layer_fused_pack', dt), *map(L.ptr, _fourteen(ps, head, tail)), L.ptr(wpack), L.ptr(vec), D_, I_, M_,
+               L.stream())
         return wpack, vec
     return _cast.cached(_boundary_params(head, tail), L.half_form('fusedpack', dt), build)
+
+
+def _layer_bwd_params(attn, ff):
+    """The parameters a layer's two backward streams read, in wmz_layer_fused_bwd_pack's order: wq, wk, wv, g1, wout, w1, g2, w2."""
+    a, f = attn.fn, ff.fn
+    return [a.to_q.weight, a.to_k.weight, a.to_v.weight, attn.norm.weight, a.to_out[0].weight, f.net[0].weight,
+            ff.norm.weight, f.net[3].weight]
 
 
 def _layer_pack_bwd(attn, ff):
     """(wpack_qkv, wpack_ff): the TRANSPOSED weight streams of one layer for wmz_qkv_fused_bwd / wmz_ff_fused_bwd, built by
     wmz_layer_fused_bwd_pack from the fp32 parameters (cached per parameter version like the forward streams)."""
-    a, f = attn.fn, ff.fn
-    params = [a.to_q.weight, a.to_k.weight, a.to_v.weight, attn.norm.weight, a.to_out[0].weight, f.net[0].weight,
-              ff.norm.weight, f.net[3].weight]
-
     def build(*ps):
         ps = [p.detach() for p in ps]
         assert all(p.dtype == torch.float32 and p.is_contiguous() for p in ps)
@@ -485,7 +494,7 @@ def _layer_pack_bwd(attn, ff):
         wf = torch.empty(2 * M_ * D_ + D_ * I_ + _PAD // 2, dtype=torch.bfloat16, device=dev)
         L.call('wmz_layer_fused_bwd_pack', *[L.ptr(t) for t in ps], L.ptr(wq), L.ptr(wf), D_, I_, M_, L.stream())
         return wq, wf
-    return _cast.cached(params, 'fusedpackbwd', build)
+    return _cast.cached(_layer_bwd_params(attn, ff), 'fusedpackbwd', build)
 
 
 class PackSet:
@@ -506,64 +515,42 @@ class PackSet:
         return [p for p in self.tr.parameters()]
 
     def _build(self):
+        import ctypes
         import numpy as np
         layers = list(self.tr.layers)
         dev = layers[0][0].norm.weight.device
         rows, jobs, self.entries = [], [], []
-        state = {'g8': 0}
+        self.total8 = 0
 
-        def ptr(t, off=0):
-            return 0 if t is None else t.data_ptr() + 4 * off
-
-        def block(dst, doff, w, woff, rs, ks, N, K, gn, gk, gamma, rgamma):
-            rows.append([ptr(w, woff), rs, ks, N, K, gn, gk, ptr(gamma), ptr(rgamma), dst.data_ptr() + 2 * doff, state['g8']])
-            state['g8'] += N * K // 8
-            return doff + N * K
+        def stream(kind, params, nw):
+            """A zeroed buffer for a stream of nw elements + padding; its rows (csrc/fused_pack_rows.h) go behind those so far."""
+            dst = torch.zeros(nw + _PAD // 2, dtype=torch.bfloat16, device=dev)
+            buf = np.zeros((_PACK_ROWS_MAX, 11), dtype=np.int64)
+            n = L.lib().wmz_fused_pack_rows(kind, (ctypes.c_void_p * len(params))(*map(L.ptr, params)), dst.data_ptr(), self.total8,
+                                            D_, I_, M_, buf.ctypes.data)
+            if n <= 0:
+                raise L.WmzError(f'wmz_fused_pack_rows failed (code {-n}): {L.lib().wmz_last_error().decode()}')
+            rows.extend(buf[:n].tolist())
+            self.total8 += nw // 8
+            assert rows[-1][10] + rows[-1][3] * rows[-1][4] // 8 == self.total8        # the last block ends where the stream does
+            return dst
 
         bounds = [(None, layers[0])] + [(layers[l], layers[l + 1] if l + 1 < len(layers) else None) for l in range(len(layers))]
         for head, tail in bounds:
             nw = (D_ * I_ + 2 * M_ * D_ if head is not None else 0) + (3 * I_ * D_ if tail is not None else 0)
-            wpack = torch.zeros(nw + _PAD // 2, dtype=torch.bfloat16, device=dev)
-            vec = torch.zeros(2048, dtype=torch.float32, device=dev)
-            params, off = _boundary_params(head, tail), 0
-            job = [0] * 10
-            if head is not None:
-                wout, bout, g2, be2, w1, b1, w2, b2 = params[:8]
-                off = block(wpack, off, wout, 0, I_, 1, D_, I_, D_, I_, None, None)
-                off = block(wpack, off, w1, 0, D_, 1, MC_, D_, MC_, D_, g2, None)
-                for c in range(1, M_ // MC_):
-                    off = block(wpack, off, w1, c * MC_ * D_, D_, 1, MC_, D_, MC_, D_, g2, None)
-                    off = block(wpack, off, w2, (c - 1) * MC_, M_, 1, D_, MC_, D_, MC_, None, None)
-                off = block(wpack, off, w2, (M_ // MC_ - 1) * MC_, M_, 1, D_, MC_, D_, MC_, None, None)
-                job[0:5] = [ptr(bout), ptr(b1), ptr(w1), ptr(be2), ptr(b2)]
-            if tail is not None:
-                g1, be1, wq, wk, wv, bv = params[-6:]
-                off = block(wpack, off, wq, 0, D_, 1, I_, D_, I_, D_, None, None)
-                off = block(wpack, off, wk, 0, D_, 1, I_, D_, I_, D_, g1, None)
-                off = block(wpack, off, wv, 0, D_, 1, I_, D_, I_, D_, g1, None)
-                job[5:9] = [ptr(wk), ptr(wv), ptr(be1), ptr(bv)]
-            assert off == nw
-            job[9] = vec.data_ptr()
-            jobs.append(job)
+            params = _boundary_params(head, tail)
+            p = _fourteen(params, head, tail)
+            wpack, vec = stream(_PACK_FWD, p, nw), torch.zeros(2048, dtype=torch.float32, device=dev)
+            # the vec job: bout, b1, w1, be2, b2, wk, wv, be1, bv of the fourteen (0: absent), vec
+            jobs.append([0 if p[i] is None else p[i].data_ptr() for i in (1, 5, 4, 3, 7, 11, 12, 9, 13)] + [vec.data_ptr()])
             self.entries.append((tuple(params), 'fusedpack', (wpack, vec)))
         if self.backward:
             for attn, ff in layers:
-                a, f = attn.fn, ff.fn
-                wq, wk, wv, g1 = a.to_q.weight, a.to_k.weight, a.to_v.weight, attn.norm.weight
-                wout, w1, g2, w2 = a.to_out[0].weight, f.net[0].weight, ff.norm.weight, f.net[3].weight
-                sq = torch.zeros(3 * D_ * I_ + _PAD // 2, dtype=torch.bfloat16, device=dev)
-                sf = torch.zeros(2 * M_ * D_ + D_ * I_ + _PAD // 2, dtype=torch.bfloat16, device=dev)
-                off = block(sq, 0, wk, 0, 1, D_, D_, I_, 128, 128, None, g1)
-                off = block(sq, off, wv, 0, 1, D_, D_, I_, 128, 128, None, g1)
-                off = block(sq, off, wq, 0, 1, D_, D_, I_, 128, 128, None, None)
-                off = 0
-                for c in range(M_ // 32):
-                    off = block(sf, off, w2, c * 32, 1, M_, 32, D_, 32, 128, None, None)
-                off = block(sf, off, w1, 0, 1, D_, D_, M_, 128, 32, None, g2)
-                off = block(sf, off, wout, 0, 1, I_, I_, D_, 128, 128, None, None)
-                self.entries.append(((wq, wk, wv, g1, wout, w1, g2, w2), 'fusedpackbwd', (sq, sf)))
+                params = _layer_bwd_params(attn, ff)
+                sq = stream(_PACK_BWD_QKV, params, 3 * D_ * I_)
+                sf = stream(_PACK_BWD_FF, params, 2 * M_ * D_ + D_ * I_)
+                self.entries.append((tuple(params), 'fusedpackbwd', (sq, sf)))
         self.nblk = len(rows)
-        self.total8 = state['g8']
         rows.append([0] * 10 + [self.total8])
         self.rows = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev)
         self.jobs = torch.from_numpy(np.asarray(jobs, dtype=np.int64)).to(dev)
