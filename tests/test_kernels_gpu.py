@@ -3,6 +3,7 @@ vectors captured from the reference.  Tolerances are written next to each check.
 import pytest
 import torch
 
+import gemm_bounds
 from conftest import load_golden, sub
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +27,18 @@ def dev(t):
 def rel(a, b):
     a, b = a.float().cpu(), b.float().cpu()
     return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+BOUND_MAX_ROWS = 20000      # the element-wise fp64 bound (tests/gemm_bounds.py) next to rel() where its reference takes a second or two
+
+
+def wgrad_within_bound(tag, dc, a, dw, db, init, binit, over, ln=None):
+    """every element of a weight gradient (and its bias gradient) within its derived bound of the fp64 reference"""
+    rw, ew, rb, eb = gemm_bounds.wgrad_ref(dc, a, None if over else init, None if over else binit, ln=ln)
+    worst = gemm_bounds.check(tag + ' dw', dw.cpu(), rw, ew)
+    if db is not None:
+        worst = max(worst, gemm_bounds.check(tag + ' dbias', db.cpu(), rb, eb))
+    print(f'[bound] {tag}: {worst:.3f}')
 
 
 # ---------------------------------------------------------------------------------------------- attention
@@ -191,7 +204,7 @@ def test_wgrad_batch_with_per_problem_layernorm(ops, M, dtype):
     case; few rows take the unsplit form (every tile one workgroup, added straight into dW, accumulate and overwrite)."""
     torch.manual_seed(43)
     shapes = [(512, 512, True), (1536, 512, True), (512, 1024, False), (1024, 512, False), (128, 264, False)]
-    probs, refs, singles = [], [], []
+    probs, refs, singles, host = [], [], [], []
     for N, K, ln in shapes:
         dc = (torch.randn(M, N) * 0.3).to(dtype)
         a = (torch.randn(M, K) * 1.3 + 0.2).to(dtype)
@@ -203,6 +216,7 @@ def test_wgrad_batch_with_per_problem_layernorm(ops, M, dtype):
             an = an.bfloat16().float()                      # the prologue rounds LN(a) to the operand type
         over = N == 1024
         refs.append(((0 if over else init) + dc.float().t() @ an, (0 if over else binit) + dc.float().sum(0)))
+        host.append((dc, a, init, binit, over, (g, b) if ln else None))
         dcd, ad = dev(dc), dev(a)
         stats = ops.layernorm_stats(ad, 1e-5) if ln else (None, None)
         dw, db = dev(init).clone(), dev(binit).clone()
@@ -213,9 +227,12 @@ def test_wgrad_batch_with_per_problem_layernorm(ops, M, dtype):
         singles.append((dw1, db1))
     ops.linear_wgrad_batch_ln(probs)
     tol = 3e-5 if dtype == torch.float32 else 2e-3
-    for q, (rw, rb), (sw, sb) in zip(probs, refs, singles):
+    for q, (rw, rb), (sw, sb), (dc, a, init, binit, over, ln) in zip(probs, refs, singles, host):
         assert rel(q['dw'], rw) < tol and rel(q['dbias'], rb) < tol
         assert rel(q['dw'], sw.cpu()) < 1e-5 and rel(q['dbias'], sb.cpu()) < 1e-5
+        if M <= BOUND_MAX_ROWS:
+            wgrad_within_bound(f'batch_ln {q["N"]}x{q["K"]} M={M}', dc, a, q['dw'], q['dbias'], init, binit, over, ln)
+            wgrad_within_bound(f'single {q["N"]}x{q["K"]} M={M}', dc, a, sw, sb, init, binit, over, ln)
 
 
 @pytest.mark.parametrize('M', [65536, 4099, 300])
@@ -227,22 +244,25 @@ def test_wgrad_batch_on_256_wide_tiles(ops, M):
     torch.manual_seed(47)
     shapes = [(256, 256, True, False), (256, 256, True, True), (256, 128, True, False), (128, 256, False, False), (512, 256, True, False),
               (256, 384, False, True)]
-    probs, refs, singles = [], [], []
+    probs, refs, singles, host = [], [], [], []
     for N, K, bias, over in shapes:
         dc = (torch.randn(M, N) * 0.3).bfloat16()
         a = (torch.randn(M, K) * 1.1 + 0.1).bfloat16()
         init, binit = torch.randn(N, K), torch.randn(N)
         refs.append(((0 if over else init) + dc.float().t() @ a.float(), (0 if over else binit) + dc.float().sum(0)))
+        host.append((dc, a, init, binit))
         dcd, ad = dev(dc), dev(a)
         probs.append((dcd, ad, dev(init).clone(), dev(binit).clone() if bias else None, over))
         dw1, db1 = dev(init).clone(), dev(binit).clone() if bias else None
         ops.linear_wgrad(dcd, ad, dw1, db1, overwrite=over)
         singles.append((dw1, db1))
     ops.linear_wgrad_batch(probs)
-    for (dcd, ad, dw, db, over), (rw, rb), (sw, sb) in zip(probs, refs, singles):
+    for (dcd, ad, dw, db, over), (rw, rb), (sw, sb), (dc, a, init, binit) in zip(probs, refs, singles, host):
         assert rel(dw, rw) < 2e-3 and rel(dw, sw) < 1e-5
         if db is not None:
             assert rel(db, rb) < 2e-3 and rel(db, sb) < 1e-5
+        if M <= BOUND_MAX_ROWS:
+            wgrad_within_bound(f'batch256 {dw.shape[0]}x{dw.shape[1]} M={M}', dc, a, dw, db, init, binit, over)
 
 
 @pytest.mark.parametrize('M', [65536, 8231])
@@ -253,18 +273,21 @@ def test_wgrad_batch_on_256_wide_tiles_partial_columns(ops, M):
     the out-of-range chunks are fetched from the tile's first chunk and must not reach the result; ragged M on top."""
     torch.manual_seed(53)
     shapes = [(128, 384, True, False), (384, 128, False, True), (200, 264, True, False), (384, 512, True, True), (264, 200, True, False)]
-    probs, refs = [], []
+    probs, refs, host = [], [], []
     for N, K, bias, over in shapes:
         dc = (torch.randn(M, N) * 0.3).bfloat16()
         a = (torch.randn(M, K) * 1.1 + 0.1).bfloat16()
         init, binit = torch.randn(N, K), torch.randn(N)
         refs.append(((0 if over else init) + dc.float().t() @ a.float(), (0 if over else binit) + dc.float().sum(0)))
+        host.append((dc, a, init, binit))
         probs.append((dev(dc), dev(a), dev(init).clone(), dev(binit).clone() if bias else None, over))
     ops.linear_wgrad_batch(probs)
-    for (dcd, ad, dw, db, over), (rw, rb) in zip(probs, refs):
+    for (dcd, ad, dw, db, over), (rw, rb), (dc, a, init, binit) in zip(probs, refs, host):
         assert torch.isfinite(dw).all() and rel(dw, rw) < 2e-3
         if db is not None:
             assert rel(db, rb) < 2e-3
+        if M <= BOUND_MAX_ROWS:
+            wgrad_within_bound(f'batch256 partial {dw.shape[0]}x{dw.shape[1]} M={M}', dc, a, dw, db, init, binit, over)
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])

@@ -457,17 +457,43 @@ static int g_linear_dma = 1;
 extern "C" int wmz_debug_linear_knobs(int dma) { g_linear_dma = dma; return WMZ_OK; }      // (development A/B: 0 = the register-staged loop)
 #endif
 
+// Which linear_kernel instantiation a problem runs on: the row-tile height and the K loop.  Host arithmetic only -- the launch and
+// the probe wmz_debug_linear_route (csrc/wmz_debug.h) both ask here, so a test that names a tile height names the one launched.
+struct LinRoute { bool small; int bm; int dma; };
+static LinRoute linear_route(const LinParams& P, bool op16, bool ln, bool gin, int dma_knob) {
+  LinRoute r;
+  // small-M GEMMs (the last-frame logits: M = B*H*W; config 5's 3 072 tokens per GPU): 64-row tiles, so that the grid covers
+  // the chip (a 16-bit output then leaves by per-lane stores: fine at these sizes)
+  r.small = (long)wmz_cdiv(P.M, 128) * wmz_cdiv(P.N, BN) < (P.out_f32 ? 192 : 320) && (op16 || (!ln && !gin));
+  r.bm = r.small ? 64 : 128;
+  const uintptr_t al = (uintptr_t)P.A | (uintptr_t)P.Wt | (uintptr_t)(P.lda * 2) | (uintptr_t)(P.bstride * 2);
+  r.dma = (r.small && op16 && !ln && !gin && P.K % 64 == 0 && (al & 15) == 0 && dma_knob) ? 1 : 0;
+  return r;
+}
+
+#ifndef WMZ_OP16_F16
+// (the half unit is this source with the operand format switched: one probe answers for both; the development knob above
+//  belongs to the bfloat16 / fp32 unit alone, the half unit always runs with it on)
+extern "C" int wmz_debug_linear_route(const void* A, long lda, const void* Wt, long block_stride, int M, int N, int K, int prologue,
+                                      int out_f32, int dtype) {
+  WMZ_REQUIRE(M > 0 && N > 0 && K > 0 && prologue >= 0 && prologue <= 2, "wmz_debug_linear_route: bad shape or prologue");
+  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16 || dtype == WMZ_F16, "wmz_debug_linear_route: bad dtype %d", dtype);
+  LinParams P = {};
+  P.A = A; P.lda = lda; P.Wt = Wt; P.bstride = block_stride; P.M = M; P.N = N; P.K = K; P.out_f32 = out_f32;
+  const LinRoute r = linear_route(P, dtype != WMZ_F32, prologue == 1, prologue == 2, dtype == WMZ_F16 ? 1 : g_linear_dma);
+  return r.bm | (r.dma << 8);
+}
+#endif
+
 static int linear_launch(LinParams P, const float* ln_gamma, int flags, int dtype, hipStream_t st) {
   const bool ln = ln_gamma != nullptr;
   const bool gin = (flags & WMZ_LIN_GELU_IN) != 0;
   WMZ_REQUIRE(!(ln && gin), "wmz_linear_fwd: LayerNorm and GELU prologues are exclusive");
   P.nbn = wmz_cdiv(P.N, BN);
-  // small-M GEMMs (the last-frame logits: M = B*H*W; config 5's 3 072 tokens per GPU): 64-row tiles, so that the grid covers
-  // the chip (a 16-bit output then leaves by per-lane stores: fine at these sizes)
-  const bool small = (long)wmz_cdiv(P.M, 128) * P.nbn < (P.out_f32 ? 192 : 320) && (dtype == kOp16Dtype || (!ln && !gin));
-  const int bm = small ? 64 : 128;
-  const uintptr_t al = (uintptr_t)P.A | (uintptr_t)P.Wt | (uintptr_t)(P.lda * 2) | (uintptr_t)(P.bstride * 2);
-  P.dma = (small && dtype == kOp16Dtype && !ln && !gin && P.K % 64 == 0 && (al & 15) == 0 && g_linear_dma) ? 1 : 0;
+  const LinRoute route = linear_route(P, dtype == kOp16Dtype, ln, gin, g_linear_dma);
+  const bool small = route.small;
+  const int bm = route.bm;
+  P.dma = route.dma;
   dim3 grid((unsigned)(wmz_cdiv(P.M, bm) * P.nbn)), block(NT);
   if (dtype == kOp16Dtype) {
     if (small && ln) hipLaunchKernelGGL((linear_kernel<bf16_t, 1, 64>), grid, block, 0, st, P);

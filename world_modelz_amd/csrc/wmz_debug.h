@@ -26,6 +26,13 @@ int wmz_debug_conv_knobs(int skew, int dbg);
 /* development knob of the nn.Linear kernel (csrc/linear_fwd.hip): dma = 0 runs the small-M GEMMs on the register-staged K loop
  * instead of the LDS-DMA ring (A/B timing; same results). */
 int wmz_debug_linear_knobs(int dma);
+/* Which instantiation of the nn.Linear kernel a problem takes (kernel-level tests name the tile they cover through this): the
+ * host-side decision of the launch itself, asked without launching anything or touching a device -- A and Wt are looked at as
+ * addresses only (their alignment decides the K loop).  prologue: 0 none, 1 LayerNorm, 2 GELU-in; block_stride: 0, or the block
+ * stride of wmz_linear_fwd_blocked; dtype: WMZ_F32 / WMZ_BF16 / WMZ_F16.  Returns the row-tile height (64 or 128), plus 256 when
+ * the K loop is the LDS-DMA ring; the wmz_debug_linear_knobs setting counts for bf16. */
+int wmz_debug_linear_route(const void* A, long lda, const void* Wt, long block_stride, int M, int N, int K, int prologue,
+                           int out_f32, int dtype);
 
 /* Timeline probe for captured steps: one thread writes the device's constant-rate wall clock (wall_clock64: 100 MHz) into
  * buf[slot] (device int64) when the launch executes on `stream` -- a marker between the phases of a hipGraph replay, where a

@@ -23,6 +23,13 @@ def _rows(t):
     return t, flat.shape[0], C
 
 
+def _out_rows(out, M, dtype):
+    """A caller's output (out=): [M rows, ...] with uniform row stride, written in place -> (tensor, row stride)."""
+    t, Mo, ld = _rows(out)
+    assert Mo == M and t.data_ptr() == out.data_ptr() and out.dtype == dtype
+    return out, ld
+
+
 def local3d_attention_fwd(q, k, v, extents, heads, need_lse=False, logits_dbg=False, general=False):
     """q, k, v: [B,S,H,W,heads*dh] (last dim contiguous, uniform row stride).  Returns (out, lse, logits).
     general: take the general kernel even where the 16-wide-plane fast path applies (parity tests)."""
@@ -85,39 +92,57 @@ KEEP_NORM_MIN_ROWS = 16384    # from here on the training forward's PreNorm GEMM
                               # a plain operand and take the 256-wide tiles (fewer rows: they sit on the graph's side branch anyway)
 
 
-def linear_fwd_train(a, weight, bias, ln, ln_eps=1e-5, ln_stats=None, want_gelu=False, want_norm=False):
+def linear_fwd_train(a, weight, bias, ln, ln_eps=1e-5, ln_stats=None, want_gelu=False, want_norm=False, out=None):
     """The training forward's PreNorm GEMM (wmz_linear_fwd_train): c = LN(a) @ weight^T + bias, and on request h = GELU(c) and
-    an = LN(a) as the GEMM consumed it -> (c, h | None, an | None)."""
+    an = LN(a) as the GEMM consumed it -> (c, h | None, an | None).  out = (c, h | None, an | None): write into these (row-strided
+    views allowed) instead of allocating."""
     K = a.shape[-1]
     N = weight.shape[0]
     dt = L.dtype_code(a.dtype)
     assert weight.dtype == a.dtype and weight.is_contiguous() and weight.shape[1] == K and ln is not None
     a, M, lda = _rows(a)
     lead = a.shape[:-1]
-    c = torch.empty(lead + (N,), dtype=a.dtype, device=a.device)
-    h = torch.empty(lead + (N,), dtype=a.dtype, device=a.device) if want_gelu else None
-    an = torch.empty(lead + (K,), dtype=a.dtype, device=a.device) if want_norm else None
+    ldc = ldh = N
+    ldan = K
+    if out is not None:
+        c, h, an = out
+        assert (h is not None) == want_gelu and (an is not None) == want_norm
+        c, ldc = _out_rows(c, M, a.dtype)
+        if h is not None:
+            h, ldh = _out_rows(h, M, a.dtype)
+        if an is not None:
+            an, ldan = _out_rows(an, M, a.dtype)
+    else:
+        c = torch.empty(lead + (N,), dtype=a.dtype, device=a.device)
+        h = torch.empty(lead + (N,), dtype=a.dtype, device=a.device) if want_gelu else None
+        an = torch.empty(lead + (K,), dtype=a.dtype, device=a.device) if want_norm else None
     g, b = ln
     mean = rstd = None
     if ln_stats is not None:
         mean, rstd = ln_stats
         assert mean.numel() == M and rstd.numel() == M
     assert bias is None or bias.dtype == torch.float32
-    L.call('wmz_linear_fwd_train', L.ptr(a), lda, L.ptr(weight), L.ptr(bias), L.ptr(c), N, L.ptr(h), N, L.ptr(an), K, M, N, K,
+    L.call('wmz_linear_fwd_train', L.ptr(a), lda, L.ptr(weight), L.ptr(bias), L.ptr(c), ldc, L.ptr(h), ldh, L.ptr(an), ldan, M, N, K,
            L.ptr(g), L.ptr(b), L.ptr(mean), L.ptr(rstd), float(ln_eps), dt, L.stream())
     return c, h, an
 
 
-def linear_fwd_gelu_pair(a, weight, bias=None, ln=None, ln_eps=1e-5, ln_stats=None):
-    """(z, h) = (LN?(a) @ weight^T + bias, GELU(z)), both in a's dtype, from one launch (wmz_linear_fwd_gelu_pair)."""
+def linear_fwd_gelu_pair(a, weight, bias=None, ln=None, ln_eps=1e-5, ln_stats=None, out=None):
+    """(z, h) = (LN?(a) @ weight^T + bias, GELU(z)), both in a's dtype, from one launch (wmz_linear_fwd_gelu_pair).
+    out = (z, h): write into these (row-strided views allowed) instead of allocating."""
     K = a.shape[-1]
     N = weight.shape[0]
     dt = L.dtype_code(a.dtype)
     assert weight.dtype == a.dtype and weight.is_contiguous() and weight.shape[1] == K
     a, M, lda = _rows(a)
     lead = a.shape[:-1]
-    z = torch.empty(lead + (N,), dtype=a.dtype, device=a.device)
-    h = torch.empty(lead + (N,), dtype=a.dtype, device=a.device)
+    ldz = ldh = N
+    if out is not None:
+        z, ldz = _out_rows(out[0], M, a.dtype)
+        h, ldh = _out_rows(out[1], M, a.dtype)
+    else:
+        z = torch.empty(lead + (N,), dtype=a.dtype, device=a.device)
+        h = torch.empty(lead + (N,), dtype=a.dtype, device=a.device)
     g = b = mean = rstd = None
     if ln is not None:
         g, b = ln
@@ -126,19 +151,23 @@ def linear_fwd_gelu_pair(a, weight, bias=None, ln=None, ln_eps=1e-5, ln_stats=No
         mean, rstd = ln_stats
         assert ln is not None and mean.numel() == M and rstd.numel() == M
     assert bias is None or bias.dtype == torch.float32
-    L.call('wmz_linear_fwd_gelu_pair', L.ptr(a), lda, L.ptr(weight), L.ptr(bias), L.ptr(z), N, L.ptr(h), N, M, N, K,
+    L.call('wmz_linear_fwd_gelu_pair', L.ptr(a), lda, L.ptr(weight), L.ptr(bias), L.ptr(z), ldz, L.ptr(h), ldh, M, N, K,
            L.ptr(g), L.ptr(b), L.ptr(mean), L.ptr(rstd), float(ln_eps), dt, L.stream())
     return z, h
 
 
-def linear_fwd_blocks(a, weight, bias=None, out_f32=False):
+def linear_fwd_blocks(a, weight, bias=None, out_f32=False, out=None):
     """a: [Bk, R, K] with contiguous rows inside each block and an arbitrary block stride (x[:, -1] of a [B,S,H,W,D]
     stream, flattened to [B, H*W, D]) -> [Bk, R, N] = a @ weight^T + bias, the blocks read in place."""
     Bk, R, K = a.shape
     N = weight.shape[0]
     assert a.stride(2) == 1 and weight.dtype == a.dtype and weight.is_contiguous() and weight.shape[1] == K
-    out = torch.empty((Bk, R, N), dtype=torch.float32 if out_f32 else a.dtype, device=a.device)
-    L.call(L.half_form('wmz_linear_fwd_blocked', a.dtype), L.ptr(a), a.stride(1), R, a.stride(0), L.ptr(weight), L.ptr(bias), L.ptr(out), N,
+    ldc = N
+    if out is None:
+        out = torch.empty((Bk, R, N), dtype=torch.float32 if out_f32 else a.dtype, device=a.device)
+    else:                               # (a caller's [Bk * R, N] rows, row-strided views allowed)
+        out, ldc = _out_rows(out, Bk * R, torch.float32 if out_f32 else a.dtype)
+    L.call(L.half_form('wmz_linear_fwd_blocked', a.dtype), L.ptr(a), a.stride(1), R, a.stride(0), L.ptr(weight), L.ptr(bias), L.ptr(out), ldc,
            Bk * R, N, K, 1 if out_f32 else 0, L.dtype_code(a.dtype), L.stream())
     return out
 
@@ -341,18 +370,23 @@ def local3d_attention_bwd(q, k, v, out, lse, dout, extents, heads, dqkv=None):
     return dq, dkv
 
 
-def linear_dgrad(dc, weight_t, dgelu_z=None):
-    """dA' = dC @ W (weight_t = W^T contiguous [K, N] in dC's dtype), optionally times gelu'(z)."""
+def linear_dgrad(dc, weight_t, dgelu_z=None, out=None):
+    """dA' = dC @ W (weight_t = W^T contiguous [K, N] in dC's dtype), optionally times gelu'(z).  out: write into this
+    (a row-strided view allowed) instead of allocating."""
     K = weight_t.shape[0]
     dt = L.dtype_code(dc.dtype)
     dc, M, ldc = _rows(dc)
     N = dc.shape[-1]
-    out = torch.empty(dc.shape[:-1] + (K,), dtype=dc.dtype, device=dc.device)
+    ldo = K
+    if out is None:
+        out = torch.empty(dc.shape[:-1] + (K,), dtype=dc.dtype, device=dc.device)
+    else:
+        out, ldo = _out_rows(out, M, dc.dtype)
     ldz = 0
     if dgelu_z is not None:
         dgelu_z, Mz, ldz = _rows(dgelu_z)
         assert Mz == M
-    L.call('wmz_linear_fwd', L.ptr(dc), ldc, L.ptr(weight_t), None, L.ptr(dgelu_z), ldz, L.ptr(out), K, M, K, N,
+    L.call('wmz_linear_fwd', L.ptr(dc), ldc, L.ptr(weight_t), None, L.ptr(dgelu_z), ldz, L.ptr(out), ldo, M, K, N,
            None, None, 0.0, L.WMZ_LIN_DGELU if dgelu_z is not None else 0, 0, dt, L.stream())
     return out
 
@@ -682,16 +716,21 @@ def linear_wgrad_batch(problems, side=None):
     L.call('wmz_linear_wgrad_batch', len(problems), *L.columns(rows, 'plplppiiiii'), L.ptr(ws), ws.numel(), dt, L.stream())
 
 
-def layernorm_stats(x, eps=1e-5):
+def layernorm_stats(x, eps=1e-5, out=None):
+    """(mean, rstd) of the rows of x, fp32 [M].  out = (mean, rstd): contiguous fp32 [M] tensors to write into."""
     x, M, ldx = _rows(x)
-    mean = torch.empty((M,), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((M,), dtype=torch.float32, device=x.device)
+    if out is not None:
+        mean, rstd = out
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == M for t in out)
+    else:
+        mean = torch.empty((M,), dtype=torch.float32, device=x.device)
+        rstd = torch.empty((M,), dtype=torch.float32, device=x.device)
     L.call('wmz_layernorm_stats', L.ptr(x), ldx, L.ptr(mean), L.ptr(rstd), M, x.shape[-1], float(eps),
            L.dtype_code(x.dtype), L.stream())
     return mean, rstd
 
 
-def layernorm_bwd(x, dyhat, gamma, dgamma, dbeta, skip=None, eps=1e-5, skip2=None):
+def layernorm_bwd(x, dyhat, gamma, dgamma, dbeta, skip=None, eps=1e-5, skip2=None, out=None):
     x, M, ldx = _rows(x)
     dyhat, _, lddy = _rows(dyhat)
     lds = lds2 = 0
@@ -701,9 +740,13 @@ def layernorm_bwd(x, dyhat, gamma, dgamma, dbeta, skip=None, eps=1e-5, skip2=Non
         skip, _, lds = _rows(skip)
     if skip2 is not None:
         skip2, _, lds2 = _rows(skip2)
-    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     K = x.shape[-1]
-    L.call('wmz_layernorm_bwd', L.ptr(x), ldx, L.ptr(dyhat), lddy, L.ptr(skip), lds, L.ptr(skip2), lds2, L.ptr(gamma), L.ptr(dx), K,
+    lddx = K
+    if out is None:
+        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    else:                               # (a caller's dx, a row-strided view allowed)
+        dx, lddx = _out_rows(out, M, x.dtype)
+    L.call('wmz_layernorm_bwd', L.ptr(x), ldx, L.ptr(dyhat), lddy, L.ptr(skip), lds, L.ptr(skip2), lds2, L.ptr(gamma), L.ptr(dx), lddx,
            L.ptr(dgamma), L.ptr(dbeta), M, K, float(eps), L.dtype_code(x.dtype), L.stream())
     return dx
 
