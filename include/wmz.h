@@ -697,6 +697,32 @@ int wmz_categorical_scatter(const float* logits, long ld, long R, int C, const i
 int wmz_sample_tokens_dev(const float* logits, long ld, int R, int C, int top_k, const float* alphas, int n_alpha,
                           int64_t mask_token, int64_t* out_tokens, long rows_per_block, long block_stride, int64_t* denoised,
                           unsigned char* last_mask, unsigned long long seed, const long long* counter, void* stream);
+/* The same step with a temperature, a nucleus (top-p) filter and codebooks up to wmz_sample_tokens_max_classes() = 16 384 classes;
+ * every argument of wmz_sample_tokens_dev keeps its meaning.  The law per row, in this order:
+ *   l = logits * inv_temperature         one fp32 multiply (inv_temperature > 0, finite: the caller passes 1 / temperature);
+ *   top-k on l                           as above;
+ *   w = exp(l - max) over what is left;
+ *   nucleus, 0 < top_p < 1               keep {w >= t}, t the LARGEST weight with mass{w >= t} >= top_p * total: the smallest set of
+ *                                        most probable classes whose mass reaches top_p, ties with its weakest member kept
+ *                                        (top_p >= 1: no filter).  The threshold comes from the same bitwise search as top-k's,
+ *                                        on the weights' bits, accumulating mass instead of counts: no sort;
+ *   draw                                 the first kept class, in class order, whose cumulative kept weight exceeds u0 * total;
+ *   re-mask                              mask_token where u1 > alpha, as above.
+ * uniforms (optional, [R, 2] fp32 in [0, 1)): u0, u1 of row r are uniforms[2 r], uniforms[2 r + 1] instead of the in-kernel
+ * generator's -- the call is then a deterministic function of its inputs.  kept_floor (optional, [R] fp32, a probe like `lse` of the
+ * attention entry points; NULL in production): the smallest kept l per row (the row's minimum when nothing was filtered), which
+ * makes the kept set {l >= kept_floor} observable.
+ * Two forms: up to 2048 classes the one-wave-per-row register kernel of wmz_sample_tokens_dev, the two filters compiled in only
+ * where they act (neutral arguments -- top_p >= 1, inv_temperature = 1, no uniforms, no probe -- launch the very kernel of
+ * wmz_sample_tokens_dev: same draws); above, one workgroup per row: the row is read ONCE (16-byte loads, the scaling applied) into
+ * LDS and the maximum, both threshold searches, the prefix sums and the draw work from there.  More classes than the limit:
+ * WMZ_ERR_UNSUPPORTED. */
+int wmz_sample_tokens_max_classes(void);
+int wmz_sample_tokens_filtered_dev(const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
+                                   const float* alphas, int n_alpha, int64_t mask_token, int64_t* out_tokens,
+                                   long rows_per_block, long block_stride, int64_t* denoised, unsigned char* last_mask,
+                                   const float* uniforms, float* kept_floor,
+                                   unsigned long long seed, const long long* counter, void* stream);
 /* CrossEntropyLoss(reduction='none') over fp32 logits [R, C] (row stride ld): loss[R], lse[R]; and its gradient
  * dlogits[r,c] = (softmax - one_hot) * grad_rows[r], written in `dtype` (the GEMM operand type of the backward). */
 int wmz_ce_fwd(const float* logits, long ld, const int64_t* target, float* loss, float* lse, long R, int C, void* stream);

@@ -43,28 +43,50 @@ __global__ __launch_bounds__(256) void corrupt_kernel(const int64_t* __restrict_
 //   * re-mask: with a second uniform u2 > alpha (and, with `last_mask`, only where the previous iteration masked:
 //     consistent masking) the position gets the mask token instead of the draw.
 // alpha = alphas[*counter % n_alpha] and the Philox stream id = *counter live in device memory: the launch sits in a hipGraph.
-template <int NV>
+// What wmz_sample_tokens_filtered_dev adds (include/wmz.h states the law), each compiled in only where it acts:
+//   * TEMP: l = logits * inv_temperature on the way into the registers;
+//   * TOPP: the nucleus threshold by the same bitwise search on the bits of the weights (non-negative floats order like their
+//     bits), accumulating the mass of the weights >= candidate instead of a count; weights below it are dropped;
+//   * PROBES: the uniforms from `uniforms` and the smallest kept l to `kept_floor`, each where the pointer is given.
+struct SampleExtras {
+  float top_p, inv_temperature;
+  const float* uniforms;
+  float* kept_floor;
+};
+
+__device__ __forceinline__ SampleExtras sample_extras() { return SampleExtras{}; }
+__device__ __forceinline__ SampleExtras sample_extras(const SampleExtras& x) { return x; }
+
+// (`extras`: nothing -- the kernel of wmz_sample_tokens_dev, its arguments as they always were -- or one SampleExtras)
+template <int NV, bool TEMP = false, bool TOPP = false, typename... Extras>
 __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restrict__ logits, long ld, int R, int C, int top_k,
                                                             const float* __restrict__ alphas, int n_alpha, int64_t mask_token,
                                                             int64_t* __restrict__ out_tokens, long rows_per_block,
                                                             long block_stride, int64_t* __restrict__ denoised,
                                                             unsigned char* __restrict__ last_mask, unsigned long long seed,
-                                                            const long long* __restrict__ counter) {
+                                                            const long long* __restrict__ counter, Extras... extras) {
+  static_assert(sizeof...(Extras) <= 1 && (sizeof...(Extras) == 1 || !(TEMP || TOPP)), "the filters read their values from a SampleExtras");
+  constexpr bool PROBES = sizeof...(Extras) == 1;
+  const SampleExtras x = sample_extras(extras...);
   const int lane = threadIdx.x & 63;
   const long ctr = *counter;
   const float alpha = alphas[(int)(ctr % n_alpha)];
   for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < R; row += (long)gridDim.x * 4) {
-    const float* x = logits + row * ld + lane * NV;
+    const float* x_lane = logits + row * ld + lane * NV;
     float v[NV];
 #pragma unroll
     for (int e = 0; e < NV; e += 4) {
       if (lane * NV + e + 3 < C) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(x + e);
+        const f32x4 q = *reinterpret_cast<const f32x4*>(x_lane + e);
         v[e] = q[0]; v[e + 1] = q[1]; v[e + 2] = q[2]; v[e + 3] = q[3];
       } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[e + i] = lane * NV + e + i < C ? x[e + i] : -INFINITY;
+        for (int i = 0; i < 4; ++i) v[e + i] = lane * NV + e + i < C ? x_lane[e + i] : -INFINITY;
       }
+    }
+    if constexpr (TEMP) {
+#pragma unroll
+      for (int e = 0; e < NV; ++e) v[e] *= x.inv_temperature;            // (-inf stays -inf: inv_temperature > 0)
     }
     if (top_k > 0 && top_k < C) {
       // order-preserving keys: flip all bits of negatives, the sign bit of non-negatives
@@ -90,6 +112,23 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
     for (int e = 1; e < NV; ++e) m = fmaxf(m, v[e]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if constexpr (TOPP) {
+      float wt[NV], part = 0.f;
+#pragma unroll
+      for (int e = 0; e < NV; ++e) { wt[e] = __expf(v[e] - m); part += wt[e]; }
+      // (one lane's sums decide for the wave: the lanes must agree on T)
+      const float need = x.top_p * __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(wave_sum(part))));
+      unsigned T = 0;                                          // (bit 31 is the sign: never set in a weight)
+      for (int bit = 30; bit >= 0; --bit) {
+        const unsigned cand = T | (1u << bit);
+        float mass = 0.f;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) mass += __float_as_uint(wt[e]) >= cand ? wt[e] : 0.f;
+        if (__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(wave_sum(mass)))) >= need) T = cand;
+      }
+#pragma unroll
+      for (int e = 0; e < NV; ++e) if (__float_as_uint(wt[e]) < T) v[e] = -INFINITY;
+    }
     float w[NV], part = 0.f;
 #pragma unroll
     for (int e = 0; e < NV; ++e) { w[e] = __expf(v[e] - m); part += w[e]; w[e] = part; }    // lane-local running sums
@@ -102,7 +141,14 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
     const float total = __shfl(inc, 63);
     const float base = inc - part;
     float u[4];
-    philox4_unit((unsigned long long)row, (unsigned long long)ctr, seed, u);
+    bool given = false;
+    if constexpr (PROBES) given = x.uniforms != nullptr;
+    if (given) {
+      u[0] = x.uniforms[2 * row];
+      u[1] = x.uniforms[2 * row + 1];
+    } else {
+      philox4_unit((unsigned long long)row, (unsigned long long)ctr, seed, u);
+    }
     const float xq = u[0] * total;
     int below = 0;
 #pragma unroll
@@ -110,6 +156,16 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
     const int draw = below < C ? below : C - 1;
+    if constexpr (PROBES) {
+      if (x.kept_floor != nullptr) {
+        float f = INFINITY;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) f = v[e] > -INFINITY ? fminf(f, v[e]) : f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) f = fminf(f, __shfl_xor(f, o));
+        if (lane == 0) x.kept_floor[row] = f;
+      }
+    }
     if (lane == 0) {
       bool mask = u[1] > alpha;
       if (last_mask != nullptr) { mask = mask && last_mask[row] != 0; last_mask[row] = mask ? 1 : 0; }
@@ -117,6 +173,206 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
       const long blk = row / rows_per_block;
       out_tokens[blk * block_stride + (row - blk * rows_per_block)] = mask ? mask_token : (int64_t)draw;
     }
+  }
+}
+
+// The same step for rows that do not fit a wave's registers (2048 < C <= SW_MAX_CLASSES): one workgroup of SW_NT threads per row.
+// The row is read from global memory ONCE -- 16-byte loads, scaled, turned into the order-preserving keys above -- into LDS, and
+// every later pass works from there.  Thread t owns the P consecutive classes t * P .. (P a multiple of 8, classes past C are
+// -inf), kept at a pitch of P + 4 words: P / 4 + 1 is odd, so the 16-byte slots that consecutive lanes read in one ds_read_b128
+// fall on different banks.  The passes, each a walk of the thread's own slots:
+//   * the maximum (of the keys: same order);
+//   * top-k: the bitwise search, counts by wave ballots, the four waves' counts through LDS (one barrier per step);
+//   * keys -> weights w = exp(l - max) in place, 0 for what top-k dropped;
+//   * nucleus: the bitwise search on the weights' bits accumulating mass; weights below the threshold become 0;
+//   * the prefix in class order -- sequential in the thread, shuffle scan over the lanes, the waves' totals in wave order --
+//     and the draw: the FIRST KEPT class whose cumulative weight exceeds u0 * total (the last kept one if rounding leaves none):
+//     a class of weight 0 is never drawn, whatever the rounding of the partial sums.
+// The kept_floor probe alone walks the global row a second time (the keys are gone by then): it is NULL in production.
+constexpr int SW_NT = 256;
+constexpr int SW_MAX_CLASSES = 16384;
+constexpr int SW_RED_WORDS = 16;          // two alternating sets of (SW_NT / 64 waves) x 2 words behind the row
+
+__device__ __forceinline__ unsigned sw_key(float l) {
+  const unsigned b = __float_as_uint(l);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float sw_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+// The four waves' (a, b) pairs to every thread: each wave's lane 0 writes, one barrier, all read.  The sets alternate, so a wave
+// that runs ahead into the next exchange writes the other set while a slower one still reads this one.
+struct SwExchange {
+  unsigned* red;
+  int turn;
+  __device__ __forceinline__ void operator()(unsigned a, unsigned b, unsigned (&oa)[4], unsigned (&ob)[4]) {
+    unsigned* set = red + (turn & 1) * 8;
+    turn ^= 1;
+    if ((threadIdx.x & 63) == 0) { set[threadIdx.x >> 6] = a; set[4 + (threadIdx.x >> 6)] = b; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { oa[w] = set[w]; ob[w] = set[4 + w]; }
+  }
+};
+
+__global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* __restrict__ logits, long ld, int R, int C, int P, int top_k,
+                                                                   float top_p, float inv_temperature,
+                                                                   const float* __restrict__ alphas, int n_alpha, int64_t mask_token,
+                                                                   int64_t* __restrict__ out_tokens, long rows_per_block,
+                                                                   long block_stride, int64_t* __restrict__ denoised,
+                                                                   unsigned char* __restrict__ last_mask,
+                                                                   const float* __restrict__ uniforms, float* __restrict__ kept_floor,
+                                                                   unsigned long long seed, const long long* __restrict__ counter) {
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+  extern __shared__ __attribute__((aligned(16))) unsigned sw_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int pitch = P + 4, nq = P >> 2;
+  u32x4* mine = reinterpret_cast<u32x4*>(sw_lds + tid * pitch);
+  SwExchange exchange{sw_lds + SW_NT * pitch, 0};
+  unsigned ra[4], rb[4];
+  const long ctr = *counter;
+  const float alpha = alphas[(int)(ctr % n_alpha)];
+  for (long row = blockIdx.x; row < R; row += gridDim.x) {
+    const float* x = logits + row * ld;
+    for (int c = tid * 4; c < SW_NT * P; c += SW_NT * 4) {
+      f32x4 q;
+      if (c + 3 < C) {
+        q = *reinterpret_cast<const f32x4*>(x + c) * inv_temperature;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = c + i < C ? x[c + i] * inv_temperature : -INFINITY;
+      }
+      const u32x4 k = {sw_key(q[0]), sw_key(q[1]), sw_key(q[2]), sw_key(q[3])};
+      *reinterpret_cast<u32x4*>(sw_lds + c + 4 * (c / P)) = k;             // (P is a multiple of 4: the four share an owner)
+    }
+    __syncthreads();
+    unsigned kmax = 0;
+    for (int q = 0; q < nq; ++q) {
+      const u32x4 k = mine[q];
+      kmax = max(max(kmax, max(k[0], k[1])), max(k[2], k[3]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o));
+    exchange(kmax, 0u, ra, rb);
+    const float m = sw_unkey(max(max(ra[0], ra[1]), max(ra[2], ra[3])));
+    unsigned Tk = 0;
+    if (top_k > 0 && top_k < C) {
+      for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = Tk | (1u << bit);
+        int cnt = 0;
+        for (int q = 0; q < nq; ++q) {
+          const u32x4 k = mine[q];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) cnt += __popcll(__ballot(k[i] >= cand));
+        }
+        exchange((unsigned)cnt, 0u, ra, rb);
+        if ((int)(ra[0] + ra[1] + ra[2] + ra[3]) >= top_k) Tk = cand;
+      }
+    }
+    float part = 0.f;                                          // the thread's kept weight, summed in class order
+    for (int q = 0; q < nq; ++q) {
+      const u32x4 k = mine[q];
+      u32x4 wq;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float w = k[i] >= Tk ? __expf(sw_unkey(k[i]) - m) : 0.f;
+        part += w;
+        wq[i] = __float_as_uint(w);
+      }
+      mine[q] = wq;
+    }
+    unsigned Tw = 0;
+    if (top_p < 1.f) {
+      exchange(__float_as_uint(wave_sum(part)), 0u, ra, rb);
+      const float need = top_p * ((__uint_as_float(ra[0]) + __uint_as_float(ra[1])) + (__uint_as_float(ra[2]) + __uint_as_float(ra[3])));
+      for (int bit = 30; bit >= 0; --bit) {                    // (bit 31 is the sign: never set in a weight)
+        const unsigned cand = Tw | (1u << bit);
+        float mass = 0.f;
+        for (int q = 0; q < nq; ++q) {
+          const u32x4 wq = mine[q];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) mass += wq[i] >= cand ? __uint_as_float(wq[i]) : 0.f;
+        }
+        exchange(__float_as_uint(wave_sum(mass)), 0u, ra, rb);
+        if ((__uint_as_float(ra[0]) + __uint_as_float(ra[1])) + (__uint_as_float(ra[2]) + __uint_as_float(ra[3])) >= need) Tw = cand;
+      }
+      part = 0.f;
+      for (int q = 0; q < nq; ++q) {
+        u32x4 wq = mine[q];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (wq[i] < Tw) wq[i] = 0u;
+          part += __uint_as_float(wq[i]);
+        }
+        mine[q] = wq;
+      }
+    }
+    float inc = part;                                          // inclusive scan of the threads' totals: lanes, then waves, in order
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float o = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += o;
+    }
+    exchange(__float_as_uint(__shfl(inc, 63)), 0u, ra, rb);
+    float before = 0.f, total = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w == wave) before = total;
+      total += __uint_as_float(ra[w]);
+    }
+    const float base = before + (inc - part);
+    float u[4];
+    if (uniforms != nullptr) {
+      u[0] = uniforms[2 * row];
+      u[1] = uniforms[2 * row + 1];
+    } else {
+      philox4_unit((unsigned long long)row, (unsigned long long)ctr, seed, u);
+    }
+    const float xq = u[0] * total;
+    int first = 0x7fffffff, last = -1;                            // kept classes of this thread: the first past xq, the last
+    float run = 0.f;
+    for (int q = 0; q < nq; ++q) {
+      const u32x4 wq = mine[q];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = tid * P + q * 4 + i;
+        run += __uint_as_float(wq[i]);
+        if (wq[i] != 0u) {
+          last = c;
+          if (base + run > xq) first = min(first, c);
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      first = min(first, __shfl_xor(first, o));
+      last = max(last, __shfl_xor(last, o));
+    }
+    exchange((unsigned)first, (unsigned)last, ra, rb);
+    first = min(min((int)ra[0], (int)ra[1]), min((int)ra[2], (int)ra[3]));
+    last = max(max((int)rb[0], (int)rb[1]), max((int)rb[2], (int)rb[3]));
+    const int draw = first != 0x7fffffff ? first : (last >= 0 ? last : C - 1);
+    if (kept_floor != nullptr) {                               // probe: the keys are gone, so the same law over the global row again
+      unsigned kmin = 0xFFFFFFFFu;
+      for (int c = tid; c < C; c += SW_NT) {
+        const unsigned k = sw_key(x[c] * inv_temperature);
+        if (k >= Tk) {
+          const unsigned wb = __float_as_uint(__expf(sw_unkey(k) - m));
+          if (Tw == 0u || wb >= Tw) kmin = min(kmin, k);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o));
+      exchange(kmin, 0u, ra, rb);
+      if (tid == 0) kept_floor[row] = sw_unkey(min(min(ra[0], ra[1]), min(ra[2], ra[3])));
+    }
+    if (tid == 0) {
+      bool mask = u[1] > alpha;
+      if (last_mask != nullptr) { mask = mask && last_mask[row] != 0; last_mask[row] = mask ? 1 : 0; }
+      denoised[row] = draw;
+      const long blk = row / rows_per_block;
+      out_tokens[blk * block_stride + (row - blk * rows_per_block)] = mask ? mask_token : (int64_t)draw;
+    }
+    __syncthreads();                                           // (the next row is staged over slots other threads own)
   }
 }
 
@@ -243,6 +499,47 @@ extern "C" int wmz_corrupt_tokens_dev(const int64_t* z_last, long clip_stride, c
   return WMZ_OK;
 }
 
+// The sampler step's launches: `filtered` = reached through wmz_sample_tokens_filtered_dev (the checks are the callers').
+static int sample_tokens_launch(const char* name, const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
+                                const float* alphas, int n_alpha, int64_t mask_token, int64_t* out_tokens, long rows_per_block,
+                                long block_stride, int64_t* denoised, unsigned char* last_mask, const float* uniforms,
+                                float* kept_floor, unsigned long long seed, const long long* counter, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const bool temp = inv_temperature != 1.f, topp = top_p < 1.f;
+  if (C > 2048) {
+    const int P = (wmz_cdiv(C, SW_NT) + 7) / 8 * 8;
+    const size_t smem = ((size_t)SW_NT * (P + 4) + SW_RED_WORDS) * 4;
+    static std::atomic<uint64_t> attr_devs{0};                       // (> 64 KB of dynamic LDS has to be asked for once per device)
+    if (wmz_first_use_on_device(attr_devs))
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tokens_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(((size_t)SW_NT * (SW_MAX_CLASSES / SW_NT + 4) + SW_RED_WORDS) * 4));
+    hipLaunchKernelGGL(sample_tokens_wide_kernel, dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R, C, P, top_k, top_p,
+                       inv_temperature, alphas, n_alpha, mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask,
+                       uniforms, kept_floor, seed, counter);
+    WMZ_LAUNCH_CHECK(name);
+    return WMZ_OK;
+  }
+  const int grid = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
+  if (!temp && !topp && uniforms == nullptr && kept_floor == nullptr) {
+#define WMZ_SMP(NV) hipLaunchKernelGGL(sample_tokens_kernel<NV>, dim3(grid), dim3(256), 0, st, logits, ld, R, C, top_k, alphas, n_alpha, \
+                                       mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask, seed, counter)
+    if (C <= 256) WMZ_SMP(4); else if (C <= 512) WMZ_SMP(8); else if (C <= 1024) WMZ_SMP(16); else WMZ_SMP(32);
+#undef WMZ_SMP
+  } else {
+    const SampleExtras x = {top_p, inv_temperature, uniforms, kept_floor};
+#define WMZ_SMP(NV, TEMP, TOPP) hipLaunchKernelGGL((sample_tokens_kernel<NV, TEMP, TOPP, SampleExtras>), dim3(grid), dim3(256), 0, st, logits, ld, R, C, \
+                                                   top_k, alphas, n_alpha, mask_token, out_tokens, rows_per_block, block_stride,          \
+                                                   denoised, last_mask, seed, counter, x)
+#define WMZ_SMP_NV(TEMP, TOPP) \
+  do { if (C <= 256) WMZ_SMP(4, TEMP, TOPP); else if (C <= 512) WMZ_SMP(8, TEMP, TOPP); else if (C <= 1024) WMZ_SMP(16, TEMP, TOPP); else WMZ_SMP(32, TEMP, TOPP); } while (0)
+    if (temp && topp) WMZ_SMP_NV(true, true); else if (temp) WMZ_SMP_NV(true, false); else if (topp) WMZ_SMP_NV(false, true); else WMZ_SMP_NV(false, false);
+#undef WMZ_SMP_NV
+#undef WMZ_SMP
+  }
+  WMZ_LAUNCH_CHECK(name);
+  return WMZ_OK;
+}
+
 extern "C" int wmz_sample_tokens_dev(const float* logits, long ld, int R, int C, int top_k, const float* alphas, int n_alpha,
                                      int64_t mask_token, int64_t* out_tokens, long rows_per_block, long block_stride,
                                      int64_t* denoised, unsigned char* last_mask, unsigned long long seed,
@@ -254,14 +551,31 @@ extern "C" int wmz_sample_tokens_dev(const float* logits, long ld, int R, int C,
     wmz_set_error("wmz_sample_tokens_dev: built for <= 2048 classes (got %d)", C);
     return WMZ_ERR_UNSUPPORTED;
   }
-  const int grid = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
-  hipStream_t st = (hipStream_t)stream;
-#define WMZ_SMP(NV) hipLaunchKernelGGL(sample_tokens_kernel<NV>, dim3(grid), dim3(256), 0, st, logits, ld, R, C, top_k, alphas, n_alpha, \
-                                       mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask, seed, counter)
-  if (C <= 256) WMZ_SMP(4); else if (C <= 512) WMZ_SMP(8); else if (C <= 1024) WMZ_SMP(16); else WMZ_SMP(32);
-#undef WMZ_SMP
-  WMZ_LAUNCH_CHECK("wmz_sample_tokens_dev");
-  return WMZ_OK;
+  return sample_tokens_launch("wmz_sample_tokens_dev", logits, ld, R, C, top_k, 1.f, 1.f, alphas, n_alpha, mask_token, out_tokens,
+                              rows_per_block, block_stride, denoised, last_mask, nullptr, nullptr, seed, counter, stream);
+}
+
+extern "C" int wmz_sample_tokens_max_classes(void) { return SW_MAX_CLASSES; }
+
+extern "C" int wmz_sample_tokens_filtered_dev(const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
+                                              const float* alphas, int n_alpha, int64_t mask_token, int64_t* out_tokens,
+                                              long rows_per_block, long block_stride, int64_t* denoised, unsigned char* last_mask,
+                                              const float* uniforms, float* kept_floor, unsigned long long seed,
+                                              const long long* counter, void* stream) {
+  WMZ_REQUIRE(logits && alphas && out_tokens && denoised && counter && R > 0 && C > 0 && n_alpha > 0 && rows_per_block > 0,
+              "wmz_sample_tokens_filtered_dev: bad arguments");
+  WMZ_REQUIRE(ld >= C && ld % 4 == 0 && (((uintptr_t)logits) & 15) == 0,
+              "wmz_sample_tokens_filtered_dev: logits rows must be 16-byte aligned");
+  WMZ_REQUIRE(inv_temperature > 0.f && inv_temperature < INFINITY,
+              "wmz_sample_tokens_filtered_dev: inv_temperature must be positive and finite (got %g)", (double)inv_temperature);
+  WMZ_REQUIRE(top_p > 0.f, "wmz_sample_tokens_filtered_dev: top_p must be positive (got %g)", (double)top_p);
+  if (C > SW_MAX_CLASSES) {
+    wmz_set_error("wmz_sample_tokens_filtered_dev: built for <= %d classes (got %d)", SW_MAX_CLASSES, C);
+    return WMZ_ERR_UNSUPPORTED;
+  }
+  return sample_tokens_launch("wmz_sample_tokens_filtered_dev", logits, ld, R, C, top_k, top_p, inv_temperature, alphas, n_alpha,
+                              mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask, uniforms, kept_floor, seed,
+                              counter, stream);
 }
 
 extern "C" int wmz_ce_fwd(const float* logits, long ld, const int64_t* target, float* loss, float* lse, long R, int C,

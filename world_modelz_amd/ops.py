@@ -301,16 +301,35 @@ def recon_loss(y_nhwc, target_nchw, kind):
     return _ReconLoss.apply(y_nhwc, target_nchw, RECON_LOSS_KINDS[kind])
 
 
-def sample_tokens(logits, top_k, alphas, mask_token, last_frame, denoised, counter, seed, last_mask=None):
+SAMPLE_REGISTER_CLASSES = 2048      # up to here a row of logits is one wave's registers (wmz_sample_tokens_dev's own limit)
+
+
+def sample_max_classes():
+    """The widest codebook the sampler step draws from (wmz_sample_tokens_filtered_dev): the library's own figure."""
+    return L.lib().wmz_sample_tokens_max_classes()
+
+
+def sample_tokens(logits, top_k, alphas, mask_token, last_frame, denoised, counter, seed, last_mask=None, *, top_p=1.0,
+                  temperature=1.0, uniforms=None, kept_floor=None):
     """wmz_sample_tokens_dev: logits fp32 [R, C]; last_frame: the [B, H, W] int64 view batch_z[:, -1] the tokens are written
-    into in place; denoised int64 [R]; alphas fp32 [n]; counter int64 [1] (device); last_mask uint8 [R] or None."""
+    into in place; denoised int64 [R]; alphas fp32 [n]; counter int64 [1] (device); last_mask uint8 [R] or None.
+    top_p (nucleus, (0, 1]), temperature (> 0), uniforms fp32 [R, 2] (u0, u1 per row instead of the in-kernel generator) and
+    kept_floor fp32 [R] (probe: receives the smallest kept scaled logit per row), or more than 2048 classes, go to
+    wmz_sample_tokens_filtered_dev (include/wmz.h states its law); the kernel scales by the fp32 value of 1 / temperature."""
     R, C = logits.shape
     B = last_frame.shape[0]
     assert logits.dtype == torch.float32 and logits.stride(1) == 1 and last_frame.dtype == torch.int64
     assert last_frame[0].is_contiguous() and R % B == 0 and denoised.numel() == R and counter.dtype == torch.int64
-    L.call('wmz_sample_tokens_dev', L.ptr(logits), logits.stride(0), R, C, int(top_k), L.ptr(alphas), alphas.numel(), int(mask_token),
-           L.ptr(last_frame), R // B, last_frame.stride(0), L.ptr(denoised), L.ptr(last_mask), int(seed) & 0xFFFFFFFFFFFFFFFF,
-           L.ptr(counter), L.stream())
+    head = (L.ptr(logits), logits.stride(0), R, C, int(top_k))
+    tail = (L.ptr(alphas), alphas.numel(), int(mask_token), L.ptr(last_frame), R // B, last_frame.stride(0), L.ptr(denoised),
+            L.ptr(last_mask))
+    if top_p >= 1.0 and temperature == 1.0 and uniforms is None and kept_floor is None and C <= SAMPLE_REGISTER_CLASSES:
+        L.call('wmz_sample_tokens_dev', *head, *tail, int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream())
+        return
+    assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.shape == (R, 2))
+    assert kept_floor is None or (kept_floor.dtype == torch.float32 and kept_floor.is_contiguous() and kept_floor.numel() == R)
+    L.call('wmz_sample_tokens_filtered_dev', *head, float(top_p), 1.0 / float(temperature), *tail, L.ptr(uniforms), L.ptr(kept_floor),
+           int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream())
 
 
 _vq_ws = {}

@@ -18,6 +18,21 @@ def top_k_logits(logits, k):
     return logits.masked_fill(logits < v[:, [-1]], -float('inf'))
 
 
+def top_p_logits(logits, p):
+    """Nucleus filter: per row keep {w >= t}, w = exp(logits - max) and t the largest weight whose classes {w >= t} hold at least
+    p of the row's total weight -- the smallest set of most probable classes whose mass reaches p, ties with its weakest member
+    kept -- and -inf elsewhere (rows already filtered by top_k_logits: their -inf entries weigh 0 and stay out).  p >= 1: the
+    logits as they are.  The law of the fused kernel (include/wmz.h wmz_sample_tokens_filtered_dev)."""
+    if p >= 1.0:
+        return logits
+    w = (logits - logits.max(dim=-1, keepdim=True).values).exp()
+    ws, _ = torch.sort(w, dim=-1, descending=True)
+    mass = ws.cumsum(dim=-1)                                     # mass[j] = weight of {w >= ws[j]} once ties are passed ...
+    reached = mass >= p * mass[:, [-1]]
+    first = reached.float().argmax(dim=-1, keepdim=True)         # ... so the first j that reaches p names the threshold weight
+    return logits.masked_fill(w < ws.gather(-1, first), -float('inf'))
+
+
 def categorical_from_uniform(p, u):
     """Inverse-CDF categorical draw: the first class whose cumulative weight exceeds u * total (u in [0, 1), one per row).
     This is the definition the sampler-parity fixtures are captured with (torch.multinomial replaced by it inside the
@@ -29,15 +44,22 @@ def categorical_from_uniform(p, u):
 
 @torch.no_grad()
 def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iterations=30, sample_topk=-1, noise_schedule=None,
-                  consistent_masking=False, generator=None, use_graph=True, uniforms=None, trace=None):
+                  consistent_masking=False, generator=None, use_graph=True, uniforms=None, trace=None, temperature=1.0,
+                  sample_topp=1.0):
     """batch_z: int64 [B,S,H,W] context tokens on the GPU (the last frame is overwritten).  Returns the list of generated
     latent frames [B,H,W] (decode them with VqAutoEncoder.decode) and the final batch_z.
 
     uniforms = (u_multi [num_frames, num_eval_iterations, B*H*W], u_mask [num_frames, num_eval_iterations, B, H*W]):
     injected randomness -- the categorical draw becomes categorical_from_uniform and the re-mask field u_mask > alpha
     (main.py:85, :97-100), which makes the loop a deterministic function of its inputs (parity tests); default: device RNG.
-    trace: optional list that receives every last frame fed to the model."""
+    trace: optional list that receives every last frame fed to the model.
+    temperature (> 0) divides the logits in front of the filters; sample_topp in (0, 1] is the nucleus filter (top_p_logits)
+    behind top-k: ValueError for anything else.  The defaults leave every draw as it was."""
     assert batch_z.is_cuda
+    if not temperature > 0 or not temperature < float('inf'):
+        raise ValueError(f'temperature must be positive and finite (got {temperature})')
+    if not 0 < sample_topp <= 1:
+        raise ValueError(f'sample_topp must lie in (0, 1] (got {sample_topp})')
     from . import half_guard
     if half_guard.wanted():
         # config.half_guard: the whole call is one guarded call (its forwards only accumulate into the word); a fallback repeats
@@ -52,15 +74,17 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
                 g.set_state(st)
             if trace is not None:
                 del trace[:]
-            return sample_frames(*args, trace=trace)
-        return half_guard.guarded('sample.sample_frames', model, batch_z.device, lambda: sample_frames(*args, trace=trace), again)
+            return sample_frames(*args, trace=trace, temperature=temperature, sample_topp=sample_topp)
+        return half_guard.guarded('sample.sample_frames', model, batch_z.device,
+                                  lambda: sample_frames(*args, trace=trace, temperature=temperature, sample_topp=sample_topp), again)
     B, S, H, W = batch_z.shape
     mask_token = num_embeddings
     batch_z = batch_z.clone()
     batch_z[:, -1] = mask_token                                   # destroy all information in the last frame (:62)
-    if use_graph and uniforms is None and trace is None and num_embeddings <= 2048:
+    from . import ops
+    if use_graph and uniforms is None and trace is None and num_embeddings <= ops.sample_max_classes():
         return _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_iterations, sample_topk, noise_schedule,
-                                    consistent_masking, generator)
+                                    consistent_masking, generator, temperature, sample_topp)
     fwd = GraphedForward(model, batch_z) if use_graph else None
     if fwd is not None:
         batch_z = fwd.static_in                                   # the loop edits the graph's own input buffer: no staging copy
@@ -68,13 +92,17 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     if uniforms is not None:
         u_multi, u_mask = (t.to(dev) for t in uniforms)
         assert u_multi.shape[:2] == (num_frames, num_eval_iterations) and u_mask.shape[:2] == (num_frames, num_eval_iterations)
+    inv_temperature = torch.tensor(1.0 / temperature, dtype=torch.float32, device=dev)     # (the fp32 value the kernel multiplies by)
     out = []
     for f in range(num_frames):
         logits = torch.zeros(B * H * W, num_embeddings, device=dev)      # flat start (:71)
         last_mask = torch.ones(B, H * W, dtype=torch.bool, device=dev)
         for i in range(num_eval_iterations):
+            if temperature != 1.0:
+                logits = logits * inv_temperature
             if sample_topk > 0:
                 logits = top_k_logits(logits, sample_topk)
+            logits = top_p_logits(logits, sample_topp)
             p = F.softmax(logits, dim=-1)
             if uniforms is not None:
                 denoised = categorical_from_uniform(p, u_multi[f, i].reshape(-1)).view(B, H * W)
@@ -166,7 +194,7 @@ class _Session:
     model across sample_frames calls: capturing costs ~4 ms, a frame of 30 iterations ~11 (GraphedForward re-captures by itself
     when the weights, the compute dtype or the run-time configuration changed)."""
 
-    def __init__(self, model, batch_z, C, n_iter, sample_topk, consistent_masking):
+    def __init__(self, model, batch_z, C, n_iter, sample_topk, consistent_masking, temperature=1.0, sample_topp=1.0):
         from . import ops
         B, S, H, W = batch_z.shape
         dev = batch_z.device
@@ -180,7 +208,8 @@ class _Session:
         holder = {}
 
         def draw(src, z):
-            ops.sample_tokens(src, sample_topk, self.alphas, C, z[:, -1], self.denoised, self.counter, _SEED_KEY, self.last_mask)
+            ops.sample_tokens(src, sample_topk, self.alphas, C, z[:, -1], self.denoised, self.counter, _SEED_KEY, self.last_mask,
+                              top_p=sample_topp, temperature=temperature)
             self.counter.add_(1)
 
         def pre(z):
@@ -197,9 +226,10 @@ class _Session:
 
 
 def _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_iterations, sample_topk, noise_schedule,
-                         consistent_masking, generator):
+                         consistent_masking, generator, temperature=1.0, sample_topp=1.0):
     """The same loop with NO host work inside a frame but one graph launch per iteration: the draw + re-mask step is one
-    kernel (wmz_sample_tokens_dev: top-k, softmax, inverse-CDF draw and re-mask per row, uniforms from in-kernel Philox indexed
+    kernel (wmz_sample_tokens_dev, or wmz_sample_tokens_filtered_dev with a temperature, a nucleus filter or more than 2048 classes
+    -- up to ops.sample_max_classes(): temperature, top-k, softmax, top-p, inverse-CDF draw and re-mask per row, uniforms from in-kernel Philox indexed
     by a device-side iteration counter that starts, per call, at a draw from the caller's generator) captured BEHIND the forward
     whose logits it reads, the counter increment behind it.  One graph replay = the forward on the current grid + the draw of the
     NEXT iteration from its logits (read where the graph leaves them: no hand-over copy when the rows are 16-byte aligned).  A
@@ -209,9 +239,11 @@ def _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_it
     injected uniforms: the parity fixtures), different random stream."""
     B, S, H, W = batch_z.shape
     n = num_eval_iterations
-    key = (B, S, H, W, num_embeddings, n, int(sample_topk), bool(consistent_masking), batch_z.device)
+    key = (B, S, H, W, num_embeddings, n, int(sample_topk), bool(consistent_masking), batch_z.device, float(temperature),
+           float(sample_topp))
     per_model = model.__dict__.setdefault('_wmz_sampler_sessions', _Sessions())
-    ses = per_model.touch(key, lambda: _Session(model, batch_z, num_embeddings, n, sample_topk, consistent_masking))
+    ses = per_model.touch(key, lambda: _Session(model, batch_z, num_embeddings, n, sample_topk, consistent_masking,
+                                                     temperature, sample_topp))
     ses.alphas.copy_(torch.tensor([min(max(noise_schedule((i + 1) / n) if noise_schedule is not None else (i + 1) / n, 0.0), 1.0)
                                    for i in range(n)], dtype=torch.float32))
     # The Philox stream is indexed by the counter; a call starts it at a 62-bit draw from the caller's generator (the global CPU
