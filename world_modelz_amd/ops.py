@@ -844,18 +844,26 @@ def conv_family(B, Hi, Wi, Cin, Cout, KH, KW, stride, pad, residual=False, pre=F
 
 
 def conv2d_nhwc(x, w_op, KH, KW, stride, pad, bias=None, scale=None, shift=None, residual=None, leaky=False,
-                slope=0.01, stats=False, pre=None):
+                slope=0.01, stats=False, pre=None, out=None):
     """x: [B,H,W,Cin] contiguous (Cin % 8 == 0), w_op: [Cout, KH*KW*Cin] in x's dtype -> [B,Ho,Wo,Cout] (+ sum, sq: fp32
     [STAT_REPLICAS, Cout] partial sums, summed by bn_finalize).  float16 (the precise mode's conv route) runs on the half forms of
-    the direct / streaming kernels and raises for a geometry they do not hold (conv_family)."""
+    the direct / streaming kernels and raises for a geometry they do not hold (conv_family).  out: the contiguous [B,Ho,Wo,Cout]
+    tensor of x's dtype to write instead of a new one -- with stats, (out, sum, sq): the two fp32 [STAT_REPLICAS, Cout] tensors the
+    launch ADDS its statistics to (zeroed by the caller)."""
     B, Hi, Wi, Cin = x.shape
     Cout = w_op.shape[0]
     assert x.is_contiguous() and w_op.is_contiguous() and w_op.shape[1] == KH * KW * Cin and w_op.dtype == x.dtype
     Ho = (Hi + 2 * pad - KH) // stride + 1
     Wo = (Wi + 2 * pad - KW) // stride + 1
-    out = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
     s = q = None
-    if stats:
+    if stats and out is not None:
+        out, s, q = out
+        assert all(t.shape == (STAT_REPLICAS, Cout) and t.dtype == torch.float32 and t.is_contiguous() for t in (s, q))
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    else:
+        assert out.shape == (B, Ho, Wo, Cout) and out.dtype == x.dtype and out.is_contiguous() and out.device == x.device
+    if stats and s is None:
         s, q = _stat_pair(Cout, x.device)
     if residual is not None:
         assert residual.shape == out.shape and residual.is_contiguous() and residual.dtype == x.dtype
@@ -1042,10 +1050,15 @@ def affine_act_nhwc(a, sa=None, ta=None, b=None, sb=None, tb=None, leaky=False, 
 DILATE_KERNEL = True
 
 
-def dilate_nhwc(dy, Hz, Wz, stride):
-    """dz [B, Hz, Wz, C] with dz[:, ::stride, ::stride] = dy and zeros elsewhere (one pass: wmz_dilate_nhwc)."""
+def dilate_nhwc(dy, Hz, Wz, stride, out=None):
+    """dz [B, Hz, Wz, C] with dz[:, ::stride, ::stride] = dy and zeros elsewhere (one pass: wmz_dilate_nhwc).  out: the contiguous
+    [B, Hz, Wz, C] tensor of dy's dtype to write instead of a new one."""
     B, Ho, Wo, C = dy.shape
     dy = dy.contiguous()
+    if out is not None:
+        assert out.shape == (B, Hz, Wz, C) and out.dtype == dy.dtype and out.is_contiguous() and out.device == dy.device
+        L.call('wmz_dilate_nhwc', L.ptr(dy), L.ptr(out), B, Ho, Wo, C, Hz, Wz, stride, L.dtype_code(dy.dtype), L.stream())
+        return out
     if not DILATE_KERNEL or B > 65535 or Hz > 65535:     # (the kernel's grid.y / grid.z limits; A/B: tools/time_vqae_modes.py) the fill + strided copy of torch
         dz = torch.zeros((B, Hz, Wz, C), dtype=dy.dtype, device=dy.device)
         dz[:, 0:(Ho - 1) * stride + 1:stride, 0:(Wo - 1) * stride + 1:stride] = dy
@@ -1090,8 +1103,9 @@ def embed_indexed_bwd(tok, pos, dx, shape, table_shapes, into=None):
     return tabs
 
 
-def conv2d_nhwc_wgrad(x, dy, KH, KW, stride, pad, want_bias, into=None):
+def conv2d_nhwc_wgrad(x, dy, KH, KW, stride, pad, want_bias, into=None, out=None):
     """x [B,Hi,Wi,Cin8], dy [B,Ho,Wo,Cout8] -> dW fp32 [Cout8, KH*KW*Cin8] (+ dbias fp32 [Cout8]).
+    out = (dW, dbias | None): the contiguous fp32 tensors of those shapes to store into instead of new ones (the plain form only).
     into = (weight_grad [Co, Ci, KH, KW], bias_grad [Co] | None): ACCUMULATE into nn.Conv2d's own gradient tensors instead
     (channel padding cropped, taps transposed by the reduction kernel); returns (None, None)."""
     B, Hi, Wi, Cin = x.shape
@@ -1129,8 +1143,13 @@ def conv2d_nhwc_wgrad(x, dy, KH, KW, stride, pad, want_bias, into=None):
                co, ci, L.ptr(ws), ws.numel(), dt, L.stream())
         return None, None
     ws = _workspace(x.device, need)
-    dw = torch.empty((Cout, KH * KW * Cin), dtype=torch.float32, device=x.device)        # stored, not accumulated: no zero fill
-    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    if out is not None:
+        dw, db = out
+        assert dw.shape == (Cout, KH * KW * Cin) and dw.dtype == torch.float32 and dw.is_contiguous() and dw.device == x.device
+        assert (db is not None) == bool(want_bias) and (db is None or (db.shape == (Cout,) and db.dtype == torch.float32 and db.is_contiguous()))
+    else:
+        dw = torch.empty((Cout, KH * KW * Cin), dtype=torch.float32, device=x.device)        # stored, not accumulated: no zero fill
+        db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
     L.call('wmz_conv2d_nhwc_wgrad_ws', L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(db), B, Hi, Wi, Cin, Cout, KH, KW, stride, pad, 1,
            0, 0, L.ptr(ws), ws.numel(), dt, L.stream())
     return dw, db
