@@ -202,8 +202,11 @@ int wmz_vq_argmin(const float* x, long ldx, const float* codebook, int64_t* idx,
  * wmz_vq_argmin_screened: the same result as wmz_vq_argmin (indices AND minimum distances bit-identical: the reference's fp32
  * summation order decides), computed by screening on the matrix cores + exact re-check (csrc/vq_screen.hip): bf16 head / tail
  * split products with a proven error bound pick each row's code; rows whose two best codes are closer than twice the bound
- * (equal codes, near ties) are re-scanned over the whole codebook in the pinned arithmetic.  Built for embedding_dim 64 and a
- * multiple of 64 codes: wmz_vq_argmin_screened_workspace_bytes returns 0 for any other shape (use wmz_vq_argmin).
+ * (equal codes, near ties) are re-scanned over the whole codebook in the pinned arithmetic.  Built for embedding_dim 16, 32, 64,
+ * 128 and 256 (the table of csrc/vq_screen_widths.h; the bound is a function of the width) and any codebook size C >= 1:
+ * wmz_vq_argmin_screened_workspace_bytes returns > 0 exactly for those widths with N > 0, C >= 1, and 0 for any other shape
+ * (use wmz_vq_argmin); wmz_vq_argmin_screened refuses such a shape with WMZ_ERR_UNSUPPORTED and names the table.  x rows must be
+ * 16-byte aligned (ldx % 4 == 0).
  * workspace: caller-allocated device scratch of that many bytes (contents irrelevant; rewritten by every call).
  * Replaces: vq.py:30-33, :77-87 (codebook_distance + argmin), as wmz_vq_argmin does.
  */

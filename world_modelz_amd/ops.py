@@ -187,8 +187,9 @@ _vq_screen_ws = {}      # device -> byte scratch of the screened nearest-code se
 
 def vq_argmin(x, codebook, need_dist=False, exact_scan=False):
     """x: [N,E] fp32, codebook: [C,E] fp32 -> int64 [N] (+ fp32 min distance), bit-identical to the reference's CPU result.
-    embedding_dim 64 with a multiple of 64 codes: screening on the matrix cores + exact re-check (wmz_vq_argmin_screened);
-    anything else, or exact_scan=True: every (row, code) distance in the pinned fp32 order (wmz_vq_argmin)."""
+    embedding_dim 16 / 32 / 64 / 128 / 256 (csrc/vq_screen_widths.h; the library is asked), any number of codes, 16-byte aligned
+    rows: screening on the matrix cores + exact re-check (wmz_vq_argmin_screened); any other width, or exact_scan=True: every
+    (row, code) distance in the pinned fp32 order (wmz_vq_argmin)."""
     assert x.dtype == torch.float32 and codebook.dtype == torch.float32
     x, N, ldx = _rows(x)
     codebook = codebook.contiguous()

@@ -3,6 +3,8 @@
 Same constructor, buffers (embedding / cluster_size persistent; latent_offsets / activation_count /
 accumulated_error non-persistent) and methods.  Nearest-neighbour search, row gather, EMA statistics and the EMA
 update are HIP kernels; the argmin reproduces the reference's fp32 summation order, so indices are bit-identical.
+The search is the screened one (matrix cores + exact re-check, ops.vq_argmin) at embedding_dim 16 / 32 / 64 / 128 / 256 with any
+num_embeddings -- the per-latent views of a num_latents > 1 quantiser included -- and the full scan at every other width.
 `VectorQuantizerEMA1` of the reference is dead code (never instantiated) and is not provided.
 """
 import torch
