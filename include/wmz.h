@@ -726,6 +726,36 @@ int wmz_sample_tokens_filtered_dev(const float* logits, long ld, int R, int C, i
                                    long rows_per_block, long block_stride, int64_t* denoised, unsigned char* last_mask,
                                    const float* uniforms, float* kept_floor,
                                    unsigned long long seed, const long long* counter, void* stream);
+/* Confidence-ordered re-masking: the sampler step as TWO launches, the draw with a score per row and a per-clip selection of the
+ * lowest scores, instead of the position-blind u1 > alpha.  Per step, alpha = alphas[*counter % n_alpha] as above.
+ *   draw      exactly wmz_sample_tokens_filtered_dev's (scale, top-k, w = exp(l - max), nucleus, inverse CDF from u0): the same
+ *             logits, filters and uniforms give the same denoised[R], bit for bit.  NO re-mask here: out_tokens receives the draws.
+ *   score     scores[r] = (l_d - max) - log(sum over ALL classes c of exp(l_c - max)), l the scaled logits BEFORE top-k and the
+ *             nucleus, d the draw: the log-probability of the draw under the unfiltered tempered softmax (-inf logits weigh 0).
+ *             Not over the kept set: under top_k = 1 that probability is 1 in every row and would order nothing.
+ *   noise     noise > 0: score += noise * (1 - alpha) * g, g = -log(-log(u1)), u1 the row's second uniform (the one the random
+ *             re-mask compares with alpha: the same Philox position, or uniforms[2 r + 1]); u1 = 0 gives -inf, so that row is
+ *             re-masked first.  noise == 0: the term is not evaluated (no 0 * inf).  A NaN score is stored as -inf.
+ *   selection wmz_remask_lowest_dev, one clip per rows_per_block rows of scores[R] (R a multiple of rows_per_block):
+ *             m = (int)floorf((1.0f - alpha) * (float)rows_per_block), the subtract and the multiply two separate fp32 operations.
+ *             Candidates: every row of the clip, or with `last_mask` the rows whose byte is non-zero.  The min(m, #candidates)
+ *             candidates with the LOWEST scores get mask_token in out_tokens (addressed as above); the order is that of the
+ *             order-preserving key of the score's bits (all bits of a negative flipped, the sign bit of the others set: the
+ *             transform of top-k's search), ties go to the LOWER row index first.  last_mask, when given, becomes 1 exactly
+ *             there and 0 elsewhere.  alpha = 1 re-masks nothing, alpha = 0 every candidate.  Exact given the fp32 scores in
+ *             memory: no tolerance applies.  One workgroup per clip (one wave up to 256 rows): scores and candidate bytes read once, the
+ *             keys held in registers, the m-th smallest key by the bitwise threshold search (wave ballots, the waves' counts
+ *             through LDS), ties ranked by a prefix count in row order.  Up to wmz_remask_lowest_max_rows()
+ *             = 4096 rows per clip; more: WMZ_ERR_UNSUPPORTED, nothing written.
+ * Neither launch advances the counter (the caller does, behind the pair); both only enqueue and allocate nothing. */
+int wmz_sample_tokens_scored_dev(const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
+                                 const float* alphas, int n_alpha, int64_t* out_tokens, long rows_per_block, long block_stride,
+                                 int64_t* denoised, float* scores, float noise, const float* uniforms, float* kept_floor,
+                                 unsigned long long seed, const long long* counter, void* stream);
+int wmz_remask_lowest_max_rows(void);
+int wmz_remask_lowest_dev(const float* scores, int R, long rows_per_block, const float* alphas, int n_alpha, int64_t mask_token,
+                          int64_t* out_tokens, long block_stride, unsigned char* last_mask, const long long* counter,
+                          void* stream);
 /* CrossEntropyLoss(reduction='none') over fp32 logits [R, C] (row stride ld): loss[R], lse[R]; and its gradient
  * dlogits[r,c] = (softmax - one_hot) * grad_rows[r], written in `dtype` (the GEMM operand type of the backward). */
 int wmz_ce_fwd(const float* logits, long ld, const int64_t* target, float* loss, float* lse, long R, int C, void* stream);

@@ -54,10 +54,41 @@ struct SampleExtras {
   float* kept_floor;
 };
 
+// The scored form (wmz_sample_tokens_scored_dev; include/wmz.h states the law): a ScoreOut behind the SampleExtras compiles in
+//   * SCORED: the sum of exp(l - max) over ALL classes, taken before top-k overwrites the values where a filter acts (else it is the
+//     draw's own total), the drawn class's scaled logit read back from the row, score = (l_d - max) - log(sum) (+ the Gumbel term
+//     from u1 with noise > 0) to `scores`; the draw goes to out_tokens as it is: no re-mask (wmz_remask_lowest_dev does that).
+struct ScoreOut {
+  float* scores;
+  float noise;
+};
+
 __device__ __forceinline__ SampleExtras sample_extras() { return SampleExtras{}; }
 __device__ __forceinline__ SampleExtras sample_extras(const SampleExtras& x) { return x; }
+__device__ __forceinline__ SampleExtras sample_extras(const SampleExtras& x, const ScoreOut&) { return x; }
+__device__ __forceinline__ ScoreOut score_out() { return ScoreOut{}; }
+__device__ __forceinline__ ScoreOut score_out(const SampleExtras&) { return ScoreOut{}; }
+__device__ __forceinline__ ScoreOut score_out(const SampleExtras&, const ScoreOut& s) { return s; }
 
-// (`extras`: nothing -- the kernel of wmz_sample_tokens_dev, its arguments as they always were -- or one SampleExtras)
+// a product / a difference that the law rounds on its own: never one half of a contracted multiply-add
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
+// score of a drawn row: lp = (l_d - max) - log(sum over all classes); NaN -> -inf
+__device__ __forceinline__ float sample_score(float l_d, float m, float sum_all, float noise, float alpha, float u1) {
+  float s = sub_rn(l_d, m) - logf(sum_all);
+  if (noise > 0.f) s += noise * (1.f - alpha) * -logf(-logf(u1));
+  return s == s ? s : -INFINITY;
+}
+
+// (`extras`: nothing -- the kernel of wmz_sample_tokens_dev, its arguments as they always were --, one SampleExtras, or a
+//  SampleExtras and a ScoreOut: the scored form)
 template <int NV, bool TEMP = false, bool TOPP = false, typename... Extras>
 __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restrict__ logits, long ld, int R, int C, int top_k,
                                                             const float* __restrict__ alphas, int n_alpha, int64_t mask_token,
@@ -65,9 +96,11 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
                                                             long block_stride, int64_t* __restrict__ denoised,
                                                             unsigned char* __restrict__ last_mask, unsigned long long seed,
                                                             const long long* __restrict__ counter, Extras... extras) {
-  static_assert(sizeof...(Extras) <= 1 && (sizeof...(Extras) == 1 || !(TEMP || TOPP)), "the filters read their values from a SampleExtras");
-  constexpr bool PROBES = sizeof...(Extras) == 1;
+  static_assert(sizeof...(Extras) <= 2 && (sizeof...(Extras) >= 1 || !(TEMP || TOPP)), "the filters read their values from a SampleExtras");
+  constexpr bool PROBES = sizeof...(Extras) >= 1;
+  constexpr bool SCORED = sizeof...(Extras) == 2;
   const SampleExtras x = sample_extras(extras...);
+  const ScoreOut so = score_out(extras...);
   const int lane = threadIdx.x & 63;
   const long ctr = *counter;
   const float alpha = alphas[(int)(ctr % n_alpha)];
@@ -87,6 +120,21 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
     if constexpr (TEMP) {
 #pragma unroll
       for (int e = 0; e < NV; ++e) v[e] *= x.inv_temperature;            // (-inf stays -inf: inv_temperature > 0)
+    }
+    const bool all_kept = !TOPP && !(top_k > 0 && top_k < C);    // no filter acts: the draw's total is the sum over all classes
+    float sum_all = 0.f;
+    if constexpr (SCORED) {
+      if (!all_kept) {
+        float m0 = v[0];
+#pragma unroll
+        for (int e = 1; e < NV; ++e) m0 = fmaxf(m0, v[e]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m0 = fmaxf(m0, __shfl_xor(m0, o));
+        float part = 0.f;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) part += __expf(sub_rn(v[e], m0));           // (no contraction with the scaling: l is the rounded product)
+        sum_all = wave_sum(part);
+      }
     }
     if (top_k > 0 && top_k < C) {
       // order-preserving keys: flip all bits of negatives, the sign bit of non-negatives
@@ -166,7 +214,15 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
         if (lane == 0) x.kept_floor[row] = f;
       }
     }
-    if (lane == 0) {
+    if constexpr (SCORED) {
+      if (lane == 0) {
+        const float l_d = TEMP ? mul_rn(logits[row * ld + draw], x.inv_temperature) : logits[row * ld + draw];
+        so.scores[row] = sample_score(l_d, m, all_kept ? total : sum_all, so.noise, alpha, u[1]);
+        denoised[row] = draw;
+        const long blk = row / rows_per_block;
+        out_tokens[blk * block_stride + (row - blk * rows_per_block)] = (int64_t)draw;
+      }
+    } else if (lane == 0) {
       bool mask = u[1] > alpha;
       if (last_mask != nullptr) { mask = mask && last_mask[row] != 0; last_mask[row] = mask ? 1 : 0; }
       denoised[row] = draw;
@@ -189,6 +245,8 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
 //     and the draw: the FIRST KEPT class whose cumulative weight exceeds u0 * total (the last kept one if rounding leaves none):
 //     a class of weight 0 is never drawn, whatever the rounding of the partial sums.
 // The kept_floor probe alone walks the global row a second time (the keys are gone by then): it is NULL in production.
+// (`score`: nothing, or one ScoreOut -- the scored form: where a filter acts, one more walk of the thread's slots in front of top-k
+//  sums exp(l - max) over all classes; else that sum is the draw's total.)
 constexpr int SW_NT = 256;
 constexpr int SW_MAX_CLASSES = 16384;
 constexpr int SW_RED_WORDS = 16;          // two alternating sets of (SW_NT / 64 waves) x 2 words behind the row
@@ -214,6 +272,7 @@ struct SwExchange {
   }
 };
 
+template <typename... Score>
 __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* __restrict__ logits, long ld, int R, int C, int P, int top_k,
                                                                    float top_p, float inv_temperature,
                                                                    const float* __restrict__ alphas, int n_alpha, int64_t mask_token,
@@ -221,7 +280,11 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
                                                                    long block_stride, int64_t* __restrict__ denoised,
                                                                    unsigned char* __restrict__ last_mask,
                                                                    const float* __restrict__ uniforms, float* __restrict__ kept_floor,
-                                                                   unsigned long long seed, const long long* __restrict__ counter) {
+                                                                   unsigned long long seed, const long long* __restrict__ counter,
+                                                                   Score... score) {
+  static_assert(sizeof...(Score) <= 1, "one ScoreOut at the most");
+  constexpr bool SCORED = sizeof...(Score) == 1;
+  const ScoreOut so = score_out(SampleExtras{}, score...);
   typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
   extern __shared__ __attribute__((aligned(16))) unsigned sw_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -254,6 +317,20 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
     for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o));
     exchange(kmax, 0u, ra, rb);
     const float m = sw_unkey(max(max(ra[0], ra[1]), max(ra[2], ra[3])));
+    const bool all_kept = !(top_p < 1.f) && !(top_k > 0 && top_k < C);
+    float sum_all = 0.f;
+    if constexpr (SCORED) {
+      if (!all_kept) {
+        float part = 0.f;
+        for (int q = 0; q < nq; ++q) {
+          const u32x4 k = mine[q];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) part += __expf(sub_rn(sw_unkey(k[i]), m));
+        }
+        exchange(__float_as_uint(wave_sum(part)), 0u, ra, rb);
+        sum_all = (__uint_as_float(ra[0]) + __uint_as_float(ra[1])) + (__uint_as_float(ra[2]) + __uint_as_float(ra[3]));
+      }
+    }
     unsigned Tk = 0;
     if (top_k > 0 && top_k < C) {
       for (int bit = 31; bit >= 0; --bit) {
@@ -365,7 +442,14 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
       exchange(kmin, 0u, ra, rb);
       if (tid == 0) kept_floor[row] = sw_unkey(min(min(ra[0], ra[1]), min(ra[2], ra[3])));
     }
-    if (tid == 0) {
+    if constexpr (SCORED) {
+      if (tid == 0) {
+        so.scores[row] = sample_score(mul_rn(x[draw], inv_temperature), m, all_kept ? total : sum_all, so.noise, alpha, u[1]);
+        denoised[row] = draw;
+        const long blk = row / rows_per_block;
+        out_tokens[blk * block_stride + (row - blk * rows_per_block)] = (int64_t)draw;
+      }
+    } else if (tid == 0) {
       bool mask = u[1] > alpha;
       if (last_mask != nullptr) { mask = mask && last_mask[row] != 0; last_mask[row] = mask ? 1 : 0; }
       denoised[row] = draw;
@@ -373,6 +457,122 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
       out_tokens[blk * block_stride + (row - blk * rows_per_block)] = mask ? mask_token : (int64_t)draw;
     }
     __syncthreads();                                           // (the next row is staged over slots other threads own)
+  }
+}
+
+// The selection behind the scored draw (wmz_remask_lowest_dev; include/wmz.h states the law): one workgroup of NW waves per clip of
+// n rows, NW = 1 up to 256 rows (no LDS, no barrier in the search: the config-4 planes), 4 up to RM_MAX_ROWS.  Thread t owns the rows
+// j * NT + t, j < MAXP: their keys (sw_key of the score: ascending like the scores) are read ONCE, coalesced, into MAXP registers --
+// a non-candidate or a row past the clip as 0xFFFFFFFF, which no search step counts -- and the candidate bits into one more; a
+// search step is then MAXP compares and ballots without a memory access (a first form that kept the keys in LDS spent ~140 ns per
+// key read and ballot, one wave per SIMD having nothing to hide the LDS latency behind: 18 us at 256 rows, 67 us at 4096).
+//   * V = the mm-th smallest candidate key, mm = min(m, #candidates), by the bitwise search: bit by bit from the top, V takes the
+//     bit while fewer than mm candidate keys lie below V | bit (counts by wave ballots, the waves' counts through LDS);
+//   * keys below V are re-masked; of the keys equal to V the first mm - #{key < V} in ROW order: row order is j-major, so the rank
+//     of a tie is the ties of all earlier (j, wave) groups -- one count each in LDS -- plus the ties of lower lanes in its own ballot.
+constexpr int RM_MAX_ROWS = 4096;
+constexpr int RM_ONE_WAVE_ROWS = 256;
+
+template <int NW>
+struct RmTotal {                      // the workgroup's sum of one count per wave (SwExchange's alternating sets; NW == 1: the wave's own)
+  unsigned* red;
+  int turn;
+  __device__ __forceinline__ unsigned operator()(unsigned wave_count) {
+    if constexpr (NW == 1) {
+      return wave_count;
+    } else {
+      unsigned* set = red + (turn & 1) * NW;
+      turn ^= 1;
+      if ((threadIdx.x & 63) == 0) set[threadIdx.x >> 6] = wave_count;
+      __syncthreads();
+      unsigned t = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) t += set[w];
+      return t;
+    }
+  }
+};
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void remask_lowest_kernel(const float* __restrict__ scores, long n,
+                                                                const float* __restrict__ alphas, int n_alpha, int64_t mask_token,
+                                                                int64_t* __restrict__ out_tokens, long block_stride,
+                                                                unsigned char* __restrict__ last_mask,
+                                                                const long long* __restrict__ counter) {
+  constexpr int NT = 64 * NW;
+  constexpr int MAXP = (NW == 1 ? RM_ONE_WAVE_ROWS : RM_MAX_ROWS) / NT;
+  __shared__ unsigned ties[MAXP * NW];
+  __shared__ unsigned red[2 * NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int rows = (int)n, P = (rows + NT - 1) / NT;                         // (P <= MAXP: the launch's check)
+  const long clip = blockIdx.x;
+  const float alpha = alphas[(int)(*counter % n_alpha)];
+  const int m = (int)floorf(mul_rn(sub_rn(1.0f, alpha), (float)rows));
+  RmTotal<NW> total{red, 0};
+  unsigned key[MAXP];                                                        // 0xFFFFFFFF where the row is no candidate
+  unsigned cand = 0;                                                         // bit j: row j * NT + tid is a candidate
+  unsigned ncand = 0;
+#pragma unroll
+  for (int j = 0; j < MAXP; ++j) {
+    const int row = j * NT + tid;
+    bool c = false;
+    key[j] = 0xFFFFFFFFu;
+    if (j < P && row < rows) {
+      c = last_mask == nullptr || last_mask[clip * n + row] != 0;
+      if (c) key[j] = sw_key(scores[clip * n + row]);
+    }
+    cand |= (c ? 1u : 0u) << j;
+    if (j < P) ncand += (unsigned)__popcll(__ballot(c));
+  }
+  ncand = total(ncand);
+  const unsigned mm = m <= 0 ? 0u : ((unsigned)m < ncand ? (unsigned)m : ncand);
+  unsigned V = 0, need = 0;
+  if (mm > 0) {                                                              // (uniform over the workgroup: the barriers inside are met by all)
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned cv = V | (1u << bit);
+      unsigned cnt = 0;
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j)                                          // (one wave: all four, without a branch: a key past P counts nothing)
+        if (NW == 1 || j < P) cnt += (unsigned)__popcll(__ballot(key[j] < cv));
+      if (total(cnt) < mm) V = cv;
+    }
+    unsigned below = 0;
+#pragma unroll
+    for (int j = 0; j < MAXP; ++j) {
+      if (j < P) {
+        below += (unsigned)__popcll(__ballot(key[j] < V));
+        const unsigned long long tb = __ballot(((cand >> j) & 1u) != 0 && key[j] == V);
+        if (lane == 0) ties[j * NW + wave] = (unsigned)__popcll(tb);
+      }
+    }
+    need = mm - total(below);                                                // (>= 1; its barrier also publishes `ties` where NW > 1)
+    if constexpr (NW == 1) __syncthreads();                                  // (one wave: no exchange above, so publish `ties` here)
+  }
+  unsigned run = 0;                                                          // ties of the groups in front of (j, wave)
+#pragma unroll
+  for (int j = 0; j < MAXP; ++j) {
+    if (j < P) {
+      const int row = j * NT + tid;
+      const bool c = ((cand >> j) & 1u) != 0;
+      bool masked = false;
+      if (mm > 0) {
+        const bool tie = c && key[j] == V;
+        const unsigned long long tb = __ballot(tie);
+        unsigned before = run;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          const unsigned t = ties[j * NW + w];
+          if (w < wave) before += t;
+          run += t;
+        }
+        const unsigned rank = before + (unsigned)__popcll(tb & ((1ull << lane) - 1ull));
+        masked = c && (key[j] < V || (tie && rank < need));
+      }
+      if (row < rows) {
+        if (masked) out_tokens[clip * block_stride + row] = mask_token;
+        if (last_mask != nullptr) last_mask[clip * n + row] = masked ? 1 : 0;
+      }
+    }
   }
 }
 
@@ -503,24 +703,43 @@ extern "C" int wmz_corrupt_tokens_dev(const int64_t* z_last, long clip_stride, c
 static int sample_tokens_launch(const char* name, const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
                                 const float* alphas, int n_alpha, int64_t mask_token, int64_t* out_tokens, long rows_per_block,
                                 long block_stride, int64_t* denoised, unsigned char* last_mask, const float* uniforms,
-                                float* kept_floor, unsigned long long seed, const long long* counter, void* stream) {
+                                float* kept_floor, unsigned long long seed, const long long* counter, void* stream,
+                                const ScoreOut* score = nullptr) {
   hipStream_t st = (hipStream_t)stream;
   const bool temp = inv_temperature != 1.f, topp = top_p < 1.f;
   if (C > 2048) {
     const int P = (wmz_cdiv(C, SW_NT) + 7) / 8 * 8;
     const size_t smem = ((size_t)SW_NT * (P + 4) + SW_RED_WORDS) * 4;
     static std::atomic<uint64_t> attr_devs{0};                       // (> 64 KB of dynamic LDS has to be asked for once per device)
-    if (wmz_first_use_on_device(attr_devs))
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tokens_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(((size_t)SW_NT * (SW_MAX_CLASSES / SW_NT + 4) + SW_RED_WORDS) * 4));
-    hipLaunchKernelGGL(sample_tokens_wide_kernel, dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R, C, P, top_k, top_p,
-                       inv_temperature, alphas, n_alpha, mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask,
-                       uniforms, kept_floor, seed, counter);
+    if (wmz_first_use_on_device(attr_devs)) {
+      const int most = (int)(((size_t)SW_NT * (SW_MAX_CLASSES / SW_NT + 4) + SW_RED_WORDS) * 4);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tokens_wide_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tokens_wide_kernel<ScoreOut>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                most);
+    }
+    if (score == nullptr)
+      hipLaunchKernelGGL(sample_tokens_wide_kernel<>, dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R, C, P, top_k, top_p,
+                         inv_temperature, alphas, n_alpha, mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask,
+                         uniforms, kept_floor, seed, counter);
+    else
+      hipLaunchKernelGGL(sample_tokens_wide_kernel<ScoreOut>, dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R, C, P, top_k,
+                         top_p, inv_temperature, alphas, n_alpha, mask_token, out_tokens, rows_per_block, block_stride, denoised,
+                         last_mask, uniforms, kept_floor, seed, counter, *score);
     WMZ_LAUNCH_CHECK(name);
     return WMZ_OK;
   }
   const int grid = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
-  if (!temp && !topp && uniforms == nullptr && kept_floor == nullptr) {
+  if (score != nullptr) {
+    const SampleExtras x = {top_p, inv_temperature, uniforms, kept_floor};
+#define WMZ_SMP(NV, TEMP, TOPP) hipLaunchKernelGGL((sample_tokens_kernel<NV, TEMP, TOPP, SampleExtras, ScoreOut>), dim3(grid), dim3(256), 0, st, logits, ld, \
+                                                   R, C, top_k, alphas, n_alpha, mask_token, out_tokens, rows_per_block, block_stride,             \
+                                                   denoised, last_mask, seed, counter, x, *score)
+#define WMZ_SMP_NV(TEMP, TOPP) \
+  do { if (C <= 256) WMZ_SMP(4, TEMP, TOPP); else if (C <= 512) WMZ_SMP(8, TEMP, TOPP); else if (C <= 1024) WMZ_SMP(16, TEMP, TOPP); else WMZ_SMP(32, TEMP, TOPP); } while (0)
+    if (temp && topp) WMZ_SMP_NV(true, true); else if (temp) WMZ_SMP_NV(true, false); else if (topp) WMZ_SMP_NV(false, true); else WMZ_SMP_NV(false, false);
+#undef WMZ_SMP_NV
+#undef WMZ_SMP
+  } else if (!temp && !topp && uniforms == nullptr && kept_floor == nullptr) {
 #define WMZ_SMP(NV) hipLaunchKernelGGL(sample_tokens_kernel<NV>, dim3(grid), dim3(256), 0, st, logits, ld, R, C, top_k, alphas, n_alpha, \
                                        mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask, seed, counter)
     if (C <= 256) WMZ_SMP(4); else if (C <= 512) WMZ_SMP(8); else if (C <= 1024) WMZ_SMP(16); else WMZ_SMP(32);
@@ -576,6 +795,51 @@ extern "C" int wmz_sample_tokens_filtered_dev(const float* logits, long ld, int 
   return sample_tokens_launch("wmz_sample_tokens_filtered_dev", logits, ld, R, C, top_k, top_p, inv_temperature, alphas, n_alpha,
                               mask_token, out_tokens, rows_per_block, block_stride, denoised, last_mask, uniforms, kept_floor, seed,
                               counter, stream);
+}
+
+extern "C" int wmz_sample_tokens_scored_dev(const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
+                                            const float* alphas, int n_alpha, int64_t* out_tokens, long rows_per_block,
+                                            long block_stride, int64_t* denoised, float* scores, float noise, const float* uniforms,
+                                            float* kept_floor, unsigned long long seed, const long long* counter, void* stream) {
+  WMZ_REQUIRE(logits && alphas && out_tokens && denoised && scores && counter && R > 0 && C > 0 && n_alpha > 0 && rows_per_block > 0,
+              "wmz_sample_tokens_scored_dev: bad arguments");
+  WMZ_REQUIRE(ld >= C && ld % 4 == 0 && (((uintptr_t)logits) & 15) == 0,
+              "wmz_sample_tokens_scored_dev: logits rows must be 16-byte aligned");
+  WMZ_REQUIRE(inv_temperature > 0.f && inv_temperature < INFINITY,
+              "wmz_sample_tokens_scored_dev: inv_temperature must be positive and finite (got %g)", (double)inv_temperature);
+  WMZ_REQUIRE(top_p > 0.f, "wmz_sample_tokens_scored_dev: top_p must be positive (got %g)", (double)top_p);
+  WMZ_REQUIRE(noise >= 0.f && noise < INFINITY, "wmz_sample_tokens_scored_dev: noise must be non-negative and finite (got %g)",
+              (double)noise);
+  if (C > SW_MAX_CLASSES) {
+    wmz_set_error("wmz_sample_tokens_scored_dev: built for <= %d classes (got %d)", SW_MAX_CLASSES, C);
+    return WMZ_ERR_UNSUPPORTED;
+  }
+  const ScoreOut score = {scores, noise};
+  return sample_tokens_launch("wmz_sample_tokens_scored_dev", logits, ld, R, C, top_k, top_p, inv_temperature, alphas, n_alpha, 0,
+                              out_tokens, rows_per_block, block_stride, denoised, nullptr, uniforms, kept_floor, seed, counter, stream,
+                              &score);
+}
+
+extern "C" int wmz_remask_lowest_max_rows(void) { return RM_MAX_ROWS; }
+
+extern "C" int wmz_remask_lowest_dev(const float* scores, int R, long rows_per_block, const float* alphas, int n_alpha,
+                                     int64_t mask_token, int64_t* out_tokens, long block_stride, unsigned char* last_mask,
+                                     const long long* counter, void* stream) {
+  WMZ_REQUIRE(scores && alphas && out_tokens && counter && R > 0 && n_alpha > 0 && rows_per_block > 0 && R % rows_per_block == 0,
+              "wmz_remask_lowest_dev: bad arguments");
+  if (rows_per_block > RM_MAX_ROWS) {
+    wmz_set_error("wmz_remask_lowest_dev: built for <= %d rows per clip (got %ld)", RM_MAX_ROWS, rows_per_block);
+    return WMZ_ERR_UNSUPPORTED;
+  }
+  const int clips = (int)(R / rows_per_block);
+  if (rows_per_block <= RM_ONE_WAVE_ROWS)
+    hipLaunchKernelGGL(remask_lowest_kernel<1>, dim3(clips), dim3(64), 0, (hipStream_t)stream, scores, rows_per_block, alphas, n_alpha,
+                       mask_token, out_tokens, block_stride, last_mask, counter);
+  else
+    hipLaunchKernelGGL(remask_lowest_kernel<4>, dim3(clips), dim3(256), 0, (hipStream_t)stream, scores, rows_per_block, alphas, n_alpha,
+                       mask_token, out_tokens, block_stride, last_mask, counter);
+  WMZ_LAUNCH_CHECK("wmz_remask_lowest_dev");
+  return WMZ_OK;
 }
 
 extern "C" int wmz_ce_fwd(const float* logits, long ld, const int64_t* target, float* loss, float* lse, long R, int C,

@@ -333,6 +333,58 @@ def sample_tokens(logits, top_k, alphas, mask_token, last_frame, denoised, count
            int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream())
 
 
+def remask_max_rows():
+    """The most rows per clip the lowest-score selection takes (wmz_remask_lowest_dev): the library's own figure."""
+    return L.lib().wmz_remask_lowest_max_rows()
+
+
+_score_ws = {}
+
+
+def _scores(device, R):
+    """fp32 scores of the confidence re-mask (one buffer per device, grown on demand; the two launches of a step run in stream
+    order)."""
+    w = _score_ws.get(device)
+    if w is None or w.numel() < R:
+        w = _score_ws[device] = torch.empty(R, dtype=torch.float32, device=device)
+    return w[:R]
+
+
+def remask_lowest(scores, alphas, mask_token, last_frame, counter, last_mask=None):
+    """wmz_remask_lowest_dev: per clip (a row of last_frame [B, H, W], int64, written in place) the min(m, #candidates) candidates with
+    the lowest scores (fp32 [B * H * W]) get mask_token, m = floor((1 - alpha) * H * W) and alpha = alphas[counter % n]; last_mask
+    (uint8 [R] or None) names the candidates and receives the new mask.  include/wmz.h states the law."""
+    R = scores.numel()
+    B = last_frame.shape[0]
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and last_frame.dtype == torch.int64 and R % B == 0
+    assert last_frame[0].is_contiguous() and last_frame[0].numel() == R // B and counter.dtype == torch.int64
+    assert last_mask is None or (last_mask.dtype == torch.uint8 and last_mask.is_contiguous() and last_mask.numel() == R)
+    L.call('wmz_remask_lowest_dev', L.ptr(scores), R, R // B, L.ptr(alphas), alphas.numel(), int(mask_token), L.ptr(last_frame),
+           last_frame.stride(0), L.ptr(last_mask), L.ptr(counter), L.stream())
+
+
+def sample_tokens_confidence(logits, top_k, alphas, mask_token, last_frame, denoised, counter, seed, last_mask=None, *, top_p=1.0,
+                             temperature=1.0, noise=0.0, uniforms=None, kept_floor=None, scores=None):
+    """The sampler step with confidence-ordered re-masking, as two launches (include/wmz.h states the law): the draw of
+    sample_tokens with the log-probability of each draw under the unfiltered tempered softmax written to `scores` (plus
+    noise * (1 - alpha) * Gumbel(u1) with noise > 0) and no re-mask (wmz_sample_tokens_scored_dev), then per clip the
+    floor((1 - alpha) * rows) lowest-scored candidates back to mask_token (wmz_remask_lowest_dev).  The arguments of sample_tokens
+    keep their meaning; scores: fp32 [R] buffer of the caller's (tests), else a per-device workspace."""
+    R, C = logits.shape
+    B = last_frame.shape[0]
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and last_frame.dtype == torch.int64
+    assert last_frame[0].is_contiguous() and R % B == 0 and denoised.numel() == R and counter.dtype == torch.int64
+    assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.shape == (R, 2))
+    assert kept_floor is None or (kept_floor.dtype == torch.float32 and kept_floor.is_contiguous() and kept_floor.numel() == R)
+    if scores is None:
+        scores = _scores(logits.device, R)
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == R
+    L.call('wmz_sample_tokens_scored_dev', L.ptr(logits), logits.stride(0), R, C, int(top_k), float(top_p), 1.0 / float(temperature),
+           L.ptr(alphas), alphas.numel(), L.ptr(last_frame), R // B, last_frame.stride(0), L.ptr(denoised), L.ptr(scores), float(noise),
+           L.ptr(uniforms), L.ptr(kept_floor), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream())
+    remask_lowest(scores, alphas, mask_token, last_frame, counter, last_mask)
+
+
 _vq_ws = {}
 
 

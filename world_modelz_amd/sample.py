@@ -42,10 +42,65 @@ def categorical_from_uniform(p, u):
     return (cdf <= x).sum(dim=-1).clamp(max=p.shape[-1] - 1)
 
 
+# Confidence-ordered re-masking, the torch form of the law that include/wmz.h states next to wmz_sample_tokens_scored_dev and
+# wmz_remask_lowest_dev: what the torch path of sample_frames applies and what the two kernels are held to.
+
+def drawn_log_prob(logits, draws):
+    """Score of each row's draw: its log-probability under the softmax of `logits` [R, C] -- the scaled logits BEFORE top-k and the
+    nucleus -- in fp32 (log_softmax gathered at draws [R]).  Over all classes, not the kept set: under top-k = 1 the kept-set
+    probability is 1 in every row and would order nothing."""
+    return F.log_softmax(logits.float(), dim=-1).gather(-1, draws.reshape(-1, 1)).squeeze(-1)
+
+
+def gumbel_from_uniform(u):
+    """g = -log(-log(u)) in fp32 for u in [0, 1): u = 0 gives -inf (that row is re-masked first)."""
+    return -torch.log(-torch.log(u.float()))
+
+
+def confidence_scores(logits, draws, alpha, noise=0.0, u=None):
+    """drawn_log_prob, plus noise * (1 - alpha) * gumbel_from_uniform(u) where noise > 0 (fp32 throughout; with noise == 0 the term
+    is not evaluated: no 0 * inf); a NaN score becomes -inf."""
+    s = drawn_log_prob(logits, draws)
+    if noise > 0:
+        one, a = torch.tensor(1.0, dtype=torch.float32), torch.tensor(alpha, dtype=torch.float32)
+        s = s + (torch.tensor(noise, dtype=torch.float32) * (one - a)).to(s.device) * gumbel_from_uniform(u.reshape(-1))
+    return torch.where(s != s, torch.full_like(s, -float('inf')), s)
+
+
+def remask_count(alpha, rows):
+    """m = floor((1 - alpha) * rows) as the kernel computes it: alpha and rows in fp32, one subtract, one multiply."""
+    one, a = torch.tensor(1.0, dtype=torch.float32), torch.tensor(alpha, dtype=torch.float32)
+    return int(torch.floor((one - a) * torch.tensor(float(rows), dtype=torch.float32)))
+
+
+def score_keys(scores):
+    """Order-preserving integer key of an fp32 score's bits (all bits of a negative flipped, the sign bit of the others set -- the
+    transform of the kernels' threshold searches), as int64: -inf < ... < -0.0 < +0.0 < ... < +inf, NaNs by their bits."""
+    b = scores.float().contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    return torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b + 0x80000000)
+
+
+def lowest_scores_mask(scores, alpha, candidates=None):
+    """Which positions go back to the mask token: per clip (row of scores [B, HW]) the min(m, #candidates) candidates with the lowest
+    scores, m = remask_count(alpha, HW); candidates: bool [B, HW] (default: all).  Order by score_keys, ties to the lower index.
+    -> bool [B, HW]."""
+    B, HW = scores.shape
+    m = remask_count(alpha, HW)
+    cand = torch.ones(B, HW, dtype=torch.bool, device=scores.device) if candidates is None else candidates.to(torch.bool)
+    idx = torch.arange(HW, device=scores.device)
+    # one unique sort key per position: (non-candidates last, key, index)
+    order = (torch.where(cand, score_keys(scores), torch.full((), 1 << 32, dtype=torch.int64, device=scores.device)) * HW + idx).argsort(dim=-1)
+    rank = torch.empty_like(order).scatter_(-1, order, idx.expand(B, HW))
+    return cand & (rank < cand.sum(-1, keepdim=True).clamp(max=m))
+
+
+REMASK_MODES = ('random', 'confidence')
+
+
 @torch.no_grad()
 def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iterations=30, sample_topk=-1, noise_schedule=None,
                   consistent_masking=False, generator=None, use_graph=True, uniforms=None, trace=None, temperature=1.0,
-                  sample_topp=1.0):
+                  sample_topp=1.0, *, remask='random', remask_noise=0.0):
     """batch_z: int64 [B,S,H,W] context tokens on the GPU (the last frame is overwritten).  Returns the list of generated
     latent frames [B,H,W] (decode them with VqAutoEncoder.decode) and the final batch_z.
 
@@ -54,8 +109,18 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     (main.py:85, :97-100), which makes the loop a deterministic function of its inputs (parity tests); default: device RNG.
     trace: optional list that receives every last frame fed to the model.
     temperature (> 0) divides the logits in front of the filters; sample_topp in (0, 1] is the nucleus filter (top_p_logits)
-    behind top-k: ValueError for anything else.  The defaults leave every draw as it was."""
+    behind top-k: ValueError for anything else.  The defaults leave every draw as it was.
+    remask: 'random' -- the reference's law: a position goes back to the mask token where its uniform exceeds alpha -- or
+    'confidence': per clip exactly the floor((1 - alpha) * H * W) positions whose draws the model was least sure of
+    (confidence_scores + lowest_scores_mask above; with consistent_masking among the positions masked before), the rule of
+    masked-token decoders (MaskGIT).  remask_noise >= 0 (finite) scales the Gumbel noise added to the scores, annealed by
+    (1 - alpha); its uniform is u_mask[f, i] when injected.  ValueError for anything else.  (Config 5's sampler,
+    sparse_diffusion.evaluate_model, has no such option.)"""
     assert batch_z.is_cuda
+    if remask not in REMASK_MODES:
+        raise ValueError(f'remask must be one of {REMASK_MODES} (got {remask!r})')
+    if not 0 <= remask_noise < float('inf'):
+        raise ValueError(f'remask_noise must be non-negative and finite (got {remask_noise})')
     if not temperature > 0 or not temperature < float('inf'):
         raise ValueError(f'temperature must be positive and finite (got {temperature})')
     if not 0 < sample_topp <= 1:
@@ -74,17 +139,19 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
                 g.set_state(st)
             if trace is not None:
                 del trace[:]
-            return sample_frames(*args, trace=trace, temperature=temperature, sample_topp=sample_topp)
-        return half_guard.guarded('sample.sample_frames', model, batch_z.device,
-                                  lambda: sample_frames(*args, trace=trace, temperature=temperature, sample_topp=sample_topp), again)
+            return sample_frames(*args, **kwargs)
+        kwargs = dict(trace=trace, temperature=temperature, sample_topp=sample_topp, remask=remask, remask_noise=remask_noise)
+        return half_guard.guarded('sample.sample_frames', model, batch_z.device, lambda: sample_frames(*args, **kwargs), again)
     B, S, H, W = batch_z.shape
     mask_token = num_embeddings
     batch_z = batch_z.clone()
     batch_z[:, -1] = mask_token                                   # destroy all information in the last frame (:62)
     from . import ops
-    if use_graph and uniforms is None and trace is None and num_embeddings <= ops.sample_max_classes():
+    confidence = remask == 'confidence'
+    if (use_graph and uniforms is None and trace is None and num_embeddings <= ops.sample_max_classes()
+            and (not confidence or H * W <= ops.remask_max_rows())):
         return _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_iterations, sample_topk, noise_schedule,
-                                    consistent_masking, generator, temperature, sample_topp)
+                                    consistent_masking, generator, temperature, sample_topp, remask, remask_noise)
     fwd = GraphedForward(model, batch_z) if use_graph else None
     if fwd is not None:
         batch_z = fwd.static_in                                   # the loop edits the graph's own input buffer: no staging copy
@@ -100,6 +167,7 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
         for i in range(num_eval_iterations):
             if temperature != 1.0:
                 logits = logits * inv_temperature
+            unfiltered = logits
             if sample_topk > 0:
                 logits = top_k_logits(logits, sample_topk)
             logits = top_p_logits(logits, sample_topp)
@@ -110,11 +178,18 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
                 denoised = torch.multinomial(p, 1, True, generator=generator).view(B, H * W)
             frac = (i + 1) / num_eval_iterations
             alpha = min(max(noise_schedule(frac) if noise_schedule is not None else frac, 0.0), 1.0)
-            u = u_mask[f, i].view(B, H * W) if uniforms is not None else torch.rand(B, H * W, device=dev, generator=generator)
-            mask = u > alpha
-            if consistent_masking:
-                mask = last_mask & mask
-                last_mask = mask
+            if not confidence or remask_noise > 0:
+                u = u_mask[f, i].view(B, H * W) if uniforms is not None else torch.rand(B, H * W, device=dev, generator=generator)
+            if confidence:
+                scores = confidence_scores(unfiltered, denoised, alpha, remask_noise, u if remask_noise > 0 else None).view(B, H * W)
+                mask = lowest_scores_mask(scores, alpha, last_mask if consistent_masking else None)
+                if consistent_masking:
+                    last_mask = mask
+            else:
+                mask = u > alpha
+                if consistent_masking:
+                    mask = last_mask & mask
+                    last_mask = mask
             frame = torch.where(mask, torch.full_like(denoised, mask_token), denoised)
             batch_z[:, -1] = frame.view(B, H, W)
             if trace is not None:
@@ -194,7 +269,8 @@ class _Session:
     model across sample_frames calls: capturing costs ~4 ms, a frame of 30 iterations ~11 (GraphedForward re-captures by itself
     when the weights, the compute dtype or the run-time configuration changed)."""
 
-    def __init__(self, model, batch_z, C, n_iter, sample_topk, consistent_masking, temperature=1.0, sample_topp=1.0):
+    def __init__(self, model, batch_z, C, n_iter, sample_topk, consistent_masking, temperature=1.0, sample_topp=1.0, remask='random',
+                 remask_noise=0.0):
         from . import ops
         B, S, H, W = batch_z.shape
         dev = batch_z.device
@@ -204,12 +280,18 @@ class _Session:
         self.denoised = torch.zeros(R, dtype=torch.int64, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
         self.last_mask = torch.ones(R, dtype=torch.uint8, device=dev) if consistent_masking else None
+        self.scores = torch.zeros(R, dtype=torch.float32, device=dev) if remask == 'confidence' else None     # (the graph's own)
         aligned = C % 4 == 0
         holder = {}
 
         def draw(src, z):
-            ops.sample_tokens(src, sample_topk, self.alphas, C, z[:, -1], self.denoised, self.counter, _SEED_KEY, self.last_mask,
-                              top_p=sample_topp, temperature=temperature)
+            if remask == 'confidence':
+                ops.sample_tokens_confidence(src, sample_topk, self.alphas, C, z[:, -1], self.denoised, self.counter, _SEED_KEY,
+                                             self.last_mask, top_p=sample_topp, temperature=temperature, noise=remask_noise,
+                                             scores=self.scores)
+            else:
+                ops.sample_tokens(src, sample_topk, self.alphas, C, z[:, -1], self.denoised, self.counter, _SEED_KEY, self.last_mask,
+                                  top_p=sample_topp, temperature=temperature)
             self.counter.add_(1)
 
         def pre(z):
@@ -226,7 +308,7 @@ class _Session:
 
 
 def _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_iterations, sample_topk, noise_schedule,
-                         consistent_masking, generator, temperature=1.0, sample_topp=1.0):
+                         consistent_masking, generator, temperature=1.0, sample_topp=1.0, remask='random', remask_noise=0.0):
     """The same loop with NO host work inside a frame but one graph launch per iteration: the draw + re-mask step is one
     kernel (wmz_sample_tokens_dev, or wmz_sample_tokens_filtered_dev with a temperature, a nucleus filter or more than 2048 classes
     -- up to ops.sample_max_classes(): temperature, top-k, softmax, top-p, inverse-CDF draw and re-mask per row, uniforms from in-kernel Philox indexed
@@ -236,14 +318,16 @@ def _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_it
     frame's first draw (from the flat start, :71) is one eager launch in front of its replays, and the forward behind a frame's
     LAST draw -- whose logits the reference computes (:111) and never reads -- is not run: n - 1 forwards per frame instead of n.
     The captured step stays with the model between calls (_Session).  Same distribution as the torch path (which stays for
-    injected uniforms: the parity fixtures), different random stream."""
+    injected uniforms: the parity fixtures), different random stream.
+    remask = 'confidence': the step is TWO kernels -- the scored draw (wmz_sample_tokens_scored_dev) and the per-clip selection of the
+    lowest scores (wmz_remask_lowest_dev) -- captured in the same place."""
     B, S, H, W = batch_z.shape
     n = num_eval_iterations
-    key = (B, S, H, W, num_embeddings, n, int(sample_topk), bool(consistent_masking), batch_z.device, float(temperature),
-           float(sample_topp))
+    key = (B, S, H, W, num_embeddings, n, int(sample_topk), bool(consistent_masking), batch_z.device, str(remask), float(remask_noise),
+           float(temperature), float(sample_topp))
     per_model = model.__dict__.setdefault('_wmz_sampler_sessions', _Sessions())
     ses = per_model.touch(key, lambda: _Session(model, batch_z, num_embeddings, n, sample_topk, consistent_masking,
-                                                     temperature, sample_topp))
+                                                     temperature, sample_topp, remask, remask_noise))
     ses.alphas.copy_(torch.tensor([min(max(noise_schedule((i + 1) / n) if noise_schedule is not None else (i + 1) / n, 0.0), 1.0)
                                    for i in range(n)], dtype=torch.float32))
     # The Philox stream is indexed by the counter; a call starts it at a 62-bit draw from the caller's generator (the global CPU
