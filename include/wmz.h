@@ -690,6 +690,37 @@ int wmz_sparse_draw_context(const int64_t* z, long clip_stride, const float* r, 
 int wmz_categorical_scatter(const float* logits, long ld, long R, int C, const int64_t* indices, int64_t* z, long clip_stride,
                             long rows_per_clip, int64_t* samples, unsigned long long seed, unsigned long long stream_id,
                             const unsigned long long* counter, void* stream);
+/* wmz_sparse_draw_context for a clip of which some positions are GIVEN (a prompt): known, optional, bytes [B, S * HW] (clip stride
+ * known_stride), non-zero = given.  The window, the n positions, their order, indices and target are exactly those of
+ * wmz_sparse_draw_context for the same (seed, stream id, counter), and the corruption uniforms come from the same Philox
+ * positions: known shifts no random stream.  For a context slot whose position is given, tokens = target: neither masked nor
+ * redrawn.  known = NULL: wmz_sparse_draw_context, bit for bit (which forwards here). */
+int wmz_sparse_draw_context_known(const int64_t* z, long clip_stride, const float* r, const float* o, int64_t* indices,
+                                  int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
+                                  unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
+                                  void* stream, const unsigned char* known, long known_stride);
+/* wmz_categorical_scatter with a temperature, top-k, a nucleus filter and given positions.  The law per row is the one stated
+ * below for wmz_sample_tokens_filtered_dev, without its re-mask step (config 5 masks when it gathers):
+ *   l = logits * inv_temperature         one fp32 multiply (inv_temperature > 0, finite);
+ *   top-k on l                           top_k <= 0 or >= C: all; ties with the k-th kept;
+ *   w = exp(l - max) over what is left;
+ *   nucleus, 0 < top_p < 1               keep {w >= t}, t the LARGEST weight with mass{w >= t} >= top_p * total (top_p >= 1: no filter);
+ *   draw                                 the first kept class, in class order, whose cumulative kept weight exceeds u0 * total; the
+ *                                        last kept class if rounding leaves none.  A class of weight 0 is never drawn.
+ * u0 = the first word of philox4(row, stream id, seed) as a unit -- the position wmz_categorical_scatter reads, keyed as there --
+ * or uniforms[row] (optional, [R] fp32 in [0, 1)): the call is then a function of its inputs.  kept_floor (optional probe, [R]
+ * fp32): the smallest kept l per row.  samples[row] (optional) always receives the draw; z[(row / rows_per_clip) * clip_stride +
+ * indices[row]] receives it unless known (optional, bytes, clip stride known_stride, addressed like z) is non-zero there.
+ * Neutral arguments -- top_k <= 0 or >= C, top_p >= 1, inv_temperature == 1, no uniforms, no probe -- run the three-pass kernel of
+ * wmz_categorical_scatter at any C and any alignment: its draws, bit for bit, for the same seed, stream id and counter (known is a
+ * branch in its write).  Otherwise 1 <= C <= wmz_sample_tokens_max_classes() and 16-byte aligned rows (ld % 4 == 0), by the two
+ * forms of wmz_sample_tokens_filtered_dev (registers up to 2048 classes, LDS above); more classes: WMZ_ERR_UNSUPPORTED, nothing
+ * written. */
+int wmz_categorical_scatter_filtered(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
+                                     const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip, int64_t* samples,
+                                     const unsigned char* known, long known_stride, const float* uniforms, float* kept_floor,
+                                     unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
+                                     void* stream);
 /* One step of the sampler loop between two forward passes (main.py:76-104): per row of fp32 logits [R, C <= 2048] keep the
  * top_k largest (<= 0: all; ties with the k-th kept), softmax, draw a class by the inverse CDF from one in-kernel uniform,
  * re-mask with a second one: the position gets mask_token where u2 > alpha (and, with `last_mask` [R] bytes, in / out, only

@@ -4,7 +4,9 @@
 //   wmz_ce_fwd / _bwd   main.py:266-274  CrossEntropyLoss(reduction='none') over the last-frame logits and its gradient,
 //                                        written directly in the GEMM operand dtype
 #include "wmz_common.h"
+#include "wmz_internal.h"
 #include "wmz_philox.h"
+#include <type_traits>
 
 namespace {
 
@@ -70,6 +72,30 @@ __device__ __forceinline__ ScoreOut score_out() { return ScoreOut{}; }
 __device__ __forceinline__ ScoreOut score_out(const SampleExtras&) { return ScoreOut{}; }
 __device__ __forceinline__ ScoreOut score_out(const SampleExtras&, const ScoreOut& s) { return s; }
 
+// The sparse form (wmz_categorical_scatter_filtered: config 5's sampler): a SparseOut behind the SampleExtras compiles in
+//   * SPARSE: u0 = uniforms[row] (one a row) or the first word of philox4(row, the SparseOut's stream, seed) -- the position
+//     categorical_scatter_kernel reads --; no alpha, no counter of the dense step, no re-mask; the draw is the first KEPT class past
+//     u0 * total (the last kept one if rounding leaves none) and goes where wmz_sparse_write puts it.
+typedef WmzSparseOut SparseOut;
+__device__ __forceinline__ SampleExtras sample_extras(const SampleExtras& x, const SparseOut&) { return x; }
+__device__ __forceinline__ ScoreOut score_out(const SampleExtras&, const SparseOut&) { return ScoreOut{}; }
+__device__ __forceinline__ SparseOut sparse_out() { return SparseOut{}; }
+template <typename A, typename... Rest>
+__device__ __forceinline__ SparseOut sparse_out(const A& a, const Rest&... rest) {
+  if constexpr (std::is_same<A, SparseOut>::value) return a; else return sparse_out(rest...);
+}
+template <typename T, typename... Ts>
+constexpr bool pack_has = (std::is_same<T, Ts>::value || ...);
+// the dense step's counter and alpha: not read in the sparse form, whose launch passes NULL for both
+template <bool SPARSE>
+__device__ __forceinline__ long dense_counter(const long long* counter) {
+  if constexpr (SPARSE) return 0; else return *counter;
+}
+template <bool SPARSE>
+__device__ __forceinline__ float dense_alpha(const float* alphas, int n_alpha, long ctr) {
+  if constexpr (SPARSE) return 0.f; else return alphas[(int)(ctr % n_alpha)];
+}
+
 // a product / a difference that the law rounds on its own: never one half of a contracted multiply-add
 __device__ __forceinline__ float mul_rn(float a, float b) {
 #pragma clang fp contract(off)
@@ -88,7 +114,8 @@ __device__ __forceinline__ float sample_score(float l_d, float m, float sum_all,
 }
 
 // (`extras`: nothing -- the kernel of wmz_sample_tokens_dev, its arguments as they always were --, one SampleExtras, or a
-//  SampleExtras and a ScoreOut: the scored form)
+//  SampleExtras and a ScoreOut: the scored form, or a SampleExtras and a SparseOut: the sparse form, which leaves the dense
+//  step's own arguments -- alphas .. counter -- unread)
 template <int NV, bool TEMP = false, bool TOPP = false, typename... Extras>
 __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restrict__ logits, long ld, int R, int C, int top_k,
                                                             const float* __restrict__ alphas, int n_alpha, int64_t mask_token,
@@ -98,12 +125,14 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
                                                             const long long* __restrict__ counter, Extras... extras) {
   static_assert(sizeof...(Extras) <= 2 && (sizeof...(Extras) >= 1 || !(TEMP || TOPP)), "the filters read their values from a SampleExtras");
   constexpr bool PROBES = sizeof...(Extras) >= 1;
-  constexpr bool SCORED = sizeof...(Extras) == 2;
+  constexpr bool SCORED = pack_has<ScoreOut, Extras...>;
+  constexpr bool SPARSE = pack_has<SparseOut, Extras...>;
   const SampleExtras x = sample_extras(extras...);
   const ScoreOut so = score_out(extras...);
+  const SparseOut sp = sparse_out(extras...);
   const int lane = threadIdx.x & 63;
-  const long ctr = *counter;
-  const float alpha = alphas[(int)(ctr % n_alpha)];
+  const long ctr = dense_counter<SPARSE>(counter);
+  const float alpha = dense_alpha<SPARSE>(alphas, n_alpha, ctr);
   for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < R; row += (long)gridDim.x * 4) {
     const float* x_lane = logits + row * ld + lane * NV;
     float v[NV];
@@ -191,19 +220,41 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
     float u[4];
     bool given = false;
     if constexpr (PROBES) given = x.uniforms != nullptr;
-    if (given) {
+    if constexpr (SPARSE) {
+      if (given) u[0] = x.uniforms[row];
+      else philox4_unit((unsigned long long)row, wmz_sparse_stream(sp), seed, u);
+      u[1] = 0.f;
+    } else if (given) {
       u[0] = x.uniforms[2 * row];
       u[1] = x.uniforms[2 * row + 1];
     } else {
       philox4_unit((unsigned long long)row, (unsigned long long)ctr, seed, u);
     }
     const float xq = u[0] * total;
-    int below = 0;
+    int draw;
+    if constexpr (SPARSE) {
+      int first = 0x7fffffff, last = -1;                       // kept classes of this lane: the first past xq, the last
 #pragma unroll
-    for (int e = 0; e < NV; ++e) below += (lane * NV + e < C && base + w[e] <= xq) ? 1 : 0;
+      for (int e = 0; e < NV; ++e) {
+        if (v[e] > -INFINITY && (e == 0 ? w[0] : w[e] - w[e - 1]) > 0.f) {
+          last = lane * NV + e;
+          if (base + w[e] > xq) first = min(first, lane * NV + e);
+        }
+      }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
-    const int draw = below < C ? below : C - 1;
+      for (int o = 32; o > 0; o >>= 1) {
+        first = min(first, __shfl_xor(first, o));
+        last = max(last, __shfl_xor(last, o));
+      }
+      draw = first != 0x7fffffff ? first : (last >= 0 ? last : C - 1);
+    } else {
+      int below = 0;
+#pragma unroll
+      for (int e = 0; e < NV; ++e) below += (lane * NV + e < C && base + w[e] <= xq) ? 1 : 0;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
+      draw = below < C ? below : C - 1;
+    }
     if constexpr (PROBES) {
       if (x.kept_floor != nullptr) {
         float f = INFINITY;
@@ -214,7 +265,9 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
         if (lane == 0) x.kept_floor[row] = f;
       }
     }
-    if constexpr (SCORED) {
+    if constexpr (SPARSE) {
+      if (lane == 0) wmz_sparse_write(sp, row, draw);
+    } else if constexpr (SCORED) {
       if (lane == 0) {
         const float l_d = TEMP ? mul_rn(logits[row * ld + draw], x.inv_temperature) : logits[row * ld + draw];
         so.scores[row] = sample_score(l_d, m, all_kept ? total : sum_all, so.noise, alpha, u[1]);
@@ -282,9 +335,11 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
                                                                    const float* __restrict__ uniforms, float* __restrict__ kept_floor,
                                                                    unsigned long long seed, const long long* __restrict__ counter,
                                                                    Score... score) {
-  static_assert(sizeof...(Score) <= 1, "one ScoreOut at the most");
-  constexpr bool SCORED = sizeof...(Score) == 1;
+  static_assert(sizeof...(Score) <= 1, "one ScoreOut or one SparseOut at the most");
+  constexpr bool SCORED = pack_has<ScoreOut, Score...>;
+  constexpr bool SPARSE = pack_has<SparseOut, Score...>;
   const ScoreOut so = score_out(SampleExtras{}, score...);
+  const SparseOut sp = sparse_out(score...);
   typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
   extern __shared__ __attribute__((aligned(16))) unsigned sw_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -292,8 +347,8 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
   u32x4* mine = reinterpret_cast<u32x4*>(sw_lds + tid * pitch);
   SwExchange exchange{sw_lds + SW_NT * pitch, 0};
   unsigned ra[4], rb[4];
-  const long ctr = *counter;
-  const float alpha = alphas[(int)(ctr % n_alpha)];
+  const long ctr = dense_counter<SPARSE>(counter);
+  const float alpha = dense_alpha<SPARSE>(alphas, n_alpha, ctr);
   for (long row = blockIdx.x; row < R; row += gridDim.x) {
     const float* x = logits + row * ld;
     for (int c = tid * 4; c < SW_NT * P; c += SW_NT * 4) {
@@ -398,7 +453,11 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
     }
     const float base = before + (inc - part);
     float u[4];
-    if (uniforms != nullptr) {
+    if constexpr (SPARSE) {
+      if (uniforms != nullptr) u[0] = uniforms[row];
+      else philox4_unit((unsigned long long)row, wmz_sparse_stream(sp), seed, u);
+      u[1] = 0.f;
+    } else if (uniforms != nullptr) {
       u[0] = uniforms[2 * row];
       u[1] = uniforms[2 * row + 1];
     } else {
@@ -442,7 +501,9 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
       exchange(kmin, 0u, ra, rb);
       if (tid == 0) kept_floor[row] = sw_unkey(min(min(ra[0], ra[1]), min(ra[2], ra[3])));
     }
-    if constexpr (SCORED) {
+    if constexpr (SPARSE) {
+      if (tid == 0) wmz_sparse_write(sp, row, draw);
+    } else if constexpr (SCORED) {
       if (tid == 0) {
         so.scores[row] = sample_score(mul_rn(x[draw], inv_temperature), m, all_kept ? total : sum_all, so.noise, alpha, u[1]);
         denoised[row] = draw;
@@ -755,6 +816,41 @@ static int sample_tokens_launch(const char* name, const float* logits, long ld, 
 #undef WMZ_SMP_NV
 #undef WMZ_SMP
   }
+  WMZ_LAUNCH_CHECK(name);
+  return WMZ_OK;
+}
+
+// The sparse form's launches (wmz_internal.h): the same two kernels, a SparseOut behind their arguments; the dense step's own
+// arguments are not read there.  The wide instantiation asks for its LDS itself: the attribute is per instantiation.
+int wmz_sparse_sample_launch(const char* name, const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
+                             const float* uniforms, float* kept_floor, unsigned long long seed, const WmzSparseOut& out,
+                             hipStream_t st) {
+  const bool temp = inv_temperature != 1.f, topp = top_p < 1.f;
+  if (C > 2048) {
+    const int P = (wmz_cdiv(C, SW_NT) + 7) / 8 * 8;
+    const size_t smem = ((size_t)SW_NT * (P + 4) + SW_RED_WORDS) * 4;
+    static std::atomic<uint64_t> attr_devs{0};
+    if (wmz_first_use_on_device(attr_devs)) {
+      const int most = (int)(((size_t)SW_NT * (SW_MAX_CLASSES / SW_NT + 4) + SW_RED_WORDS) * 4);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tokens_wide_kernel<SparseOut>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                most);
+    }
+    hipLaunchKernelGGL(sample_tokens_wide_kernel<SparseOut>, dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R, C, P, top_k,
+                       top_p, inv_temperature, (const float*)nullptr, 0, (int64_t)0, (int64_t*)nullptr, 0L, 0L, (int64_t*)nullptr,
+                       (unsigned char*)nullptr, uniforms, kept_floor, seed, (const long long*)nullptr, out);
+    WMZ_LAUNCH_CHECK(name);
+    return WMZ_OK;
+  }
+  const int grid = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
+  const SampleExtras x = {top_p, inv_temperature, uniforms, kept_floor};
+#define WMZ_SMP(NV, TEMP, TOPP) hipLaunchKernelGGL((sample_tokens_kernel<NV, TEMP, TOPP, SampleExtras, SparseOut>), dim3(grid), dim3(256), 0, st, logits, ld, \
+                                                   R, C, top_k, (const float*)nullptr, 0, (int64_t)0, (int64_t*)nullptr, 0L, 0L,                    \
+                                                   (int64_t*)nullptr, (unsigned char*)nullptr, seed, (const long long*)nullptr, x, out)
+#define WMZ_SMP_NV(TEMP, TOPP) \
+  do { if (C <= 256) WMZ_SMP(4, TEMP, TOPP); else if (C <= 512) WMZ_SMP(8, TEMP, TOPP); else if (C <= 1024) WMZ_SMP(16, TEMP, TOPP); else WMZ_SMP(32, TEMP, TOPP); } while (0)
+  if (temp && topp) WMZ_SMP_NV(true, true); else if (temp) WMZ_SMP_NV(true, false); else if (topp) WMZ_SMP_NV(false, true); else WMZ_SMP_NV(false, false);
+#undef WMZ_SMP_NV
+#undef WMZ_SMP
   WMZ_LAUNCH_CHECK(name);
   return WMZ_OK;
 }

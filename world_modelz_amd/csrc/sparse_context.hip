@@ -35,6 +35,7 @@ struct ScParams {
   float p_uniform;   // redraw probability per unit of r (training: 0.1, sparse_diffusion.py:447 p_max_uniform; the sampler: 0)
   unsigned long long seed, stream;
   const unsigned long long* counter;
+  const unsigned char* known; long known_stride;   // optional bytes [B, S * HW]: a non-zero position is given -- gathered as it is
 };
 
 constexpr int SC_BINS = 2048, SC_CAND = 1024;
@@ -140,6 +141,7 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) 
     int64_t d = tok;
     if (philox_unit(c[0]) < rb * P.p_uniform) { const int kk = (int)(philox_unit(c[1]) * (float)P.C); d = kk < P.C ? kk : P.C - 1; }
     if (philox_unit(c[2]) < rb) d = P.C;
+    if (P.known != nullptr && P.known[b * P.known_stride + pos] != 0) d = tok;       // (the uniforms above are drawn all the same)
     const long at = (long)b * P.n + i;
     P.indices[at] = pos;
     P.target[at] = tok;
@@ -153,12 +155,8 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) 
 // order -- the first class whose cumulative weight exceeds u * total (lane l owns the contiguous classes [l C / 64, (l + 1) C / 64):
 // lane sums -> a wave prefix -> the owning lane walks its classes).
 __global__ __launch_bounds__(256) void categorical_scatter_kernel(const float* __restrict__ logits, long ld, long R, int C,
-                                                                  const int64_t* __restrict__ indices, int64_t* __restrict__ z,
-                                                                  long clip_stride, long rows_per_clip,
-                                                                  int64_t* __restrict__ samples, unsigned long long seed,
-                                                                  unsigned long long stream,
-                                                                  const unsigned long long* __restrict__ counter) {
-  if (counter != nullptr) stream |= *counter & ((1ull << 40) - 1);
+                                                                  WmzSparseOut out, unsigned long long seed) {
+  const unsigned long long stream = wmz_sparse_stream(out);
   const int lane = threadIdx.x & 63;
   const int per = (C + 63) / 64, c0 = lane * per, c1 = min(c0 + per, C);
   for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < R; row += (long)gridDim.x * 4) {
@@ -192,10 +190,7 @@ __global__ __launch_bounds__(256) void categorical_scatter_kernel(const float* _
       }
     }
     pick = __shfl(pick, owner);
-    if (lane == 0) {
-      if (samples != nullptr) samples[row] = pick;
-      if (z != nullptr) z[(row / rows_per_clip) * clip_stride + indices[row]] = pick;
-    }
+    if (lane == 0) wmz_sparse_write(out, row, pick);
   }
 }
 
@@ -216,8 +211,20 @@ extern "C" int wmz_sparse_draw_context(const int64_t* z, long clip_stride, const
                                        int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
                                        unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
                                        void* stream) {
+  return wmz_sparse_draw_context_known(z, clip_stride, r, o, indices, tokens, target, B, S, HW, n, C, p_uniform, seed, stream_id, counter,
+                                       stream, nullptr, 0);
+}
+
+// The same draw for a clip of which some positions are given (include/wmz.h states the law): `known` changes the corrupted copy
+// of a given slot and nothing else.
+extern "C" int wmz_sparse_draw_context_known(const int64_t* z, long clip_stride, const float* r, const float* o, int64_t* indices,
+                                             int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
+                                             unsigned long long seed, unsigned long long stream_id,
+                                             const unsigned long long* counter, void* stream, const unsigned char* known,
+                                             long known_stride) {
   WMZ_REQUIRE(z && r && indices && tokens && target && B > 0 && C > 0, "wmz_sparse_draw_context: bad arguments");
   WMZ_REQUIRE(p_uniform >= 0.f && p_uniform <= 1.f, "wmz_sparse_draw_context: p_uniform in [0, 1] expected");
+  WMZ_REQUIRE(known == nullptr || known_stride >= (long)S * HW, "wmz_sparse_draw_context_known: known_stride below S * HW");
   if (!wmz_sparse_draw_context_supported(S, HW, n)) {
     wmz_set_error("wmz_sparse_draw_context: grid %d x %d with %d context positions not built (<= 65536 positions, <= 512 of "
                   "them drawn, 2 ceil(n / HW) <= S)", S, HW, n);
@@ -233,6 +240,7 @@ extern "C" int wmz_sparse_draw_context(const int64_t* z, long clip_stride, const
   P.stream = counter != nullptr ? (stream_id & ~((1ull << 40) - 1)) : stream_id;
   P.stream &= ~(SC_KEY_DOMAIN | SC_WIN_DOMAIN);
   P.counter = counter;
+  P.known = known; P.known_stride = known_stride;
   hipLaunchKernelGGL(sparse_context_kernel, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P);
   WMZ_LAUNCH_CHECK("wmz_sparse_draw_context");
   return WMZ_OK;
@@ -244,13 +252,40 @@ extern "C" int wmz_sparse_draw_context(const int64_t* z, long clip_stride, const
 extern "C" int wmz_categorical_scatter(const float* logits, long ld, long R, int C, const int64_t* indices, int64_t* z,
                                        long clip_stride, long rows_per_clip, int64_t* samples, unsigned long long seed,
                                        unsigned long long stream_id, const unsigned long long* counter, void* stream) {
+  return wmz_categorical_scatter_filtered(logits, ld, R, C, -1, 1.f, 1.f, indices, z, clip_stride, rows_per_clip, samples, nullptr, 0,
+                                          nullptr, nullptr, seed, stream_id, counter, stream);
+}
+
+// The same with a temperature, top-k, a nucleus and given positions (include/wmz.h states the law).  Neutral filters and no probe:
+// categorical_scatter_kernel, the three passes over the global row at any C and any alignment -- the draws of the entry point
+// above.  Else the two row bodies of wmz_sample_tokens_filtered_dev (loss.hip) with this sampler's uniform and destination.
+extern "C" int wmz_categorical_scatter_filtered(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
+                                                const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip,
+                                                int64_t* samples, const unsigned char* known, long known_stride,
+                                                const float* uniforms, float* kept_floor, unsigned long long seed,
+                                                unsigned long long stream_id, const unsigned long long* counter, void* stream) {
   WMZ_REQUIRE(logits && R > 0 && C > 0 && ld >= C, "wmz_categorical_scatter: bad arguments");
   WMZ_REQUIRE(z == nullptr || (indices != nullptr && rows_per_clip > 0), "wmz_categorical_scatter: the scatter needs indices and rows_per_clip");
   WMZ_REQUIRE(z != nullptr || samples != nullptr, "wmz_categorical_scatter: nothing to write");
-  const int grid = (int)((R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048);
+  WMZ_REQUIRE(inv_temperature > 0.f && inv_temperature < INFINITY,
+              "wmz_categorical_scatter_filtered: inv_temperature must be positive and finite (got %g)", (double)inv_temperature);
+  WMZ_REQUIRE(top_p > 0.f, "wmz_categorical_scatter_filtered: top_p must be positive (got %g)", (double)top_p);
   const unsigned long long sid = (counter != nullptr ? (stream_id & ~((1ull << 40) - 1)) : stream_id) & ~(SC_KEY_DOMAIN | SC_WIN_DOMAIN);
-  hipLaunchKernelGGL(categorical_scatter_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, R, C, indices, z, clip_stride,
-                     rows_per_clip, samples, seed, sid | (SC_KEY_DOMAIN | SC_WIN_DOMAIN), counter);
-  WMZ_LAUNCH_CHECK("wmz_categorical_scatter");
-  return WMZ_OK;
+  const WmzSparseOut out = {indices, z, clip_stride, rows_per_clip, samples, z != nullptr ? known : nullptr, known_stride,
+                            sid | (SC_KEY_DOMAIN | SC_WIN_DOMAIN), counter};
+  const bool neutral = !(top_k > 0 && top_k < C) && !(top_p < 1.f) && inv_temperature == 1.f && uniforms == nullptr && kept_floor == nullptr;
+  if (neutral) {
+    const int grid = (int)((R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048);
+    hipLaunchKernelGGL(categorical_scatter_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, R, C, out, seed);
+    WMZ_LAUNCH_CHECK("wmz_categorical_scatter");
+    return WMZ_OK;
+  }
+  if (C > wmz_sample_tokens_max_classes()) {
+    wmz_set_error("wmz_categorical_scatter_filtered: filters are built for <= %d classes (got %d)", wmz_sample_tokens_max_classes(), C);
+    return WMZ_ERR_UNSUPPORTED;
+  }
+  WMZ_REQUIRE(ld % 4 == 0 && (((uintptr_t)logits) & 15) == 0, "wmz_categorical_scatter_filtered: logits rows must be 16-byte aligned");
+  WMZ_REQUIRE(R <= 0x7fffffffL, "wmz_categorical_scatter_filtered: more than 2^31 - 1 rows");
+  return wmz_sparse_sample_launch("wmz_categorical_scatter_filtered", logits, ld, (int)R, C, top_k, top_p, inv_temperature, uniforms,
+                                  kept_floor, seed, out, (hipStream_t)stream);
 }

@@ -115,7 +115,7 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     (confidence_scores + lowest_scores_mask above; with consistent_masking among the positions masked before), the rule of
     masked-token decoders (MaskGIT).  remask_noise >= 0 (finite) scales the Gumbel noise added to the scores, annealed by
     (1 - alpha); its uniform is u_mask[f, i] when injected.  ValueError for anything else.  (Config 5's sampler,
-    sparse_diffusion.evaluate_model, has no such option.)"""
+    sparse_diffusion.sample_clips, takes temperature, sample_topk and sample_topp too; it has no re-mask step to order.)"""
     assert batch_z.is_cuda
     if remask not in REMASK_MODES:
         raise ValueError(f'remask must be one of {REMASK_MODES} (got {remask!r})')

@@ -83,21 +83,79 @@ class VqSparseDiffusionModel(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ the sampler (reference :99-202)
-def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counter=None):
+def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counter=None, *, top_k=-1, top_p=1.0, temperature=1.0,
+                        known=None, uniforms=None, kept_floor=None, samples=None):
     """One multinomial draw per row from softmax(logits) (reference :190-194), written into the clips at the rows' positions
-    (:197 `full_z_flat.scatter_`): logits fp32 [B, n, C], indices int64 [B, n], z_flat int64 [B, G] (in place).  The draw's
-    Philox stream: (seed, rank, call_id) -- or, with counter (device int64 [1]), the call number read on the device."""
+    (:197 `full_z_flat.scatter_`): logits fp32 [B, n, C] (rows at one stride, classes contiguous), indices int64 [B, n], z_flat
+    int64 [B, G] (in place).  The draw's Philox stream: (seed, rank, call_id) -- or, with counter (device int64 [1]), the call
+    number read on the device.
+    temperature (> 0), top_k (<= 0 or >= C: all) and top_p (nucleus, (0, 1]) filter the row by the law include/wmz.h states for
+    wmz_categorical_scatter_filtered; known (bool / uint8 [B, G]): positions of z_flat that are given and stay as they are;
+    uniforms fp32 [B * n] (u0 per row instead of the generator's), kept_floor fp32 [B * n] (probe: the smallest kept scaled
+    logit per row) and samples int64 [B * n] (every row's draw, known or not) as there.  The route: neutral filters and no known --
+    wmz_categorical_scatter, as ever; else wmz_categorical_scatter_filtered, rows off the 16-byte granule staged through a padded
+    buffer; a filter acting on more classes than ops.sample_max_classes() is applied with torch ops (sample.top_k_logits /
+    top_p_logits on the scaled logits) in front of the neutral form of that entry point."""
     from . import _lib as L
     B, n, C = logits.shape
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and indices.is_contiguous() and z_flat.stride(1) == 1
+    assert logits.dtype == torch.float32 and logits.stride(2) == 1 and indices.is_contiguous() and z_flat.stride(1) == 1
+    ld, R = (logits.stride(1) if n > 1 else logits.stride(0) if B > 1 else C), B * n
+    assert ld >= C and (B == 1 or logits.stride(0) == n * ld)
     sid = (int(rank) << 40) | (0 if counter is not None else int(call_id) & ((1 << 40) - 1))
-    L.call('wmz_categorical_scatter', L.ptr(logits), C, B * n, C, L.ptr(indices), L.ptr(z_flat), z_flat.stride(0), n, None,
-           int(seed) & 0xFFFFFFFFFFFFFFFF, sid, L.ptr(counter), L.stream())
+    tail = (int(seed) & 0xFFFFFFFFFFFFFFFF, sid, L.ptr(counter), L.stream())
+    dest = (L.ptr(indices), L.ptr(z_flat), z_flat.stride(0), n, L.ptr(samples))
+    assert samples is None or (samples.dtype == torch.int64 and samples.is_contiguous() and samples.numel() == R)
+    probes = uniforms is not None or kept_floor is not None
+    acting = 0 < top_k < C or top_p < 1.0 or temperature != 1.0 or probes
+    if not acting and known is None:
+        L.call('wmz_categorical_scatter', L.ptr(logits), ld, R, C, *dest, *tail)
+        return
+    assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.numel() == R)
+    assert kept_floor is None or (kept_floor.dtype == torch.float32 and kept_floor.is_contiguous() and kept_floor.numel() == R)
+    if known is not None:
+        assert known.dtype in (torch.bool, torch.uint8) and known.shape == z_flat.shape and known.stride(1) == 1
+    given = (L.ptr(known), known.stride(0) if known is not None else 0)
+    k, p, inv_t = int(top_k), float(top_p), 1.0 / float(temperature)
+    if acting:
+        from . import ops
+        from .sample import top_k_logits, top_p_logits
+        if C > ops.sample_max_classes():
+            if probes:
+                raise ValueError(f'uniforms / kept_floor are built for <= {ops.sample_max_classes()} classes (got {C})')
+            rows = logits.reshape(R, C) * torch.tensor(inv_t, dtype=torch.float32, device=logits.device)
+            if 0 < k < C:
+                rows = top_k_logits(rows, k)
+            logits, ld, k, p, inv_t = top_p_logits(rows, p).contiguous(), C, -1, 1.0, 1.0
+        elif ld % 4 != 0 or logits.data_ptr() % 16 != 0:
+            ld = (C + 3) // 4 * 4
+            staged = torch.empty(R, ld, dtype=torch.float32, device=logits.device)
+            staged[:, :C].copy_(logits.reshape(R, C))
+            logits = staged
+    L.call('wmz_categorical_scatter_filtered', L.ptr(logits), ld, R, C, k, p, inv_t, *dest, *given, L.ptr(uniforms), L.ptr(kept_floor),
+           *tail)
+
+
+def _check_sampler_arguments(temperature, sample_topp, prompt, shape, num_embeddings, device):
+    """sample_clips' filters are sample_frames' (same names, same refusals); prompt: int64 [batch_size, S, H, W] on the model's
+    device, tokens in [0, num_embeddings] -- num_embeddings, the mask token, marks what is to be generated."""
+    if not temperature > 0 or not temperature < float('inf'):
+        raise ValueError(f'temperature must be positive and finite (got {temperature})')
+    if not 0 < sample_topp <= 1:
+        raise ValueError(f'sample_topp must lie in (0, 1] (got {sample_topp})')
+    if prompt is None:
+        return
+    if not torch.is_tensor(prompt) or prompt.dtype != torch.int64 or tuple(prompt.shape) != tuple(shape):
+        raise ValueError(f'prompt must be an int64 tensor of shape {tuple(shape)} '
+                         f'(got {tuple(prompt.shape) if torch.is_tensor(prompt) else type(prompt).__name__})')
+    if prompt.device != device:
+        raise ValueError(f'prompt must live on the model\'s device {device} (got {prompt.device})')
+    if prompt.numel() and (int(prompt.min()) < 0 or int(prompt.max()) > int(num_embeddings)):
+        raise ValueError(f'prompt tokens must lie in [0, {int(num_embeddings)}] ({int(num_embeddings)}: the mask token, to be generated)')
 
 
 @torch.no_grad()
 def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', num_context=512, num_eval_iterations=100,
-                 generator=None, seed=None, use_graph=True):
+                 generator=None, seed=None, use_graph=True, *, temperature=1.0, sample_topk=-1, sample_topp=1.0, prompt=None):
     """The token side of the reference's evaluate_model (:139-202): clips [batch_size, S, H, W] that start fully masked and are
     re-drawn num_eval_iterations times -- per iteration G // num_context + 1 contexts, each gathered from the clip, masked with
     probability 1 - i / (iterations - 1), denoised by the model, sampled from softmax(logits) and scattered back.  'neighbors' (the
@@ -106,9 +164,13 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
     (wmz_sparse_draw_context with p_uniform = 0), the draw and the scatter another (wmz_categorical_scatter); nothing returns to
     the host inside the loop, and with use_graph the whole sub-step (draw, forward, sample, scatter; the call number counted on
     the device) is ONE hipGraph launch -- same tokens as the eager launches, bit for bit.  'uniform': consecutive num_context-wide slices of one permutation per iteration (the reference
-    slices at k * max_index, which is empty from k = 1 on; the evident intent -- k * num_context -- is what runs here)."""
-    from . import _lib as L
-    from .train import draw_sparse_context
+    slices at k * max_index, which is empty from k = 1 on; the evident intent -- k * num_context -- is what runs here).
+    temperature (> 0), sample_topk (<= 0: all) and sample_topp ((0, 1]) filter every draw as in sample_frames (the reference's
+    results were sampled with top-k 100); ValueError for anything else.  prompt: int64 [batch_size, S, H, W] on the model's device
+    -- the clip starts as the prompt instead of all masks; tokens in [0, num_embeddings) are GIVEN: fed to the model as they are,
+    never masked, never redrawn; num_embeddings (the mask token) marks what is generated.  ValueError for another shape, device or
+    value.  Every route takes them (the fused launches become wmz_sparse_draw_context_known / wmz_categorical_scatter_filtered);
+    the defaults run the launches they always ran."""
     if sampling_type not in ('uniform', 'neighbors'):
         raise ValueError('Specified sampling_type not supported')                 # reference :182
     if num_eval_iterations < 2:
@@ -116,9 +178,18 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
     S, H, W = (int(v) for v in model.shape)
     G = S * H * W
     dev = model.embedding.weight.device
+    _check_sampler_arguments(temperature, sample_topp, prompt, (batch_size, S, H, W), num_embeddings, dev)
+    from . import _lib as L
+    from .train import draw_sparse_context
     n = int(num_context)
-    full_z = torch.full((batch_size, S, H, W), int(num_embeddings), dtype=torch.int64, device=dev)      # all mask tokens (:153-155)
+    if prompt is None:
+        full_z = torch.full((batch_size, S, H, W), int(num_embeddings), dtype=torch.int64, device=dev)  # all mask tokens (:153-155)
+        known = None
+    else:
+        full_z = prompt.clone()
+        known = (prompt != int(num_embeddings)).view(batch_size, -1).to(torch.uint8)        # static: what is given stays given
     flat = full_z.view(batch_size, -1)
+    draw = dict(top_k=int(sample_topk), top_p=float(sample_topp), temperature=float(temperature), known=known)
     if seed is None:
         seed = generator.initial_seed() if generator is not None else torch.initial_seed()
     fused = sampling_type == 'neighbors' and bool(L.lib().wmz_sparse_draw_context_supported(S, H * W, n))
@@ -126,6 +197,13 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
     was_training = model.training
     model.eval()
     graph = None
+
+    def mask_unknown(tokens, indices, frac):
+        """The torch-drawn routes' masking (:185-187), given positions left as they are."""
+        hide = torch.rand(tokens.shape, device=dev) > frac
+        if known is not None:
+            hide &= torch.gather(known, 1, indices) == 0
+        return torch.where(hide, torch.full_like(tokens, num_embeddings), tokens)
     if fused and use_graph:
         # one captured sub-step on static inputs: the noise level / window width r, the window placement o, the call counter
         r_s = torch.ones(batch_size, dtype=torch.float32, device=dev)
@@ -135,9 +213,9 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
         def substep():
             ctr.add_(1)
             indices, tokens, _ = draw_sparse_context(full_z, r_s, n, (S, H, W), num_embeddings, seed=seed, rank=0, counter=ctr, o=o_s,
-                                                     p_uniform=0.0)
+                                                     p_uniform=0.0, known=known)
             logits = model(tokens, indices)
-            categorical_scatter(logits.float().contiguous(), indices, flat, seed, counter=ctr)
+            categorical_scatter(logits.float().contiguous(), indices, flat, seed, counter=ctr, **draw)
         from . import config as _cfg
         side = _cfg.shared_stream('warmup')
         side.wait_stream(torch.cuda.current_stream())
@@ -149,7 +227,11 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
         from .graph import capture_mode
         with torch.cuda.graph(graph, capture_error_mode=capture_mode()):
             substep()
-        full_z.fill_(int(num_embeddings))               # the warm-up wrote tokens: start from all masks, call number 0 (+ bit 38)
+        # the warm-up wrote tokens: start from all masks (or the prompt), call number 0 (+ bit 38)
+        if prompt is None:
+            full_z.fill_(int(num_embeddings))
+        else:
+            full_z.copy_(prompt)
         ctr.fill_(1 << 38)
     try:
         for i in range(num_eval_iterations):
@@ -173,17 +255,15 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
                     if idx.numel() == 0:
                         continue
                     indices = idx.unsqueeze(0).expand(batch_size, -1).contiguous()
-                    tokens = torch.gather(flat, 1, indices)
-                    tokens = torch.where(torch.rand(tokens.shape, device=dev) > frac, torch.full_like(tokens, num_embeddings), tokens)
+                    tokens = mask_unknown(torch.gather(flat, 1, indices), indices, frac)
                 elif fused:
                     indices, tokens, _ = draw_sparse_context(full_z, r, n, (S, H, W), num_embeddings, seed=seed, rank=0, o=o_rows[k],
-                                                             p_uniform=0.0, call_id=call)
+                                                             p_uniform=0.0, call_id=call, known=known)
                 else:
                     indices = sample_time_dependent(batch_size, n, S, H, W, r, dev, o=o_rows[k])
-                    tokens = torch.gather(flat, 1, indices)
-                    tokens = torch.where(torch.rand(tokens.shape, device=dev) > frac, torch.full_like(tokens, num_embeddings), tokens)
+                    tokens = mask_unknown(torch.gather(flat, 1, indices), indices, frac)
                 logits = model(tokens, indices)                                                         # [B, n, C] fp32
-                categorical_scatter(logits.float().contiguous(), indices, flat, seed, call)
+                categorical_scatter(logits.float().contiguous(), indices, flat, seed, call, **draw)
     finally:
         model.train(was_training)
     return full_z
@@ -201,8 +281,11 @@ def decode(decoder_model, batch, decode_N=16):
 
 
 @torch.no_grad()
-def evaluate_model(device, batch_size, model, decoder_model, shape, sampling_type, num_context=512, num_eval_iterations=100):
-    """The reference's evaluate_model (:139-202), same signature: sampled clips decoded to frames."""
+def evaluate_model(device, batch_size, model, decoder_model, shape, sampling_type, num_context=512, num_eval_iterations=100, *,
+                   temperature=1.0, sample_topk=-1, sample_topp=1.0, prompt=None):
+    """The reference's evaluate_model (:139-202), same positional signature: sampled clips decoded to frames.  temperature,
+    sample_topk, sample_topp and prompt (keyword-only) are sample_clips'."""
     assert tuple(int(v) for v in shape) == tuple(int(v) for v in model.shape)
-    z = sample_clips(model, batch_size, decoder_model.vq.num_embeddings, sampling_type, num_context, num_eval_iterations)
+    z = sample_clips(model, batch_size, decoder_model.vq.num_embeddings, sampling_type, num_context, num_eval_iterations,
+                     temperature=temperature, sample_topk=sample_topk, sample_topp=sample_topp, prompt=prompt)
     return decode(decoder_model, z)

@@ -84,12 +84,15 @@ def corrupt_tokens(tokens, r, num_embeddings, generator=None, seed=None, rank=No
 
 
 def draw_sparse_context(z, r, num_context, shape, num_embeddings, generator=None, seed=None, rank=None, counter=None, o=None,
-                        p_uniform=0.1, call_id=None):
+                        p_uniform=0.1, call_id=None, known=None):
     """Config 5's step prologue by ONE launch (wmz_sparse_draw_context: minecraft/sparse_diffusion.py:44-72 sample_time_dependent,
     :437 gather, :440-449 perturbation & masking): z [B, S, H, W] token clips, r [B] noise levels -> (indices, corrupted tokens,
     target), each [B, num_context].  o [B]: the window placements (else drawn in the kernel).  p_uniform: the redraw probability
     per unit of r (:447 p_max_uniform = 0.1; the sampler masks only: 0).  Random stream as corrupt_tokens:
-    (seed, rank, per-call counter -- on the device when `counter` is given: hipGraph replays)."""
+    (seed, rank, per-call counter -- on the device when `counter` is given: hipGraph replays).
+    known (bool / uint8 [B, S * H * W], the prompted sampler's; training passes none): a context slot at a given position keeps
+    its token -- neither masked nor redrawn -- and everything else, the random streams included, is as without it
+    (wmz_sparse_draw_context_known)."""
     global _corrupt_calls
     assert z.is_cuda and z.dtype == torch.int64
     B = z.shape[0]
@@ -112,8 +115,13 @@ def draw_sparse_context(z, r, num_context, shape, num_embeddings, generator=None
     else:
         _corrupt_calls += 1
         stream_id = (rank << 40) | (_corrupt_calls & ((1 << 40) - 1))
-    L.call('wmz_sparse_draw_context', L.ptr(zf), zf.stride(0), L.ptr(r), L.ptr(o), L.ptr(indices), L.ptr(tokens), L.ptr(target),
-           B, S, H * W, n, int(num_embeddings), float(p_uniform), int(seed) & 0xFFFFFFFFFFFFFFFF, stream_id, L.ptr(counter), L.stream())
+    args = (L.ptr(zf), zf.stride(0), L.ptr(r), L.ptr(o), L.ptr(indices), L.ptr(tokens), L.ptr(target), B, S, H * W, n,
+            int(num_embeddings), float(p_uniform), int(seed) & 0xFFFFFFFFFFFFFFFF, stream_id, L.ptr(counter), L.stream())
+    if known is None:
+        L.call('wmz_sparse_draw_context', *args)
+    else:
+        assert known.dtype in (torch.bool, torch.uint8) and known.shape == zf.shape and known.stride(1) == 1 and known.device == dev
+        L.call('wmz_sparse_draw_context_known', *args, L.ptr(known), known.stride(0))
     return indices, tokens, target
 
 
