@@ -6,11 +6,12 @@ src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 asm = subprocess.run(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-S', '--cuda-device-only', src, '-o', '-'],
                      capture_output=True, text=True).stdout
 bad_total = 0
-for name, body in re.findall(r'^(_ZN\S*layer_fused_kernel\S*):\s*;.*?\n(.*?)s_endpgm', asm, flags=re.S | re.M):
+# (layer_fused_kernel: every caller's kernel; layer_fused_infer_kernel: the inference unit, whose loads take a scalar base)
+for name, body in re.findall(r'^(_ZN\S*layer_fused(?:_infer)?_kernel\S*):\s*;.*?\n(.*?)s_endpgm', asm, flags=re.S | re.M):
     lines = body.split('\n')
     loads = []
     for i, l in enumerate(lines):
-        m = re.match(r'\s*global_load_dwordx4 v\[(\d+):(\d+)\], v\[\d+:\d+\], off\s*$', l)
+        m = re.match(r'\s*global_load_dwordx4 v\[(\d+):(\d+)\], (?:v\[\d+:\d+\], off|v\d+, s\[\d+:\d+\] offset:(?:0x[0-9a-f]+|\d+))\s*$', l)
         if m and i and '#ASMSTART' in lines[i - 1]:
             loads.append((i, int(m.group(1)), int(m.group(2))))
     if not loads:

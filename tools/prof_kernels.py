@@ -1,6 +1,9 @@
 """Micro-driver for profiling single kernels under rocprofv3 (not part of the product).
 
-    python3 tools/prof_kernels.py {fused|attn|attn_bwd|vq} N        config-4 shapes (65 536 tokens, dh 128, window 7x7x7)
+    python3 tools/prof_kernels.py {fused|fused_infer|attn|attn_bwd|vq} N        config-4 shapes (65 536 tokens, dh 128, window 7x7x7)
+
+fused: the head + tail launch on row-major streams (the run-time kernel); fused_infer: on the tiled stream, as the inference step
+launches it (the inference unit, layer_fused_infer_kernel).
 """
 import sys
 import torch
@@ -30,6 +33,8 @@ if which == 'vq':
 for _ in range(int(sys.argv[2]) if len(sys.argv) > 2 else 5):
     if which == 'fused':
         fused.layer_fused(o, x, layers[0], layers[1])
+    elif which == 'fused_infer':
+        fused.layer_fused(o, x, layers[0], layers[1], xflags=3)
     elif which == 'attn':
         ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1)
     elif which == 'attn_bwd':

@@ -37,7 +37,15 @@ constexpr int VECB = 8192;      // the layer's bias / LayerNorm vectors (2048 fp
 constexpr int MC = 32;          // feed-forward hidden chunk: W1 rows / W2 columns streamed MC at a time
 
 // ---- weight stream: RING-slot LDS ring filled by LDS-DMA (global_load_lds), RING-1 slabs in flight.
-struct WStream {
+// FIXED = false: the ablation switches and timing probes are live and every counted wait takes its count at run time (the
+// kernels whose options come from their arguments).  FIXED = true (the inference unit of layer_fused.hip): no switches, no
+// probes, and every counted wait must reduce to ONE s_waitcnt with a literal -- the bookkeeping below is the same code either
+// way (ws_extra / ws_issue feed both), but here it has to fold at compile time or the build fails (vm_wait_literal).
+template <bool FIXED>
+struct WStreamT {
+  static constexpr bool kFixed = FIXED;
+  __device__ __forceinline__ int knobs() const { return FIXED ? 0 : dbg; }
+  __device__ __forceinline__ bool probing() const { return !FIXED && probe && ts; }
   int dbg;
   const char* src;     // global address of the next slab to ISSUE (this lane's 16 bytes of piece 0 of its wave)
   char* ring;          // LDS ring base + this wave's eighth of a slab
@@ -52,11 +60,20 @@ struct WStream {
   int tot, t1, t2, t3;
   int all;             // every VMEM op this wave has issued (ring pieces included): vm_wait_since() waits by sequence number
 };
+typedef WStreamT<false> WStream;
 
-__device__ __forceinline__ void ws_issue(WStream& ws) {
+// s_waitcnt vmcnt(n) for an n that is a constant of the program point: the "i" constraint takes nothing else, so a tally that
+// does not fold to a literal (an option decided at run time on the way here) stops the build instead of costing a switch.
+// The counter has 6 bits; more than 63 waits for the surplus (safe).
+__device__ __forceinline__ void vm_wait_literal(int n) {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(n < 63 ? n : 63) : "memory");
+}
+
+template <typename WS>
+__device__ __forceinline__ void ws_issue(WS& ws) {
   ws.t1 = ws.t2; ws.t2 = ws.t3; ws.t3 = ws.tot;
   ws.all += WPP;
-  if (ws.dbg & 2) return;
+  if (ws.knobs() & 2) return;
   char* dst = ws.ring + ws.issue_slot * SLAB;
 #pragma unroll
   for (int i = 0; i < WPP; ++i)
@@ -71,11 +88,13 @@ __device__ __forceinline__ void ws_issue(WStream& ws) {
 // the requests over the stage instead measured slower).  vmcnt counts loads, stores and LDS-DMA together in issue
 // order: the oldest slab in flight has landed <=> at most [the WPP*(RING-2) pieces of the younger slabs + every other op
 // issued after its pieces (tot - its t)] is outstanding.
-__device__ __forceinline__ void ws_wait(WStream& ws) {
+template <typename WS>
+__device__ __forceinline__ void ws_wait(WS& ws) {
   constexpr int YB = WPP * (RING - 2);
   static_assert(YB == 4 || YB == 0, "literals below");
   const int e = ws.tot - (RING == 4 ? ws.t1 : (RING == 3 ? ws.t2 : ws.t3));
-  if (!(ws.dbg & 2)) {
+  if constexpr (WS::kFixed) vm_wait_literal(e + YB);
+  else if (!(ws.dbg & 2)) {
 #define WMZ_VMC(n) case n: if (YB == 4) asm volatile("s_waitcnt vmcnt(" #n " + 4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); break;
     switch (e) {
       WMZ_VMC(0) WMZ_VMC(1) WMZ_VMC(2) WMZ_VMC(3) WMZ_VMC(4) WMZ_VMC(5) WMZ_VMC(6) WMZ_VMC(7) WMZ_VMC(8) WMZ_VMC(9)
@@ -86,12 +105,12 @@ __device__ __forceinline__ void ws_wait(WStream& ws) {
     }
 #undef WMZ_VMC
   }
-  if (ws.probe && ws.ts) ws.ts[ws.probe] = __builtin_readcyclecounter();
-  if (!(ws.dbg & 4)) __builtin_amdgcn_s_barrier();     // (dbg 4: timing experiment without the per-slab rendezvous; garbage results)
-  if (ws.probe && ws.ts) ws.ts[ws.probe + 1] = __builtin_readcyclecounter();
+  if (ws.probing()) ws.ts[ws.probe] = __builtin_readcyclecounter();
+  if (!(ws.knobs() & 4)) __builtin_amdgcn_s_barrier();     // (dbg 4: timing experiment without the per-slab rendezvous; garbage results)
+  if (ws.probing()) ws.ts[ws.probe + 1] = __builtin_readcyclecounter();
 }
-__device__ __forceinline__ void ws_release(WStream& ws) { ws.cur = ws.cur == RING - 1 ? 0 : ws.cur + 1; }
-__device__ __forceinline__ void ws_extra(WStream& ws, int n) { ws.tot += n; ws.all += n; }
+template <typename WS> __device__ __forceinline__ void ws_release(WS& ws) { ws.cur = ws.cur == RING - 1 ? 0 : ws.cur + 1; }
+template <typename WS> __device__ __forceinline__ void ws_extra(WS& ws, int n) { ws.tot += n; ws.all += n; }
 // s_waitcnt vmcnt(n) for a run-time n (vmcnt completes in issue order: "at most n outstanding" = everything but the n
 // youngest VMEM ops of this wave has landed).  More than 48: waits for the surplus (safe).
 __device__ __forceinline__ void vm_wait(int n) {
@@ -107,7 +126,11 @@ __device__ __forceinline__ void vm_wait(int n) {
 #undef WMZ_VMW
 }
 // every VMEM op up to sequence number `mark` (= ws.all right after it was issued and accounted) has landed
-__device__ __forceinline__ void vm_wait_since(const WStream& ws, int mark) { vm_wait(ws.all - mark); }
+template <typename WS>
+__device__ __forceinline__ void vm_wait_since(const WS& ws, int mark) {
+  if constexpr (WS::kFixed) vm_wait_literal(ws.all - mark);
+  else vm_wait(ws.all - mark);
+}
 
 // Side work of a GEMM stage: called once per group of AG MFMAs; kValuPerMfma tells the stage how many of its VALU
 // instructions the scheduler should place behind EACH MFMA (measured on MI355X at two waves per SIMD: up to ~2 VALU per
@@ -123,8 +146,8 @@ template <int VPM, typename F> __device__ __forceinline__ SideWork<VPM, F> side_
 // acc[NB blocks of 32 features x 32 tokens] += W . act^T over KS 16-deep k-steps; the stream holds the pieces in
 // (k-step, block) order, so a k-step's operand is used by NB independent accumulators.  bget(s) yields the B operand
 // of k-step s (a register array, or an LDS read issued one k-step ahead).
-template <int NB, int KS, typename BGet, typename Side = NoSide>
-__device__ __forceinline__ void gemm_stage_b(f32x16 (&acc)[NB], BGet bget, const char* ring0, WStream& ws, int lane,
+template <int NB, int KS, typename BGet, typename WS, typename Side = NoSide>
+__device__ __forceinline__ void gemm_stage_b(f32x16 (&acc)[NB], BGet bget, const char* ring0, WS& ws, int lane,
                                              Side side = Side()) {
   constexpr int NP = NB * KS;
   static_assert(NP % PIECES == 0, "a stage is a whole number of slabs");
@@ -138,16 +161,16 @@ __device__ __forceinline__ void gemm_stage_b(f32x16 (&acc)[NB], BGet bget, const
     // A operands: groups of AG, the next group's ds_reads in flight under this group's MFMAs (8 fragments live, no more:
     // the scheduler is fenced so that it cannot hoist the whole slab's reads into registers the chain needs)
     Frag8<bf16_t> af[2][AG];
-    if (!(ws.dbg & 1)) {
+    if (!(ws.knobs() & 1)) {
 #pragma unroll
       for (int j = 0; j < AG; ++j) af[0][j].v = *reinterpret_cast<const s16x8*>(slab + j * 1024);
     }
     if (ws.half == 0) ws_issue(ws);                        // refill the retired slot while the first fragments arrive
-    if (ws.probe && ws.ts) ws.ts[ws.probe + 2] = __builtin_readcyclecounter();
-    if (!(ws.dbg & 1)) {
+    if (ws.probing()) ws.ts[ws.probe + 2] = __builtin_readcyclecounter();
+    if (!(ws.knobs() & 1)) {
 #pragma unroll
       for (int gq = 0; gq < GPS; ++gq) {
-        if (gq == 1 && ws.probe && ws.ts) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ws.ts[ws.probe + 3] = __builtin_readcyclecounter(); }
+        if (gq == 1 && ws.probing()) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ws.ts[ws.probe + 3] = __builtin_readcyclecounter(); }
         if (gq + 1 < GPS) {
 #pragma unroll
           for (int j = 0; j < AG; ++j)
@@ -183,8 +206,8 @@ __device__ __forceinline__ void gemm_stage_b(f32x16 (&acc)[NB], BGet bget, const
     else ++ws.half;
   }
 }
-template <int NB, int KS, typename Side = NoSide>
-__device__ __forceinline__ void gemm_stage(f32x16 (&acc)[NB], const Frag8<bf16_t> (&bop)[KS], const char* ring0, WStream& ws,
+template <int NB, int KS, typename WS, typename Side = NoSide>
+__device__ __forceinline__ void gemm_stage(f32x16 (&acc)[NB], const Frag8<bf16_t> (&bop)[KS], const char* ring0, WS& ws,
                                            int lane, Side side = Side()) {
   gemm_stage_b<NB, KS>(acc, [&](int s) { return bop[s]; }, ring0, ws, lane, side);
 }
@@ -242,6 +265,14 @@ __device__ __forceinline__ s16x8 gload_untracked(const bf16_t* p) {
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
+// The same from a wave-uniform base: 32-bit byte offset per lane + an immediate (0 .. 4095).
+template <int IMM>
+__device__ __forceinline__ s16x8 gload_untracked(const bf16_t* base, unsigned voff) {
+  static_assert(IMM >= 0 && IMM < 4096, "13-bit signed instruction offset");
+  s16x8 v;
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(v) : "v"(voff), "s"(base), "i"(IMM) : "memory");
+  return v;
+}
 // vmcnt is in issue order: once at most the ring's WPP*(RING-1) youngest pieces are outstanding, every older load is done.
 template <int KS>
 __device__ __forceinline__ void wait_untracked(Frag8<bf16_t> (&b)[KS]) {
@@ -272,15 +303,23 @@ __device__ __forceinline__ void load_bop_tiled(Frag8<bf16_t> (&bop)[KS], const b
 #pragma unroll
   for (int s = 0; s < KS; ++s) bop[s].v = *reinterpret_cast<const s16x8*>(tile + (s * 64 + lane) * 8);   // (2s+h)*32+t = 64s+lane
 }
-template <int KS>
+// (WHOLE, here and in the row I/O below: the caller vouches for whole 256-token workgroups, so `tile` / the row base is
+//  wave-uniform and every row exists -- 32-bit per-lane byte offsets from that scalar base, no guards, no clamps)
+template <int KS, bool WHOLE = false>
 __device__ __forceinline__ void store_bop_tiled(bf16_t* tile, const Frag8<bf16_t> (&bop)[KS], int lane, HalfGuard& hg) {
   if (hg.on()) {
 #pragma unroll
     for (int s = 0; s < KS; ++s) hg.see(bop[s].v);
     hg.fold(WMZ_HG_STREAM);
   }
+  if constexpr (WHOLE) {
 #pragma unroll
-  for (int s = 0; s < KS; ++s) *reinterpret_cast<s16x8*>(tile + (s * 64 + lane) * 8) = bop[s].v;
+    for (int s = 0; s < KS; ++s)
+      *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(tile) + (unsigned)(s * 1024 + lane * 16)) = bop[s].v;
+  } else {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) *reinterpret_cast<s16x8*>(tile + (s * 64 + lane) * 8) = bop[s].v;
+  }
 }
 
 // Row stores through the wave's private 8 KB LDS buffer: a lane owns HALF A ROW of its token, so direct 16-byte stores
@@ -290,13 +329,20 @@ __device__ __forceinline__ void store_bop_tiled(bf16_t* tile, const Frag8<bf16_t
 // instruction, whole 256-byte runs per row.
 // LDS-DMA a [32 tokens x 128 features] tile (rows of ROWF features, 256 B of each from column col0) into the wave's image,
 // same chunk swizzle as the store path (applied on the source address: the DMA writes lane-linear).
+template <bool WHOLE = false>
 __device__ __forceinline__ void stage_dma128(char* stg, const bf16_t* src, int rowf, long tok0, int ntok, int lane) {
 #pragma unroll
   for (int p = 0; p < 8; ++p) {
     const int r = p * 4 + (lane >> 4), pc = lane & 15;
-    const long row = tok0 + r < ntok ? tok0 + r : ntok - 1;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + row * rowf + ((pc ^ (r & 15)) << 3)),
-                                     (__attribute__((address_space(3))) void*)(stg + p * 1024), 16, 0, 0);
+    if constexpr (WHOLE) {
+      const char* base = reinterpret_cast<const char*>(src + tok0 * rowf);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + (unsigned)((r * rowf + ((pc ^ (r & 15)) << 3)) * 2)),
+                                       (__attribute__((address_space(3))) void*)(stg + p * 1024), 16, 0, 0);
+    } else {
+      const long row = tok0 + r < ntok ? tok0 + r : ntok - 1;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + row * rowf + ((pc ^ (r & 15)) << 3)),
+                                       (__attribute__((address_space(3))) void*)(stg + p * 1024), 16, 0, 0);
+    }
   }
 }
 __device__ __forceinline__ Frag8<bf16_t> stage_get(const char* stg, int t, int c) {
@@ -308,7 +354,7 @@ __device__ __forceinline__ void stage_put(char* stg, const s16x8& v, int t, int 
   *reinterpret_cast<s16x8*>(stg + t * 256 + ((c ^ (t & 15)) << 4)) = v;
 }
 // copy the 8 KB image out: row r of the image -> dst + (tok0 + r) * ROWF + col0, 128 features (256 B) per row
-template <int ROWF>
+template <int ROWF, bool WHOLE = false>
 __device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long tok0, int ntok, int col0, int lane, HalfGuard& hg,
                                             unsigned kind) {
   asm volatile("" : "+s"(tok0), "+v"(lane));   // compute the store addresses HERE (hoisted / shared with the prologue's
@@ -327,7 +373,9 @@ __device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long t
   for (int p = 0; p < 8; ++p) {
     const int r = p * 4 + (lane >> 4), pc = lane & 15;
     const int c = pc ^ (r & 15);
-    if (tok0 + r < ntok) *reinterpret_cast<s16x8*>(dst + (tok0 + r) * ROWF + col0 + c * 8) = v[p];
+    if constexpr (WHOLE)
+      *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(dst + tok0 * ROWF) + (unsigned)((r * ROWF + col0 + c * 8) * 2)) = v[p];
+    else if (tok0 + r < ntok) *reinterpret_cast<s16x8*>(dst + (tok0 + r) * ROWF + col0 + c * 8) = v[p];
   }
 }
 template <int ROWF>
@@ -346,13 +394,14 @@ __device__ __forceinline__ Frag8<bf16_t> frag_unpark(const char* stg, int slot, 
 }
 
 // an I-feature tile (q, k, v: 128 features, every lane holds 8 chunks of its row): one pass
+template <bool WHOLE = false>
 __device__ __forceinline__ void store_tile128(char* stg, bf16_t* dst, int rowf, long tok0, int ntok, int col0,
                                               const Frag8<bf16_t> (&b)[8], int lane, HalfGuard& hg) {
   const int t = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int s = 0; s < 8; ++s) stage_put(stg, b[s].v, t, h * 8 + s);
-  if (rowf == 128) stage_flush<128>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
-  else stage_flush<256>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
+  if (rowf == 128) stage_flush<128, WHOLE>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
+  else stage_flush<256, WHOLE>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
 }
 __device__ __forceinline__ void store_tile128(char* stg, bf16_t* dst, int rowf, long tok0, int ntok, int col0,
                                               const Frag8<bf16_t> (&b)[8], int lane) {
@@ -360,6 +409,7 @@ __device__ __forceinline__ void store_tile128(char* stg, bf16_t* dst, int rowf, 
   store_tile128(stg, dst, rowf, tok0, ntok, col0, b, lane, none);
 }
 // the D-feature stream (256 features, a lane holds 16 chunks = its whole 256-byte half row): one pass per lane half
+template <bool WHOLE = false>
 __device__ __forceinline__ void store_tile256(char* stg, bf16_t* dst, long tok0, int ntok, const Frag8<bf16_t> (&b)[16],
                                               int lane, HalfGuard& hg) {
   const int t = lane & 31, h = lane >> 5;
@@ -369,7 +419,7 @@ __device__ __forceinline__ void store_tile256(char* stg, bf16_t* dst, long tok0,
 #pragma unroll
       for (int s = 0; s < 16; ++s) stage_put(stg, b[s].v, t, s);
     }
-    stage_flush<256>(stg, dst, tok0, ntok, hh * 128, lane, hg, WMZ_HG_STREAM);
+    stage_flush<256, WHOLE>(stg, dst, tok0, ntok, hh * 128, lane, hg, WMZ_HG_STREAM);
   }
 }
 __device__ __forceinline__ void store_tile256(char* stg, bf16_t* dst, long tok0, int ntok, const Frag8<bf16_t> (&b)[16],

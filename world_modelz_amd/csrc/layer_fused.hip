@@ -24,6 +24,7 @@
 #include "fused_common.h"
 #include "fused_pack_rows.h"
 #include "wmz_debug.h"
+#include <atomic>
 
 namespace {
 
@@ -63,19 +64,51 @@ struct FusedParams {
 // stage-boundary probe: wave w of workgroup 0 stores the shader clock into ts[w * 64 + slot]
 #define WMZ_TS(slot)                                                                                      \
   do {                                                                                                    \
-    if (P.ts != nullptr && blockIdx.x == 0 && lane == 0) P.ts[wave * 64 + (slot)] = __builtin_readcyclecounter(); \
+    if (O::ts(P) != nullptr && blockIdx.x == 0 && lane == 0) O::ts(P)[wave * 64 + (slot)] = __builtin_readcyclecounter(); \
   } while (0)
-__device__ __forceinline__ long src_row(const FusedParams& P, long t) {
-  if (P.rows_out == 0) return t;
-  const int c = (int)t / P.rows_out;
-  return (long)c * P.rows_in + P.row0 + ((int)t - c * P.rows_out);
-}
+
+// Option policies of the kernel body (layer_fused_body): where each optional feature of a launch is decided.
+// OptRuntime: from the kernel arguments, all of them -- layer_fused_kernel, every caller's kernel.
+struct OptRuntime {
+  static constexpr bool kFixed = false;
+  static constexpr int kXflags = 0;          // (unused: the layout is an argument)
+  typedef WStreamT<false> Stream;
+  __device__ static __forceinline__ int xflags(const FusedParams& P) { return P.xflags; }
+  __device__ static __forceinline__ bool embed(const FusedParams& P) { return P.z != nullptr; }
+  template <typename T> __device__ static __forceinline__ T* train(T* p) { return p; }     // a training output (NULL = off)
+  __device__ static __forceinline__ int kv_combined(const FusedParams& P) { return P.kv_combined; }
+  __device__ static __forceinline__ int dbg(const FusedParams& P) { return P.dbg; }
+  __device__ static __forceinline__ long long* ts(const FusedParams& P) { return P.ts; }
+  __device__ static __forceinline__ long src_row(const FusedParams& P, long t) {
+    if (P.rows_out == 0) return t;
+    const int c = (int)t / P.rows_out;
+    return (long)c * P.rows_in + P.row0 + ((int)t - c * P.rows_out);
+  }
+};
+// OptInfer: at compile time -- the plain inference launch of the full grid (layer_fused_infer_kernel; fused_launch checks what
+// is assumed here).  Whole 256-token workgroups (no row guards, no clamps, wave-uniform bases with 32-bit lane offsets), the
+// stream layout XFLAGS, no training outputs (k rows then v rows), identity rows, the first layer's x from the embedding by
+// embed_coop (16-wide planes of an even height), no ablation switches, no probes.  With nothing left to decide at run time
+// the VMEM tallies of the weight stream are constants of the program point: every counted wait is one literal s_waitcnt.
+template <int XFLAGS>
+struct OptInfer {
+  static constexpr bool kFixed = true;
+  static constexpr int kXflags = XFLAGS;
+  typedef WStreamT<true> Stream;
+  __device__ static __forceinline__ int xflags(const FusedParams&) { return XFLAGS; }
+  __device__ static __forceinline__ bool embed(const FusedParams&) { return true; }
+  template <typename T> __device__ static __forceinline__ T* train(T*) { return nullptr; }
+  __device__ static __forceinline__ int kv_combined(const FusedParams&) { return 0; }
+  __device__ static __forceinline__ int dbg(const FusedParams&) { return 0; }
+  __device__ static __forceinline__ long long* ts(const FusedParams&) { return nullptr; }
+  __device__ static __forceinline__ long src_row(const FusedParams&, long t) { return t; }
+};
 
 // token + 3-axis position embedding of the lane's half row, rounded to bf16 (the value the stream carries)
-template <int F>
+template <int F, typename O>
 __device__ __forceinline__ void embed_bop(Frag8<bf16_t> (&bop)[F / 16], const FusedParams& P, long t, bool ok, int h) {
   (void)ok;                                              // t is already clamped to a valid token
-  const long ts = src_row(P, t);
+  const long ts = O::src_row(P, t);
   const int w = (int)(ts % P.W), hh = (int)((ts / P.W) % P.H), s = (int)((ts / ((long)P.W * P.H)) % P.S);
   long tk = P.z[ts];
   tk = tk < 0 ? 0 : (tk >= P.num_classes ? P.num_classes - 1 : tk);
@@ -106,12 +139,21 @@ __device__ __forceinline__ void embed_bop(Frag8<bf16_t> (&bop)[F / 16], const Fu
 // form above gathers 64 different rows per instruction), adds the position rows (plane and the two plane-row terms
 // hoisted, the 16 column rows kept in registers), and drops the bf16 row into the wave's LDS image; the lanes then pick
 // up their own half rows.  Same fp32 sum order, e + ((s + h) + w): bit-identical to embed_bop.
-template <int F>
+template <int F, typename O>
 __device__ __forceinline__ void embed_coop(Frag8<bf16_t> (&bop)[F / 16], char* stg, const FusedParams& P, long tok0, int lane) {
   static_assert(F == 256, "one 1 KB fp32 row per wave instruction");
   const long last = P.ntok - 1;
-  const long ts0 = src_row(P, tok0 < last ? tok0 : last);                 // first token of the tile in the full grid
-  const int h0 = (int)((ts0 / 16) % P.H), s = (int)((ts0 / (16L * P.H)) % P.S);
+  // first token of the tile in the full grid (whole workgroups, identity rows: the tile's own first token, nothing to clamp)
+  const long ts0 = O::kFixed ? tok0 : O::src_row(P, tok0 < last ? tok0 : last);
+  int h0, s;
+  if constexpr (O::kFixed) {                       // (token counts fit 31 bits: the same quotients without 64-bit divisions)
+    const unsigned row = (unsigned)ts0 / 16u;
+    h0 = (int)(row % (unsigned)P.H);
+    s = (int)((row / (unsigned)P.H) % (unsigned)P.S);
+  } else {
+    h0 = (int)((ts0 / 16) % P.H);
+    s = (int)((ts0 / (16L * P.H)) % P.S);
+  }
   const int h1 = h0 + 1 < P.H ? h0 + 1 : h0;
   const f32x4 ps = *reinterpret_cast<const f32x4*>(P.pos_s + (long)s * F + lane * 4);
   const f32x4 a0 = ps + *reinterpret_cast<const f32x4*>(P.pos_h + (long)h0 * F + lane * 4);
@@ -124,7 +166,7 @@ __device__ __forceinline__ void embed_coop(Frag8<bf16_t> (&bop)[F / 16], char* s
   int tkv;
   {
     const long tt = tok0 + t < last ? tok0 + t : last;
-    long tk = P.z[ts0 + (tt - (tok0 < last ? tok0 : last))];
+    long tk = O::kFixed ? P.z[tok0 + (unsigned)t] : P.z[ts0 + (tt - (tok0 < last ? tok0 : last))];
     tk = tk < 0 ? 0 : (tk >= P.num_classes ? P.num_classes - 1 : tk);
     tkv = (int)tk;
   }
@@ -162,9 +204,10 @@ __device__ __forceinline__ void store_z_tiled(bf16_t* zt, long tok0, int c, cons
   }
 }
 
-template <int D, int I, int M, bool HEAD, bool TAIL>
-__global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P) {
+template <int D, int I, int M, bool HEAD, bool TAIL, typename O>
+__device__ __forceinline__ void layer_fused_body(const FusedParams& P) {
   static_assert(D == 256 && M == 256 && I == 128, "built for the default denoiser widths");
+  constexpr bool WH = O::kFixed;             // whole workgroups: every row of the tile exists
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -172,26 +215,32 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
   float* vecs = reinterpret_cast<float*>(smem);
   const char* ring0 = smem + VECB;
   HalfGuard hg;
-  WStream ws;
+  typename O::Stream ws;
   ws.ring = smem + VECB + wave * (SLAB / FW);
   ws.src = P.wpack + wave * (SLAB / FW) + lane * 16;
   ws.half = 0;
   ws.issue_slot = 0;
   ws.cur = 0;
-  ws.dbg = P.dbg;
+  ws.dbg = O::dbg(P);
   ws.tot = ws.t1 = ws.t2 = ws.t3 = 0;
   ws.all = 0;
   ws.wave = wave;
   ws.probe = 0;
-  ws.ts = (P.ts != nullptr && blockIdx.x == 0 && lane == 0) ? P.ts + wave * 64 : nullptr;
+  ws.ts = (O::ts(P) != nullptr && blockIdx.x == 0 && lane == 0) ? O::ts(P) + wave * 64 : nullptr;
   WMZ_TS(0);
   const long tok0 = (long)blockIdx.x * (TW * FW) + wave * TW;        // first token of this wave
   const long tok = tok0 + (lane & 31);
-  const long tokc = tok < P.ntok ? tok : P.ntok - 1;                  // clamped: loads are unconditional
+  const long tokc = WH || tok < P.ntok ? tok : P.ntok - 1;            // clamped: loads are unconditional
   // tiled stream: ntok is a whole number of 32-token tiles, a wave's tile is all valid or all beyond the end -- a wave
   // beyond the end re-reads the last tile and stores nothing
-  const bool tile_ok = tok0 < P.ntok;
+  const bool tile_ok = WH || tok0 < P.ntok;
   const long tok0c = tile_ok ? tok0 : (P.ntok >= 32 ? P.ntok - 32 : 0);
+  const int xflags = O::xflags(P);
+  bf16_t* const x1o = O::train(P.x1o);                                 // the training outputs (all NULL for inference)
+  bf16_t* const xo_rm = O::train(P.xo_rm);
+  bf16_t* const zt = O::train(P.zt);
+  float* const st_ff = O::train(P.st_ff);
+  float* const st_attn = O::train(P.st_attn);
   char* stg = smem + VECB + RING * SLAB + wave * 8192;                // this wave's store-staging image
   static_assert(VECB == 8192 && 8 % FW == 0, "vector block is 2048 floats, 8 / FW KB per wave");
   const float* v_bout = vecs + h * (D / 2);                            // bout[D] b1'[M] b2[D] bk'[I] bv'[I]
@@ -207,13 +256,23 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
     // Everything the chain needs is requested up front, most urgent first, and nothing is waited for as a whole: the o
     // tile and the vectors by LDS-DMA, three weight slabs, then the residual rows (needed only after the first GEMM) by
     // loads the compiler does not track (it would drain the whole queue, weight ring included, at their first use).
-    stage_dma128(stg, P.o, I, tok0, P.ntok, lane);                     // o tile -> the wave's LDS image (coalesced)
+    stage_dma128<WH>(stg, P.o, I, tok0, P.ntok, lane);                     // o tile -> the wave's LDS image (coalesced)
     vec_dma(vecs, P.vec, wave, lane);
 #pragma unroll
     for (int i = 0; i < RING - 1; ++i) ws_issue(ws);                   // prime: RING-1 slabs in flight
-    const bool xt = (P.xflags & WMZ_FUSED_X_IN_TILED) != 0;
-    {
-      const bf16_t* xp = xt ? P.x + src_row(P, tok0c) * D + lane * 8 : P.x + src_row(P, tokc) * D + h * (D / 2);
+    const bool xt = (xflags & WMZ_FUSED_X_IN_TILED) != 0;
+    if constexpr (WH && (O::kXflags & WMZ_FUSED_X_IN_TILED) != 0) {   // the tile's 16 KB from its scalar base, 4 lane offsets
+      const bf16_t* tile = P.x + tok0 * D;
+#pragma unroll
+      for (int s4 = 0; s4 < D / 64; ++s4) {
+        const unsigned voff = (unsigned)(lane * 16 + s4 * 4096);
+        xb[4 * s4 + 0].v = gload_untracked<0>(tile, voff);
+        xb[4 * s4 + 1].v = gload_untracked<1024>(tile, voff);
+        xb[4 * s4 + 2].v = gload_untracked<2048>(tile, voff);
+        xb[4 * s4 + 3].v = gload_untracked<3072>(tile, voff);
+      }
+    } else {
+      const bf16_t* xp = xt ? P.x + O::src_row(P, tok0c) * D + lane * 8 : P.x + O::src_row(P, tokc) * D + h * (D / 2);
       const int xs = xt ? 64 * 8 : 8;                                  // elements between consecutive k-steps
 #pragma unroll
       for (int s = 0; s < D / 16; ++s) xb[s].v = gload_untracked(xp + s * xs);
@@ -234,17 +293,17 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
     wait_untracked<D / 16>(xb);                                        // the residual rows are older than the ring's 6 pieces
     WMZ_TS(45);
     add_bop<D / 32>(xr, xb);                                           // + x  -> x1
-    const bool x1_hat = (P.xflags & WMZ_FUSED_X1_NORMALISED) != 0;
-    if (P.x1o != nullptr && !x1_hat) {                                 // training, op-by-op backward: x1 itself
+    const bool x1_hat = (xflags & WMZ_FUSED_X1_NORMALISED) != 0;
+    if (x1o != nullptr && !x1_hat) {                                   // training, op-by-op backward: x1 itself
       bop_from_acc<D / 32>(xb, xr);
-      store_tile256(stg, P.x1o, tok0, P.ntok, xb, lane, hg);
+      store_tile256(stg, x1o, tok0, P.ntok, xb, lane, hg);
       ws_extra(ws, 16);
     }
     WMZ_TS(3);
-    ln_to_bop<D / 32>(xb, xr, P.eps, P.st_ff, tok, P.ntok, lane);   // LN2(x1)
-    if (P.st_ff != nullptr) ws_extra(ws, 2);
-    if (P.x1o != nullptr && x1_hat) {                                  // training, fused backward: the NORMALISED rows -- all the
-      store_tile256(stg, P.x1o, tok0, P.ntok, xb, lane, hg);               // backward needs of x1 (LayerNorm backward and the dW1
+    ln_to_bop<D / 32>(xb, xr, P.eps, st_ff, tok, P.ntok, lane);     // LN2(x1)
+    if (st_ff != nullptr) ws_extra(ws, 2);
+    if (x1o != nullptr && x1_hat) {                                    // training, fused backward: the NORMALISED rows -- all the
+      store_tile256(stg, x1o, tok0, P.ntok, xb, lane, hg);                 // backward needs of x1 (LayerNorm backward and the dW1
       ws_extra(ws, 16);                                                // operand), already in registers as the W1 operand
     }
     WMZ_TS(4);
@@ -265,19 +324,18 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
       float y[8];
       init_vec<1>(zc, v_b1);
       gemm_stage_b<1, D / 16>(zc, lnb, ring0, ws, lane);                           // z0 = b1[0] + W1[0] LN2(x1)
-      const bool zsave = P.zt != nullptr && tile_ok;
-      if (zsave) { store_z_tiled(P.zt, tok0, 0, zc[0], lane); ws_extra(ws, 2); }
+      const bool zsave = zt != nullptr && tile_ok;
+      if (zsave) { store_z_tiled(zt, tok0, 0, zc[0], lane); ws_extra(ws, 2); }
       WMZ_TS(5);
       init_vec<1>(zn, v_b1 + MC);
       gemm_stage_b<1, D / 16>(zn, lnb, ring0, ws, lane, side_work<9>([&](int g) {  // z1 | GELU(0), all of it
         gelu_n(y, zc[0], 4 * g, (g & 1) * 4, 4);
         if (g & 1) pack8(gb[g >> 1], y);
       }));
-      if (zsave) { store_z_tiled(P.zt, tok0, 1, zn[0], lane); ws_extra(ws, 2); }
+      if (zsave) { store_z_tiled(zt, tok0, 1, zn[0], lane); ws_extra(ws, 2); }
       zc[0] = zn[0];
       WMZ_TS(6);
-#pragma unroll 1
-      for (int c = 1; c < M / MC - 1; ++c) {                                       // zc = z_c, gb = GELU(c-1)
+      auto chunk = [&](int c) {                                                    // zc = z_c, gb = GELU(c-1)
         if (c == 4) ws.probe = 48;
         gemm_stage<D / 32, MC / 16>(xr, gb, ring0, ws, lane, side_work<5>([&](int g) {   // x1 += W2[:, c-1] GELU(c-1) | GELU(c) 0..7
           gelu_n(y, zc[0], 2 * g, 2 * g, 2);
@@ -292,11 +350,21 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
           if (g == 3) pack8(gn[1], y);
         }));
         ws.probe = 0;
-        if (zsave) { store_z_tiled(P.zt, tok0, c + 1, zn[0], lane); ws_extra(ws, 2); }
+        if (zsave) { store_z_tiled(zt, tok0, c + 1, zn[0], lane); ws_extra(ws, 2); }
         WMZ_TS(7 + 3 * c);
         zc[0] = zn[0];
         gb[0] = gn[0];
         gb[1] = gn[1];
+      };
+      // One slab per chunk: with a ring of two the ring slot alternates from trip to trip, so the fixed policy walks the
+      // chunks in pairs -- slot, granule and tallies are then constants at every point of the loop body as well.
+      static_assert((M / MC - 2) % 2 == 0, "chunks 1 .. M/MC-2 in pairs");
+      if constexpr (O::kFixed && RING * HPS <= 4) {
+#pragma unroll 1
+        for (int c = 1; c < M / MC - 1; c += 2) { chunk(c); chunk(c + 1); }
+      } else {
+#pragma unroll 1
+        for (int c = 1; c < M / MC - 1; ++c) chunk(c);
       }
       gemm_stage<D / 32, MC / 16>(xr, gb, ring0, ws, lane, side_work<9>([&](int g) {     // x1 += W2[:, 6] GELU(6) | GELU(7), all of it
         gelu_n(y, zc[0], 4 * g, (g & 1) * 4, 4);
@@ -308,17 +376,17 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
     add_vec<D / 32>(xr, v_b2);                                         //                 -> x2
     Frag8<bf16_t> x2b[D / 16];                                         // x2 as the stream carries it
     if constexpr (TAIL) {                                              // + LN1'(x2), while x2 is still fp32
-      ln_and_pack<D / 32>(xb, x2b, xr, P.eps, P.st_attn, tok, P.ntok, lane);
-      if (P.st_attn != nullptr) ws_extra(ws, 2);
+      ln_and_pack<D / 32>(xb, x2b, xr, P.eps, st_attn, tok, P.ntok, lane);
+      if (st_attn != nullptr) ws_extra(ws, 2);
     }
     else bop_from_acc<D / 32>(x2b, xr);
     WMZ_TS(30);
-    if (P.xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16>(P.xo + tok0 * D, x2b, lane, hg); }
-    else store_tile256(stg, P.xo, tok0, P.ntok, x2b, lane, hg);
+    if (xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16, WH>(P.xo + tok0 * D, x2b, lane, hg); }
+    else store_tile256<WH>(stg, P.xo, tok0, P.ntok, x2b, lane, hg);
     ws_extra(ws, 16);
-    if (P.xo_rm != nullptr) {        // training: the row-major copy for the backward -- x2 itself, or (WMZ_FUSED_XRM_NORMALISED)
-      if (TAIL && (P.xflags & WMZ_FUSED_XRM_NORMALISED)) store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane, hg);   // LN1'(x2)'s rows
-      else store_tile256(stg, P.xo_rm, tok0, P.ntok, x2b, lane, hg);
+    if (xo_rm != nullptr) {          // training: the row-major copy for the backward -- x2 itself, or (WMZ_FUSED_XRM_NORMALISED)
+      if (TAIL && (xflags & WMZ_FUSED_XRM_NORMALISED)) store_tile256(stg, xo_rm, tok0, P.ntok, xb, lane, hg);   // LN1'(x2)'s rows
+      else store_tile256(stg, xo_rm, tok0, P.ntok, x2b, lane, hg);
       ws_extra(ws, 16);
     }
     WMZ_TS(31);
@@ -330,13 +398,13 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
       bop_from_acc<I / 32>(qkvb, qa);                                  // stored under the to_k MFMAs below
     }
   } else {
-    if (P.z != nullptr) {                                            // first layer: x = embedding, also written to x_out
-      const bool coop = P.W == 16 && (P.H * 16) % 32 == 0 && (P.rows_out == 0 || (P.rows_out % 32 == 0 && P.rows_in % 32 == 0 && P.row0 % 32 == 0));
-      if (coop) embed_coop<D>(xb, stg, P, tok0, lane);
-      else embed_bop<D>(xb, P, tokc, true, h);
+    if (O::embed(P)) {                                               // first layer: x = embedding, also written to x_out
+      const bool coop = WH || (P.W == 16 && (P.H * 16) % 32 == 0 && (P.rows_out == 0 || (P.rows_out % 32 == 0 && P.rows_in % 32 == 0 && P.row0 % 32 == 0)));
+      if (coop) embed_coop<D, O>(xb, stg, P, tok0, lane);
+      else embed_bop<D, O>(xb, P, tokc, true, h);
     }
-    else if (P.xflags & WMZ_FUSED_X_IN_TILED) load_bop_tiled<D / 16>(xb, P.x + src_row(P, tok0c) * D, lane);
-    else load_bop<D / 16>(xb, P.x + src_row(P, tokc) * D + h * (D / 2));
+    else if (xflags & WMZ_FUSED_X_IN_TILED) load_bop_tiled<D / 16>(xb, P.x + O::src_row(P, tok0c) * D, lane);
+    else load_bop<D / 16>(xb, P.x + O::src_row(P, tokc) * D + h * (D / 2));
     f32x4 vecv[8 / FW];
 #pragma unroll
     for (int i = 0; i < 8 / FW; ++i) vecv[i] = *reinterpret_cast<const f32x4*>(P.vec + (tid + i * NTHR) * 4);
@@ -345,11 +413,11 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
 #pragma unroll
     for (int i = 0; i < 8 / FW; ++i) *reinterpret_cast<f32x4*>(vecs + (tid + i * NTHR) * 4) = vecv[i];
     __syncthreads();
-    if (P.z != nullptr) {
-      if (P.xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16>(P.xo + tok0 * D, xb, lane, hg); }
-      else store_tile256(stg, P.xo, tok0, P.ntok, xb, lane, hg);
+    if (O::embed(P)) {
+      if (xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16, WH>(P.xo + tok0 * D, xb, lane, hg); }
+      else store_tile256<WH>(stg, P.xo, tok0, P.ntok, xb, lane, hg);
       ws_extra(ws, 16);
-      if (P.xo_rm != nullptr && !(P.xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane, hg); ws_extra(ws, 16); }
+      if (xo_rm != nullptr && !(xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, xo_rm, tok0, P.ntok, xb, lane, hg); ws_extra(ws, 16); }
     }
     {
       f32x16 qa[I / 32];
@@ -358,35 +426,49 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P
       bop_from_acc<I / 32>(qkvb, qa);
     }
     acc_from_bop<D / 32>(xr, xb);
-    ln_to_bop<D / 32>(xb, xr, P.eps, P.st_attn, tok, P.ntok, lane);   // LN1'(x)
-    if (P.st_attn != nullptr) ws_extra(ws, 2);
-    if (P.xo_rm != nullptr && (P.xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, P.xo_rm, tok0, P.ntok, xb, lane, hg); ws_extra(ws, 16); }
+    ln_to_bop<D / 32>(xb, xr, P.eps, st_attn, tok, P.ntok, lane);     // LN1'(x)
+    if (st_attn != nullptr) ws_extra(ws, 2);
+    if (xo_rm != nullptr && (xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, xo_rm, tok0, P.ntok, xb, lane, hg); ws_extra(ws, 16); }
   }
   if constexpr (TAIL) {
     f32x16 ka[I / 32];
     Frag8<bf16_t> kb[I / 16];
     init_vec<I / 32>(ka, v_bk);
-    store_tile128(stg, P.q, I, tok0, P.ntok, 0, qkvb, lane, hg);         // q rows (as side work under the to_k MFMAs: slower)
+    store_tile128<WH>(stg, P.q, I, tok0, P.ntok, 0, qkvb, lane, hg);     // q rows (as side work under the to_k MFMAs: slower)
     ws_extra(ws, 8);
     WMZ_TS(33);
     gemm_stage<I / 32, D / 16>(ka, xb, ring0, ws, lane);               // to_k
     WMZ_TS(34);
     bop_from_acc<I / 32>(kb, ka);
-    if (P.kv_combined) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, 0, kb, lane, hg);   // k | v column halves of [ntok, 2I]
-    else store_tile128(stg, P.kv, I, tok0, P.ntok, 0, kb, lane, hg);       // k rows
+    if (O::kv_combined(P)) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, 0, kb, lane, hg);   // k | v column halves of [ntok, 2I]
+    else store_tile128<WH>(stg, P.kv, I, tok0, P.ntok, 0, kb, lane, hg);   // k rows
     ws_extra(ws, 8);
     init_vec<I / 32>(ka, v_bv);
     WMZ_TS(35);
     gemm_stage<I / 32, D / 16>(ka, xb, ring0, ws, lane);               // to_v
     WMZ_TS(36);
     bop_from_acc<I / 32>(kb, ka);
-    if (P.kv_combined) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, I, kb, lane, hg);
-    else store_tile128(stg, P.kv + (long)P.ntok * I, I, tok0, P.ntok, 0, kb, lane, hg);    // v rows, behind the k rows
+    if (O::kv_combined(P)) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, I, kb, lane, hg);
+    else store_tile128<WH>(stg, P.kv + (long)P.ntok * I, I, tok0, P.ntok, 0, kb, lane, hg);    // v rows, behind the k rows
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the padding slabs still in flight target this workgroup's LDS
   hg.commit();
   WMZ_TS(37);
 }
+
+// Every caller's kernel: the options of a launch come with its arguments.
+template <int D, int I, int M, bool HEAD, bool TAIL>
+__global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_kernel(FusedParams P) {
+  layer_fused_body<D, I, M, HEAD, TAIL, OptRuntime>(P);
+}
+#ifndef WMZ_OP16_F16
+// The inference unit (bfloat16 only): the same body with the options of the plain full-grid inference step compiled in --
+// embedding + tail (x_out tiled), head + tail (tiled in and out), head only (the last layer: tiled in, row-major out).
+template <bool HEAD, bool TAIL>
+__global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_infer_kernel(FusedParams P) {
+  layer_fused_body<256, 128, 256, HEAD, TAIL, OptInfer<(HEAD ? WMZ_FUSED_X_IN_TILED : 0) | (TAIL ? WMZ_FUSED_X_OUT_TILED : 0)>>(P);
+}
+#endif
 
 }  // namespace
 
@@ -401,7 +483,8 @@ static FusedParams fused_params(const void* o, const void* x, void* x_out, void*
   return P;
 }
 static long long* g_fused_ts = nullptr;
-static int g_fused_dbg = 0;       // ablation switches (wmz_debug_fused_knobs): 1 = skip the MFMA loops, 2 = skip the weight DMA + waits
+static int g_fused_dbg = 0;       // ablation switches (wmz_debug_fused_knobs): 1 = skip the MFMA loops, 2 = skip the weight DMA + waits,
+                                  // 4 = no per-slab barrier, 8 = keep the run-time kernel where the inference unit would run (A/B)
 #ifndef WMZ_OP16_F16
 extern "C" int wmz_debug_fused_knobs(int dbg) { g_fused_dbg = dbg; return WMZ_OK; }
 // Timing probe for kernel development (tools/ts_fused.py): a device buffer of 8 * 64 int64; NULL switches it off.
@@ -661,6 +744,19 @@ extern "C" int WMZ_FN(wmz_embed_qkv_fused_fwd_planes)(const int64_t* z, const fl
   return fused_launch(P, P.ntok, D, I, M, 0, 1, stream);
 }
 
+// One instantiation's launch.  Its dynamic LDS limit is raised once per device, not on every launch (the attribute belongs to
+// the device's copy of the function).
+template <void (*KERN)(FusedParams)>
+static void fused_launch_kernel(const FusedParams& P, dim3 grid, hipStream_t st) {
+  static std::atomic<bool> raised[64];
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(KERN, grid, dim3(NTHR), VECB + RING * SLAB + FW * 8192, st, P);
+}
+
 static int fused_launch(FusedParams& P, int ntok, int D, int I, int M, int has_head, int has_tail, void* stream) {
   if (!(D == 256 && I == 128 && M == 256)) {
     wmz_set_error("wmz_layer_fused_fwd: built for dim 256 / inner 128 / mlp 256 (got %d/%d/%d); use the unfused path", D, I, M);
@@ -668,19 +764,25 @@ static int fused_launch(FusedParams& P, int ntok, int D, int I, int M, int has_h
   }
   P.dbg = g_fused_dbg;
   P.ts = g_fused_ts;
-  const size_t smem = VECB + RING * SLAB + FW * 8192;
-  dim3 grid((unsigned)wmz_cdiv(ntok, TW * FW)), block(NTHR);
+  const dim3 grid((unsigned)wmz_cdiv(ntok, TW * FW));
   hipStream_t st = (hipStream_t)stream;
-#define WMZ_FUSED(H, T)                                                                                            \
-  do {                                                                                                             \
-    auto kern = layer_fused_kernel<256, 128, 256, H, T>;                                                           \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL(kern, grid, block, smem, st, P);                                                            \
-  } while (0)
-  if (has_head && has_tail) WMZ_FUSED(true, true);
-  else if (has_head) WMZ_FUSED(true, false);
-  else WMZ_FUSED(false, true);
-#undef WMZ_FUSED
+#ifndef WMZ_OP16_F16
+  // The inference unit: whole workgroups, nothing optional asked for, and the layout its instantiation was built for.  Every
+  // other launch -- the cone, ragged counts, 8-wide planes, row-major streams, training, the timing tools -- keeps the run-time
+  // kernel, and so does everything while a knob is set (8 asks for exactly that).
+  const bool plain = ntok % (TW * FW) == 0 && !P.x1o && !P.xo_rm && !P.st_ff && !P.st_attn && !P.zt && !P.kv_combined &&
+                     P.rows_out == 0 && g_fused_dbg == 0 && g_fused_ts == nullptr;
+  if (plain && has_head && has_tail && P.xflags == (WMZ_FUSED_X_IN_TILED | WMZ_FUSED_X_OUT_TILED))
+    fused_launch_kernel<layer_fused_infer_kernel<true, true>>(P, grid, st);
+  else if (plain && has_head && !has_tail && P.xflags == WMZ_FUSED_X_IN_TILED)
+    fused_launch_kernel<layer_fused_infer_kernel<true, false>>(P, grid, st);
+  else if (plain && !has_head && P.z != nullptr && P.xflags == WMZ_FUSED_X_OUT_TILED && P.W == 16 && P.H % 2 == 0)
+    fused_launch_kernel<layer_fused_infer_kernel<false, true>>(P, grid, st);
+  else
+#endif
+  if (has_head && has_tail) fused_launch_kernel<layer_fused_kernel<256, 128, 256, true, true>>(P, grid, st);
+  else if (has_head) fused_launch_kernel<layer_fused_kernel<256, 128, 256, true, false>>(P, grid, st);
+  else fused_launch_kernel<layer_fused_kernel<256, 128, 256, false, true>>(P, grid, st);
   WMZ_LAUNCH_CHECK("wmz_layer_fused_fwd");
   return WMZ_OK;
 }

@@ -10,7 +10,8 @@ extern "C" {
  * buf (device, 8 waves x 64 int64); NULL (default) switches the probe off. */
 int wmz_debug_fused_timestamps(void* buf);
 /* Ablation switches of the fused per-token kernel (timing experiments only, results are garbage): 1 = skip the MFMA loops,
- * 2 = skip the weight DMA and its waits, 4 = skip the per-slab workgroup barrier (bits combine); 0 = product behaviour. */
+ * 2 = skip the weight DMA and its waits, 4 = skip the per-slab workgroup barrier (bits combine); 8 = keep the run-time kernel where
+ * the inference unit (layer_fused_infer_kernel) would run -- same results, A/B timing and tests; 0 = product behaviour. */
 int wmz_debug_fused_knobs(int dbg);
 /* Same for the 16-wide-plane attention forward kernel (16 waves x 64 int64). */
 int wmz_debug_attn_timestamps(void* buf);
