@@ -721,6 +721,49 @@ int wmz_categorical_scatter_filtered(const float* logits, long ld, long R, int C
                                      const unsigned char* known, long known_stride, const float* uniforms, float* kept_floor,
                                      unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
                                      void* stream);
+/* Confidence-ordered masking for config 5's sampler: the tokens hidden from the model in a context are the ones it was least sure
+ * of, not a coin per slot.  The sparse sampler masks when it GATHERS, not behind its draw, so the order needs a score per clip
+ * position that lives between sub-steps: scores, fp32 [B, S * HW] (clip stride scores_stride), addressed like z.  The caller fills
+ * it with -inf beside an all-mask clip: a position never drawn is hidden first.
+ *   scored scatter  wmz_categorical_scatter_scored: the 20 arguments of wmz_categorical_scatter_filtered in place, then scores and
+ *             scores_stride.  The draw is exactly wmz_categorical_scatter_filtered's by its row-read-once kernels (registers up to
+ *             2048 classes, LDS up to wmz_sample_tokens_max_classes(); `scores` counts as a probe like uniforms and kept_floor, so
+ *             neutral filters take these kernels too; rows 16-byte aligned; more classes: WMZ_ERR_UNSUPPORTED, nothing written):
+ *             the same logits, filters, uniforms, seed, stream id and counter give the samples and the z that entry point writes
+ *             with a probe given, bit for bit.  z must be given.
+ *             scores[clip * scores_stride + indices[row]] = (l_d - max) - log(sum over ALL classes c of exp(l_c - max)), l the
+ *             scaled logits BEFORE top-k and the nucleus, d the draw: the score law of wmz_sample_tokens_scored_dev below with
+ *             noise = 0, word for word; a NaN is stored as -inf.  The score is written exactly where the token is written: nothing
+ *             where `known` is non-zero, nothing outside indices.  scores == NULL: wmz_categorical_scatter_filtered (forwards).
+ *   scored context draw  wmz_sparse_draw_context_scored: the 19 arguments of wmz_sparse_draw_context_known in place, then scores,
+ *             scores_stride, noise and slot_scores.  p_uniform must be 0 (the sampler masks only), noise finite and >= 0, scores
+ *             not NULL: WMZ_ERR_ARG otherwise.  The window, the n positions, their order, indices and target are exactly those of
+ *             wmz_sparse_draw_context_known for the same (seed, stream id, counter), every Philox word read from the same
+ *             position: the rule shifts no random stream.
+ *             slot score  s_i = scores[b * scores_stride + pos_i]; with noise > 0, s_i += noise * rc * g(u_i), g(u) = -log(-log u),
+ *                         rc = clamp(r[b], 0, 1), u_i the unit of the THIRD word of philox4(b * n + i, stream id, seed) -- the
+ *                         word the random rule compares with r --, the products in that order (noise * rc, then * g); noise == 0:
+ *                         the term is not evaluated.  A NaN becomes -inf.  slot_scores (optional probe, [B, n] fp32) receives
+ *                         s_i of every slot, which makes the selection checkable exactly.
+ *             count       m = (int)floorf(rc * (float)n), one fp32 multiply rounded on its own.
+ *             candidates  the slots whose position is not `known`.
+ *             selection   the min(m, #candidates) candidates with the LOWEST s_i get tokens = C, the mask token; every other slot
+ *                         tokens = target.  The order is that of the order-preserving key of the score's bits (as for
+ *                         wmz_remask_lowest_dev below), ties go to the LOWER slot index first.  Exact given the fp32 values in
+ *                         memory: no tolerance applies.  r = 0 masks nothing, r = 1 every candidate.
+ *             Still one workgroup per clip and one launch: the selection is a last phase over the <= 512 slot keys, the bitwise
+ *             threshold search by wave ballots that wmz_remask_lowest_dev runs.
+ * Neither advances a counter; both only enqueue and allocate nothing. */
+int wmz_categorical_scatter_scored(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
+                                   const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip, int64_t* samples,
+                                   const unsigned char* known, long known_stride, const float* uniforms, float* kept_floor,
+                                   unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
+                                   void* stream, float* scores, long scores_stride);
+int wmz_sparse_draw_context_scored(const int64_t* z, long clip_stride, const float* r, const float* o, int64_t* indices,
+                                   int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
+                                   unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
+                                   void* stream, const unsigned char* known, long known_stride, const float* scores,
+                                   long scores_stride, float noise, float* slot_scores);
 /* One step of the sampler loop between two forward passes (main.py:76-104): per row of fp32 logits [R, C <= 2048] keep the
  * top_k largest (<= 0: all; ties with the k-th kept), softmax, draw a class by the inverse CDF from one in-kernel uniform,
  * re-mask with a second one: the position gets mask_token where u2 > alpha (and, with `last_mask` [R] bytes, in / out, only

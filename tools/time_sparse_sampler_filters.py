@@ -7,8 +7,10 @@ rows per draw), VqSparseDiffusionModel dim 512 / 4 x 128 / depth 8 / mlp 1024, b
     topk      sample_topk=100
     all       sample_topk=100, sample_topp=0.9, temperature=0.7
     prompt    the same with a prompt that gives the first half of the frames
+    confidence        remask='confidence' (wmz_sparse_draw_context_scored + wmz_categorical_scatter_scored), no filter
+    confidence+topk   the same with sample_topk=100
 
-(the last three in trees that take them), in ONE process, in alternating groups.  A call captures its own graph, so a group times
+(all but the first in trees that take them), in ONE process, in alternating groups.  A call captures its own graph, so a group times
 two calls that differ in the number of iterations only and reports the DIFFERENCE per sub-step: the capture, the warm-up sub-step
 and the set-up are in both and cancel.
 
@@ -16,7 +18,7 @@ and the set-up are in both and cancel.
         one JSON line: median / min / max ms per captured sub-step over the groups, (max - min) / median as the spread.
         --variants: only these (a process that holds one model is the like-for-like of a tree that has only `default`)
         --root: the tree to import world_modelz_amd from (compare two checkouts by running the tool once for each)
-    python tools/time_sparse_sampler_filters.py --replay default|topk|all|prompt [--iterations 3]
+    python tools/time_sparse_sampler_filters.py --replay default|topk|all|prompt|confidence|confidence+topk [--iterations 3]
         nothing but one sample_clips call of that variant: the program to put behind `rocprofv3 --kernel-trace --stats --`
 """
 import argparse
@@ -32,7 +34,8 @@ SHAPE, CLIPS, CODES, CONTEXT = (64, 16, 16), 8, 8192, 512
 SUBSTEPS = SHAPE[0] * SHAPE[1] * SHAPE[2] // CONTEXT + 1            # per iteration
 SHORT, LONG = 2, 6                                                   # iterations of the two calls of a group
 FILTERS = {'default': {}, 'topk': dict(sample_topk=100), 'all': dict(sample_topk=100, sample_topp=0.9, temperature=0.7),
-           'prompt': dict(sample_topk=100, sample_topp=0.9, temperature=0.7)}
+           'prompt': dict(sample_topk=100, sample_topp=0.9, temperature=0.7),
+           'confidence': dict(remask='confidence'), 'confidence+topk': dict(remask='confidence', sample_topk=100)}
 
 
 def build(name):
@@ -71,12 +74,12 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit('no GPU: a timing from anywhere else says nothing')
     config.set_compute_dtype(torch.bfloat16)
-    has_filters = 'sample_topp' in inspect.signature(sparse_diffusion.sample_clips).parameters
+    taken = inspect.signature(sparse_diffusion.sample_clips).parameters
     if args.replay:
         build(args.replay)(args.iterations)
         torch.cuda.synchronize()
         return
-    variants = {name: build(name) for name in args.variants.split(',') if has_filters or name == 'default'}
+    variants = {name: build(name) for name in args.variants.split(',') if all(k in taken for k in FILTERS[name])}
     for fn in variants.values():                        # every variant warm (operand copies, allocator) before a clock starts
         timed(fn, SHORT)
     groups = {name: [] for name in variants}

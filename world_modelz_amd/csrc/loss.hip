@@ -6,6 +6,7 @@
 #include "wmz_common.h"
 #include "wmz_internal.h"
 #include "wmz_philox.h"
+#include "wmz_select.h"
 #include <type_traits>
 
 namespace {
@@ -86,6 +87,16 @@ __device__ __forceinline__ SparseOut sparse_out(const A& a, const Rest&... rest)
 }
 template <typename T, typename... Ts>
 constexpr bool pack_has = (std::is_same<T, Ts>::value || ...);
+// The scored sparse form (wmz_categorical_scatter_scored): a SparseScore behind the SparseOut compiles in SPARSE and the sum over
+// all classes of SCORED; the score -- sample_score without noise -- goes where wmz_sparse_write_scored puts the token.
+typedef WmzSparseScore SparseScore;
+__device__ __forceinline__ SampleExtras sample_extras(const SampleExtras& x, const SparseOut&, const SparseScore&) { return x; }
+__device__ __forceinline__ ScoreOut score_out(const SampleExtras&, const SparseOut&, const SparseScore&) { return ScoreOut{}; }
+__device__ __forceinline__ SparseScore sparse_score() { return SparseScore{}; }
+template <typename A, typename... Rest>
+__device__ __forceinline__ SparseScore sparse_score(const A& a, const Rest&... rest) {
+  if constexpr (std::is_same<A, SparseScore>::value) return a; else return sparse_score(rest...);
+}
 // the dense step's counter and alpha: not read in the sparse form, whose launch passes NULL for both
 template <bool SPARSE>
 __device__ __forceinline__ long dense_counter(const long long* counter) {
@@ -94,16 +105,6 @@ __device__ __forceinline__ long dense_counter(const long long* counter) {
 template <bool SPARSE>
 __device__ __forceinline__ float dense_alpha(const float* alphas, int n_alpha, long ctr) {
   if constexpr (SPARSE) return 0.f; else return alphas[(int)(ctr % n_alpha)];
-}
-
-// a product / a difference that the law rounds on its own: never one half of a contracted multiply-add
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
 }
 
 // score of a drawn row: lp = (l_d - max) - log(sum over all classes); NaN -> -inf
@@ -115,7 +116,7 @@ __device__ __forceinline__ float sample_score(float l_d, float m, float sum_all,
 
 // (`extras`: nothing -- the kernel of wmz_sample_tokens_dev, its arguments as they always were --, one SampleExtras, or a
 //  SampleExtras and a ScoreOut: the scored form, or a SampleExtras and a SparseOut: the sparse form, which leaves the dense
-//  step's own arguments -- alphas .. counter -- unread)
+//  step's own arguments -- alphas .. counter -- unread; a SparseScore behind the SparseOut: the scored sparse form)
 template <int NV, bool TEMP = false, bool TOPP = false, typename... Extras>
 __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restrict__ logits, long ld, int R, int C, int top_k,
                                                             const float* __restrict__ alphas, int n_alpha, int64_t mask_token,
@@ -123,13 +124,16 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
                                                             long block_stride, int64_t* __restrict__ denoised,
                                                             unsigned char* __restrict__ last_mask, unsigned long long seed,
                                                             const long long* __restrict__ counter, Extras... extras) {
-  static_assert(sizeof...(Extras) <= 2 && (sizeof...(Extras) >= 1 || !(TEMP || TOPP)), "the filters read their values from a SampleExtras");
+  static_assert(sizeof...(Extras) <= 3 && (sizeof...(Extras) >= 1 || !(TEMP || TOPP)), "the filters read their values from a SampleExtras");
   constexpr bool PROBES = sizeof...(Extras) >= 1;
-  constexpr bool SCORED = pack_has<ScoreOut, Extras...>;
+  constexpr bool SPARSE_SCORED = pack_has<SparseScore, Extras...>;
+  constexpr bool SCORED = pack_has<ScoreOut, Extras...> || SPARSE_SCORED;
   constexpr bool SPARSE = pack_has<SparseOut, Extras...>;
+  static_assert(!SPARSE_SCORED || SPARSE, "a SparseScore follows a SparseOut");
   const SampleExtras x = sample_extras(extras...);
   const ScoreOut so = score_out(extras...);
   const SparseOut sp = sparse_out(extras...);
+  const SparseScore ss = sparse_score(extras...);
   const int lane = threadIdx.x & 63;
   const long ctr = dense_counter<SPARSE>(counter);
   const float alpha = dense_alpha<SPARSE>(alphas, n_alpha, ctr);
@@ -265,7 +269,12 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
         if (lane == 0) x.kept_floor[row] = f;
       }
     }
-    if constexpr (SPARSE) {
+    if constexpr (SPARSE_SCORED) {
+      if (lane == 0) {
+        const float l_d = TEMP ? mul_rn(logits[row * ld + draw], x.inv_temperature) : logits[row * ld + draw];
+        wmz_sparse_write_scored(sp, ss, row, draw, sample_score(l_d, m, all_kept ? total : sum_all, 0.f, 0.f, 0.f));
+      }
+    } else if constexpr (SPARSE) {
       if (lane == 0) wmz_sparse_write(sp, row, draw);
     } else if constexpr (SCORED) {
       if (lane == 0) {
@@ -299,17 +308,12 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
 //     a class of weight 0 is never drawn, whatever the rounding of the partial sums.
 // The kept_floor probe alone walks the global row a second time (the keys are gone by then): it is NULL in production.
 // (`score`: nothing, or one ScoreOut -- the scored form: where a filter acts, one more walk of the thread's slots in front of top-k
-//  sums exp(l - max) over all classes; else that sum is the draw's total.)
+//  sums exp(l - max) over all classes; else that sum is the draw's total --, or one SparseOut, or a SparseOut and a SparseScore.)
 constexpr int SW_NT = 256;
 constexpr int SW_MAX_CLASSES = 16384;
 constexpr int SW_RED_WORDS = 16;          // two alternating sets of (SW_NT / 64 waves) x 2 words behind the row
 
-__device__ __forceinline__ unsigned sw_key(float l) {
-  const unsigned b = __float_as_uint(l);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float sw_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
+// (sw_key / sw_unkey, the order-preserving keys of the searches below: wmz_select.h)
 // The four waves' (a, b) pairs to every thread: each wave's lane 0 writes, one barrier, all read.  The sets alternate, so a wave
 // that runs ahead into the next exchange writes the other set while a slower one still reads this one.
 struct SwExchange {
@@ -335,11 +339,14 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
                                                                    const float* __restrict__ uniforms, float* __restrict__ kept_floor,
                                                                    unsigned long long seed, const long long* __restrict__ counter,
                                                                    Score... score) {
-  static_assert(sizeof...(Score) <= 1, "one ScoreOut or one SparseOut at the most");
-  constexpr bool SCORED = pack_has<ScoreOut, Score...>;
+  static_assert(sizeof...(Score) <= 2, "one ScoreOut, or one SparseOut and its SparseScore, at the most");
+  constexpr bool SPARSE_SCORED = pack_has<SparseScore, Score...>;
+  constexpr bool SCORED = pack_has<ScoreOut, Score...> || SPARSE_SCORED;
   constexpr bool SPARSE = pack_has<SparseOut, Score...>;
+  static_assert(!SPARSE_SCORED || SPARSE, "a SparseScore follows a SparseOut");
   const ScoreOut so = score_out(SampleExtras{}, score...);
   const SparseOut sp = sparse_out(score...);
+  const SparseScore ss = sparse_score(score...);
   typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
   extern __shared__ __attribute__((aligned(16))) unsigned sw_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -501,7 +508,11 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
       exchange(kmin, 0u, ra, rb);
       if (tid == 0) kept_floor[row] = sw_unkey(min(min(ra[0], ra[1]), min(ra[2], ra[3])));
     }
-    if constexpr (SPARSE) {
+    if constexpr (SPARSE_SCORED) {
+      if (tid == 0)
+        wmz_sparse_write_scored(sp, ss, row, draw,
+                                sample_score(mul_rn(x[draw], inv_temperature), m, all_kept ? total : sum_all, 0.f, 0.f, 0.f));
+    } else if constexpr (SPARSE) {
       if (tid == 0) wmz_sparse_write(sp, row, draw);
     } else if constexpr (SCORED) {
       if (tid == 0) {
@@ -527,32 +538,10 @@ __global__ __launch_bounds__(SW_NT) void sample_tokens_wide_kernel(const float* 
 // a non-candidate or a row past the clip as 0xFFFFFFFF, which no search step counts -- and the candidate bits into one more; a
 // search step is then MAXP compares and ballots without a memory access (a first form that kept the keys in LDS spent ~140 ns per
 // key read and ballot, one wave per SIMD having nothing to hide the LDS latency behind: 18 us at 256 rows, 67 us at 4096).
-//   * V = the mm-th smallest candidate key, mm = min(m, #candidates), by the bitwise search: bit by bit from the top, V takes the
-//     bit while fewer than mm candidate keys lie below V | bit (counts by wave ballots, the waves' counts through LDS);
-//   * keys below V are re-masked; of the keys equal to V the first mm - #{key < V} in ROW order: row order is j-major, so the rank
-//     of a tie is the ties of all earlier (j, wave) groups -- one count each in LDS -- plus the ties of lower lanes in its own ballot.
+// The search itself -- the mm-th smallest candidate key, mm = min(m, #candidates), ties ranked in row order -- is
+// wmz_select_lowest (wmz_select.h), which config 5's scored context draw runs too.
 constexpr int RM_MAX_ROWS = 4096;
 constexpr int RM_ONE_WAVE_ROWS = 256;
-
-template <int NW>
-struct RmTotal {                      // the workgroup's sum of one count per wave (SwExchange's alternating sets; NW == 1: the wave's own)
-  unsigned* red;
-  int turn;
-  __device__ __forceinline__ unsigned operator()(unsigned wave_count) {
-    if constexpr (NW == 1) {
-      return wave_count;
-    } else {
-      unsigned* set = red + (turn & 1) * NW;
-      turn ^= 1;
-      if ((threadIdx.x & 63) == 0) set[threadIdx.x >> 6] = wave_count;
-      __syncthreads();
-      unsigned t = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) t += set[w];
-      return t;
-    }
-  }
-};
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void remask_lowest_kernel(const float* __restrict__ scores, long n,
@@ -564,7 +553,7 @@ __global__ __launch_bounds__(64 * NW) void remask_lowest_kernel(const float* __r
   constexpr int MAXP = (NW == 1 ? RM_ONE_WAVE_ROWS : RM_MAX_ROWS) / NT;
   __shared__ unsigned ties[MAXP * NW];
   __shared__ unsigned red[2 * NW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int rows = (int)n, P = (rows + NT - 1) / NT;                         // (P <= MAXP: the launch's check)
   const long clip = blockIdx.x;
   const float alpha = alphas[(int)(*counter % n_alpha)];
@@ -587,52 +576,14 @@ __global__ __launch_bounds__(64 * NW) void remask_lowest_kernel(const float* __r
   }
   ncand = total(ncand);
   const unsigned mm = m <= 0 ? 0u : ((unsigned)m < ncand ? (unsigned)m : ncand);
-  unsigned V = 0, need = 0;
-  if (mm > 0) {                                                              // (uniform over the workgroup: the barriers inside are met by all)
-    for (int bit = 31; bit >= 0; --bit) {
-      const unsigned cv = V | (1u << bit);
-      unsigned cnt = 0;
-#pragma unroll
-      for (int j = 0; j < MAXP; ++j)                                          // (one wave: all four, without a branch: a key past P counts nothing)
-        if (NW == 1 || j < P) cnt += (unsigned)__popcll(__ballot(key[j] < cv));
-      if (total(cnt) < mm) V = cv;
-    }
-    unsigned below = 0;
-#pragma unroll
-    for (int j = 0; j < MAXP; ++j) {
-      if (j < P) {
-        below += (unsigned)__popcll(__ballot(key[j] < V));
-        const unsigned long long tb = __ballot(((cand >> j) & 1u) != 0 && key[j] == V);
-        if (lane == 0) ties[j * NW + wave] = (unsigned)__popcll(tb);
-      }
-    }
-    need = mm - total(below);                                                // (>= 1; its barrier also publishes `ties` where NW > 1)
-    if constexpr (NW == 1) __syncthreads();                                  // (one wave: no exchange above, so publish `ties` here)
-  }
-  unsigned run = 0;                                                          // ties of the groups in front of (j, wave)
+  const unsigned taken = wmz_select_lowest<NW, MAXP>(key, cand, P, mm, ties, total);
 #pragma unroll
   for (int j = 0; j < MAXP; ++j) {
-    if (j < P) {
-      const int row = j * NT + tid;
-      const bool c = ((cand >> j) & 1u) != 0;
-      bool masked = false;
-      if (mm > 0) {
-        const bool tie = c && key[j] == V;
-        const unsigned long long tb = __ballot(tie);
-        unsigned before = run;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          const unsigned t = ties[j * NW + w];
-          if (w < wave) before += t;
-          run += t;
-        }
-        const unsigned rank = before + (unsigned)__popcll(tb & ((1ull << lane) - 1ull));
-        masked = c && (key[j] < V || (tie && rank < need));
-      }
-      if (row < rows) {
-        if (masked) out_tokens[clip * block_stride + row] = mask_token;
-        if (last_mask != nullptr) last_mask[clip * n + row] = masked ? 1 : 0;
-      }
+    const int row = j * NT + tid;
+    if (j < P && row < rows) {
+      const bool masked = ((taken >> j) & 1u) != 0;
+      if (masked) out_tokens[clip * block_stride + row] = mask_token;
+      if (last_mask != nullptr) last_mask[clip * n + row] = masked ? 1 : 0;
     }
   }
 }
@@ -820,11 +771,12 @@ static int sample_tokens_launch(const char* name, const float* logits, long ld, 
   return WMZ_OK;
 }
 
-// The sparse form's launches (wmz_internal.h): the same two kernels, a SparseOut behind their arguments; the dense step's own
-// arguments are not read there.  The wide instantiation asks for its LDS itself: the attribute is per instantiation.
+// The sparse form's launches (wmz_internal.h): the same two kernels, a SparseOut behind their arguments -- and, with `score`, its
+// SparseScore behind that --; the dense step's own arguments are not read there.  The wide instantiations ask for their LDS
+// themselves: the attribute is per instantiation.
 int wmz_sparse_sample_launch(const char* name, const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
                              const float* uniforms, float* kept_floor, unsigned long long seed, const WmzSparseOut& out,
-                             hipStream_t st) {
+                             hipStream_t st, const WmzSparseScore* score) {
   const bool temp = inv_temperature != 1.f, topp = top_p < 1.f;
   if (C > 2048) {
     const int P = (wmz_cdiv(C, SW_NT) + 7) / 8 * 8;
@@ -834,8 +786,15 @@ int wmz_sparse_sample_launch(const char* name, const float* logits, long ld, int
       const int most = (int)(((size_t)SW_NT * (SW_MAX_CLASSES / SW_NT + 4) + SW_RED_WORDS) * 4);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tokens_wide_kernel<SparseOut>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 most);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tokens_wide_kernel<SparseOut, SparseScore>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, most);
     }
-    hipLaunchKernelGGL(sample_tokens_wide_kernel<SparseOut>, dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R, C, P, top_k,
+    if (score != nullptr)
+      hipLaunchKernelGGL((sample_tokens_wide_kernel<SparseOut, SparseScore>), dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R,
+                         C, P, top_k, top_p, inv_temperature, (const float*)nullptr, 0, (int64_t)0, (int64_t*)nullptr, 0L, 0L,
+                         (int64_t*)nullptr, (unsigned char*)nullptr, uniforms, kept_floor, seed, (const long long*)nullptr, out, *score);
+    else
+      hipLaunchKernelGGL(sample_tokens_wide_kernel<SparseOut>, dim3(R < 4096 ? R : 4096), dim3(SW_NT), smem, st, logits, ld, R, C, P, top_k,
                        top_p, inv_temperature, (const float*)nullptr, 0, (int64_t)0, (int64_t*)nullptr, 0L, 0L, (int64_t*)nullptr,
                        (unsigned char*)nullptr, uniforms, kept_floor, seed, (const long long*)nullptr, out);
     WMZ_LAUNCH_CHECK(name);
@@ -848,7 +807,16 @@ int wmz_sparse_sample_launch(const char* name, const float* logits, long ld, int
                                                    (int64_t*)nullptr, (unsigned char*)nullptr, seed, (const long long*)nullptr, x, out)
 #define WMZ_SMP_NV(TEMP, TOPP) \
   do { if (C <= 256) WMZ_SMP(4, TEMP, TOPP); else if (C <= 512) WMZ_SMP(8, TEMP, TOPP); else if (C <= 1024) WMZ_SMP(16, TEMP, TOPP); else WMZ_SMP(32, TEMP, TOPP); } while (0)
-  if (temp && topp) WMZ_SMP_NV(true, true); else if (temp) WMZ_SMP_NV(true, false); else if (topp) WMZ_SMP_NV(false, true); else WMZ_SMP_NV(false, false);
+#define WMZ_SMP_S(NV, TEMP, TOPP) hipLaunchKernelGGL((sample_tokens_kernel<NV, TEMP, TOPP, SampleExtras, SparseOut, SparseScore>), dim3(grid), dim3(256), 0, st, \
+                                                     logits, ld, R, C, top_k, (const float*)nullptr, 0, (int64_t)0, (int64_t*)nullptr, 0L, 0L,          \
+                                                     (int64_t*)nullptr, (unsigned char*)nullptr, seed, (const long long*)nullptr, x, out, *score)
+#define WMZ_SMP_S_NV(TEMP, TOPP) \
+  do { if (C <= 256) WMZ_SMP_S(4, TEMP, TOPP); else if (C <= 512) WMZ_SMP_S(8, TEMP, TOPP); else if (C <= 1024) WMZ_SMP_S(16, TEMP, TOPP); else WMZ_SMP_S(32, TEMP, TOPP); } while (0)
+  if (score != nullptr) {
+    if (temp && topp) WMZ_SMP_S_NV(true, true); else if (temp) WMZ_SMP_S_NV(true, false); else if (topp) WMZ_SMP_S_NV(false, true); else WMZ_SMP_S_NV(false, false);
+  } else if (temp && topp) WMZ_SMP_NV(true, true); else if (temp) WMZ_SMP_NV(true, false); else if (topp) WMZ_SMP_NV(false, true); else WMZ_SMP_NV(false, false);
+#undef WMZ_SMP_S_NV
+#undef WMZ_SMP_S
 #undef WMZ_SMP_NV
 #undef WMZ_SMP
   WMZ_LAUNCH_CHECK(name);

@@ -17,9 +17,18 @@
 //     (bitonic, <= 1 024 packed (key, position) pairs);
 //   * indices, gathered tokens (targets) and their corrupted copies are written from the sorted prefix.
 // Deterministic in (seed, stream id, device counter): a hipGraph replay with the counter advanced draws a fresh context.
+//
+// The scored form (wmz_sparse_draw_context_scored; include/wmz.h states the law), a compile-time variant -- one ScScore behind the
+// ScParams --: the sampler's masking ordered by confidence instead of a coin per slot.  Everything up to the sorted prefix is the
+// same code reading the same Philox words; the last phase differs.  Slot i = thread i (n <= 512) gathers its position's score
+// (+ the annealed Gumbel term from the very uniform the coin rule compares with r) and leaves its key and candidate flag in LDS --
+// in the words of `hist`, which is dead behind the scan: the variant adds no LDS --; wave 0 then holds all <= 512 keys in 8
+// registers a lane and runs wmz_select_lowest (wmz_select.h: 32 search steps of 8 ballots, no barrier, no memory access -- the
+// one-wave form of remask_lowest_kernel); two barriers around it, and every slot writes its token.
 #include "wmz_common.h"
 #include "wmz_internal.h"
 #include "wmz_philox.h"
+#include "wmz_select.h"
 
 namespace {
 
@@ -38,9 +47,19 @@ struct ScParams {
   const unsigned char* known; long known_stride;   // optional bytes [B, S * HW]: a non-zero position is given -- gathered as it is
 };
 
-constexpr int SC_BINS = 2048, SC_CAND = 1024;
+struct ScScore {
+  const float* scores; long stride;                 // [B, S * HW] fp32, addressed like z: the score of the token drawn there
+  float noise;
+  float* slot_scores;                               // optional probe [B, n]: the score each slot was ranked by
+};
 
-__global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) {
+constexpr int SC_BINS = 2048, SC_CAND = 1024;
+constexpr int SC_SLOTS = 512;                       // context positions at the most (wmz_sparse_draw_context_supported)
+
+template <typename... Score>
+__global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P, Score... score) {
+  static_assert(sizeof...(Score) <= 1, "one ScScore at the most");
+  constexpr bool SCORED = sizeof...(Score) == 1;
   __shared__ unsigned hist[SC_BINS];
   __shared__ unsigned long long cand[SC_CAND];                 // packed (key << 32 | position inside the window)
   __shared__ unsigned wave_tot[SC_THREADS / 64];
@@ -131,6 +150,56 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) 
   }
   // ---- the n smallest: positions, targets, corrupted tokens (the law and the stream layout of corrupt_kernel, loss.hip)
   const float rb = P.r[b];
+  if constexpr (SCORED) {
+    const ScScore X = (score, ...);
+    static_assert(2 * SC_SLOTS <= SC_BINS && SC_SLOTS % 64 == 0 && SC_SLOTS <= SC_THREADS, "keys and flags of every slot fit the histogram's words");
+    unsigned* skey = hist;                                     // [SC_SLOTS] the slot's key; 0xFFFFFFFF: no candidate / past n
+    unsigned* sflag = hist + SC_SLOTS;                         // [SC_SLOTS] in: candidate; out: masked
+    const float rc = fminf(fmaxf(rb, 0.f), 1.f);
+    const int i = tid;
+    const long at = (long)b * P.n + i;
+    int64_t tok = 0;
+    if (i < SC_SLOTS) { skey[i] = 0xFFFFFFFFu; sflag[i] = 0u; }
+    if (i < P.n) {
+      unsigned wpos = (unsigned)cand[i];
+      if (wpos >= (unsigned)Wn) wpos = 0;                      // (never: a padding entry would mean fewer than n candidates)
+      const long pos = (long)wpos + (long)first * P.HW;
+      tok = P.z[b * P.clip_stride + pos];
+      float sc = X.scores[b * X.stride + pos];
+      if (X.noise > 0.f) {
+        unsigned c[4];
+        philox4((unsigned long long)b * P.n + i, stream, P.seed, c);        // c[2]: the word the coin rule compares with r
+        sc += X.noise * rc * -logf(-logf(philox_unit(c[2])));
+      }
+      sc = sc == sc ? sc : -INFINITY;
+      const bool candidate = P.known == nullptr || P.known[b * P.known_stride + pos] == 0;
+      if (candidate) { skey[i] = sw_key(sc); sflag[i] = 1u; }
+      if (X.slot_scores != nullptr) X.slot_scores[at] = sc;
+      P.indices[at] = pos;
+      P.target[at] = tok;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      constexpr int MAXP = SC_SLOTS / 64;
+      unsigned key[MAXP], cbits = 0, ncand = 0;
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j) {
+        key[j] = skey[j * 64 + lane];
+        const bool c = sflag[j * 64 + lane] != 0u;
+        cbits |= (c ? 1u : 0u) << j;
+        ncand += (unsigned)__popcll(__ballot(c));
+      }
+      const int m = (int)floorf(mul_rn(rc, (float)P.n));
+      const unsigned mm = m <= 0 ? 0u : ((unsigned)m < ncand ? (unsigned)m : ncand);
+      RmTotal<1> total{nullptr, 0};
+      const unsigned taken = wmz_select_lowest<1, MAXP>(key, cbits, MAXP, mm, nullptr, total);
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j) sflag[j * 64 + lane] = (taken >> j) & 1u;
+    }
+    __syncthreads();
+    if (i < P.n) P.tokens[at] = sflag[i] != 0u ? (int64_t)P.C : tok;
+    return;
+  }
   for (int i = tid; i < P.n; i += SC_THREADS) {
     unsigned wpos = (unsigned)cand[i];
     if (wpos >= (unsigned)Wn) wpos = 0;                        // (never: a sort padding entry would mean fewer than n candidates)
@@ -217,11 +286,10 @@ extern "C" int wmz_sparse_draw_context(const int64_t* z, long clip_stride, const
 
 // The same draw for a clip of which some positions are given (include/wmz.h states the law): `known` changes the corrupted copy
 // of a given slot and nothing else.
-extern "C" int wmz_sparse_draw_context_known(const int64_t* z, long clip_stride, const float* r, const float* o, int64_t* indices,
-                                             int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
-                                             unsigned long long seed, unsigned long long stream_id,
-                                             const unsigned long long* counter, void* stream, const unsigned char* known,
-                                             long known_stride) {
+static int sparse_context_launch(const int64_t* z, long clip_stride, const float* r, const float* o, int64_t* indices,
+                                 int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
+                                 unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
+                                 void* stream, const unsigned char* known, long known_stride, const ScScore* score) {
   WMZ_REQUIRE(z && r && indices && tokens && target && B > 0 && C > 0, "wmz_sparse_draw_context: bad arguments");
   WMZ_REQUIRE(p_uniform >= 0.f && p_uniform <= 1.f, "wmz_sparse_draw_context: p_uniform in [0, 1] expected");
   WMZ_REQUIRE(known == nullptr || known_stride >= (long)S * HW, "wmz_sparse_draw_context_known: known_stride below S * HW");
@@ -241,9 +309,38 @@ extern "C" int wmz_sparse_draw_context_known(const int64_t* z, long clip_stride,
   P.stream &= ~(SC_KEY_DOMAIN | SC_WIN_DOMAIN);
   P.counter = counter;
   P.known = known; P.known_stride = known_stride;
-  hipLaunchKernelGGL(sparse_context_kernel, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P);
+  if (score == nullptr)
+    hipLaunchKernelGGL(sparse_context_kernel<>, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P);
+  else
+    hipLaunchKernelGGL(sparse_context_kernel<ScScore>, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P, *score);
   WMZ_LAUNCH_CHECK("wmz_sparse_draw_context");
   return WMZ_OK;
+}
+
+extern "C" int wmz_sparse_draw_context_known(const int64_t* z, long clip_stride, const float* r, const float* o, int64_t* indices,
+                                             int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
+                                             unsigned long long seed, unsigned long long stream_id,
+                                             const unsigned long long* counter, void* stream, const unsigned char* known,
+                                             long known_stride) {
+  return sparse_context_launch(z, clip_stride, r, o, indices, tokens, target, B, S, HW, n, C, p_uniform, seed, stream_id, counter, stream,
+                               known, known_stride, nullptr);
+}
+
+// The sampler's masking ordered by confidence (include/wmz.h states the law): the scored variant of the kernel, same launch shape.
+extern "C" int wmz_sparse_draw_context_scored(const int64_t* z, long clip_stride, const float* r, const float* o, int64_t* indices,
+                                              int64_t* tokens, int64_t* target, int B, int S, int HW, int n, int C, float p_uniform,
+                                              unsigned long long seed, unsigned long long stream_id,
+                                              const unsigned long long* counter, void* stream, const unsigned char* known,
+                                              long known_stride, const float* scores, long scores_stride, float noise,
+                                              float* slot_scores) {
+  WMZ_REQUIRE(scores != nullptr, "wmz_sparse_draw_context_scored: scores expected");
+  WMZ_REQUIRE(p_uniform == 0.f, "wmz_sparse_draw_context_scored: the ordered rule masks only: p_uniform must be 0 (got %g)", (double)p_uniform);
+  WMZ_REQUIRE(noise >= 0.f && noise < INFINITY, "wmz_sparse_draw_context_scored: noise must be non-negative and finite (got %g)",
+              (double)noise);
+  WMZ_REQUIRE(scores_stride >= (long)S * HW, "wmz_sparse_draw_context_scored: scores_stride below S * HW");
+  const ScScore score = {scores, scores_stride, noise, slot_scores};
+  return sparse_context_launch(z, clip_stride, r, o, indices, tokens, target, B, S, HW, n, C, p_uniform, seed, stream_id, counter, stream,
+                               known, known_stride, &score);
 }
 
 // One multinomial draw per row of fp32 logits [R, C] (row stride ld) from softmax(logits) -- sparse_diffusion.py:190-194 -- and,
@@ -259,11 +356,11 @@ extern "C" int wmz_categorical_scatter(const float* logits, long ld, long R, int
 // The same with a temperature, top-k, a nucleus and given positions (include/wmz.h states the law).  Neutral filters and no probe:
 // categorical_scatter_kernel, the three passes over the global row at any C and any alignment -- the draws of the entry point
 // above.  Else the two row bodies of wmz_sample_tokens_filtered_dev (loss.hip) with this sampler's uniform and destination.
-extern "C" int wmz_categorical_scatter_filtered(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
-                                                const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip,
-                                                int64_t* samples, const unsigned char* known, long known_stride,
-                                                const float* uniforms, float* kept_floor, unsigned long long seed,
-                                                unsigned long long stream_id, const unsigned long long* counter, void* stream) {
+static int categorical_scatter_launch(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
+                                      const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip, int64_t* samples,
+                                      const unsigned char* known, long known_stride, const float* uniforms, float* kept_floor,
+                                      unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
+                                      void* stream, const WmzSparseScore* score) {
   WMZ_REQUIRE(logits && R > 0 && C > 0 && ld >= C, "wmz_categorical_scatter: bad arguments");
   WMZ_REQUIRE(z == nullptr || (indices != nullptr && rows_per_clip > 0), "wmz_categorical_scatter: the scatter needs indices and rows_per_clip");
   WMZ_REQUIRE(z != nullptr || samples != nullptr, "wmz_categorical_scatter: nothing to write");
@@ -273,7 +370,8 @@ extern "C" int wmz_categorical_scatter_filtered(const float* logits, long ld, lo
   const unsigned long long sid = (counter != nullptr ? (stream_id & ~((1ull << 40) - 1)) : stream_id) & ~(SC_KEY_DOMAIN | SC_WIN_DOMAIN);
   const WmzSparseOut out = {indices, z, clip_stride, rows_per_clip, samples, z != nullptr ? known : nullptr, known_stride,
                             sid | (SC_KEY_DOMAIN | SC_WIN_DOMAIN), counter};
-  const bool neutral = !(top_k > 0 && top_k < C) && !(top_p < 1.f) && inv_temperature == 1.f && uniforms == nullptr && kept_floor == nullptr;
+  const bool neutral = !(top_k > 0 && top_k < C) && !(top_p < 1.f) && inv_temperature == 1.f && uniforms == nullptr && kept_floor == nullptr &&
+                       score == nullptr;
   if (neutral) {
     const int grid = (int)((R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048);
     hipLaunchKernelGGL(categorical_scatter_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, R, C, out, seed);
@@ -287,5 +385,31 @@ extern "C" int wmz_categorical_scatter_filtered(const float* logits, long ld, lo
   WMZ_REQUIRE(ld % 4 == 0 && (((uintptr_t)logits) & 15) == 0, "wmz_categorical_scatter_filtered: logits rows must be 16-byte aligned");
   WMZ_REQUIRE(R <= 0x7fffffffL, "wmz_categorical_scatter_filtered: more than 2^31 - 1 rows");
   return wmz_sparse_sample_launch("wmz_categorical_scatter_filtered", logits, ld, (int)R, C, top_k, top_p, inv_temperature, uniforms,
-                                  kept_floor, seed, out, (hipStream_t)stream);
+                                  kept_floor, seed, out, (hipStream_t)stream, score);
+}
+
+extern "C" int wmz_categorical_scatter_filtered(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
+                                                const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip,
+                                                int64_t* samples, const unsigned char* known, long known_stride,
+                                                const float* uniforms, float* kept_floor, unsigned long long seed,
+                                                unsigned long long stream_id, const unsigned long long* counter, void* stream) {
+  return categorical_scatter_launch(logits, ld, R, C, top_k, top_p, inv_temperature, indices, z, clip_stride, rows_per_clip, samples, known,
+                                    known_stride, uniforms, kept_floor, seed, stream_id, counter, stream, nullptr);
+}
+
+// The same draw with the score of every draw written beside its token (include/wmz.h states the law): `scores` counts as a probe,
+// so the row-read-once kernels run whatever the filters are.
+extern "C" int wmz_categorical_scatter_scored(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
+                                              const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip,
+                                              int64_t* samples, const unsigned char* known, long known_stride,
+                                              const float* uniforms, float* kept_floor, unsigned long long seed,
+                                              unsigned long long stream_id, const unsigned long long* counter, void* stream,
+                                              float* scores, long scores_stride) {
+  if (scores == nullptr)
+    return wmz_categorical_scatter_filtered(logits, ld, R, C, top_k, top_p, inv_temperature, indices, z, clip_stride, rows_per_clip, samples,
+                                            known, known_stride, uniforms, kept_floor, seed, stream_id, counter, stream);
+  WMZ_REQUIRE(z != nullptr, "wmz_categorical_scatter_scored: a score is written where a token is: z expected");
+  const WmzSparseScore score = {scores, scores_stride};
+  return categorical_scatter_launch(logits, ld, R, C, top_k, top_p, inv_temperature, indices, z, clip_stride, rows_per_clip, samples, known,
+                                    known_stride, uniforms, kept_floor, seed, stream_id, counter, stream, &score);
 }

@@ -31,11 +31,28 @@ __device__ __forceinline__ void wmz_sparse_write(const WmzSparseOut& o, long row
     if (o.known == nullptr || o.known[clip * o.known_stride + pos] == 0) o.z[clip * o.clip_stride + pos] = draw;
   }
 }
-// loss.hip: the filtered draw (the row bodies of wmz_sample_tokens_filtered_dev) with a WmzSparseOut as destination; the checks are
-// the caller's (wmz_categorical_scatter_filtered)
+// The scored form's second destination (wmz_categorical_scatter_scored): scores [clips, stride] fp32, addressed like z -- the score of
+// a draw is written exactly where its token is written, and nowhere else.
+struct WmzSparseScore {
+  float* scores;
+  long stride;
+};
+__device__ __forceinline__ void wmz_sparse_write_scored(const WmzSparseOut& o, const WmzSparseScore& s, long row, int draw, float score) {
+  if (o.samples != nullptr) o.samples[row] = draw;
+  if (o.z != nullptr) {
+    const long clip = row / o.rows_per_clip;
+    const int64_t pos = o.indices[row];
+    if (o.known == nullptr || o.known[clip * o.known_stride + pos] == 0) {
+      o.z[clip * o.clip_stride + pos] = draw;
+      s.scores[clip * s.stride + pos] = score;
+    }
+  }
+}
+// loss.hip: the filtered draw (the row bodies of wmz_sample_tokens_filtered_dev) with a WmzSparseOut as destination -- and, with
+// `score`, the score of each draw beside it --; the checks are the caller's (wmz_categorical_scatter_filtered / _scored)
 int wmz_sparse_sample_launch(const char* name, const float* logits, long ld, int R, int C, int top_k, float top_p, float inv_temperature,
                              const float* uniforms, float* kept_floor, unsigned long long seed, const WmzSparseOut& out,
-                             hipStream_t stream);
+                             hipStream_t stream, const WmzSparseScore* score = nullptr);
 // conv_wgrad.hip: direct 3x3 weight gradient (bf16, stride 1, pad 1, Cout = 128, Cin in {64, 128}, H % 8 == 0, W % 16 == 0)
 int wmz_convw_supported(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dtype);
 long wmz_convw_workspace_floats(int B, int H, int W, int Cin, int Cout);

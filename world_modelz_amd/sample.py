@@ -80,18 +80,28 @@ def score_keys(scores):
     return torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b + 0x80000000)
 
 
-def lowest_scores_mask(scores, alpha, candidates=None):
+def context_remask_count(r, n):
+    """Config 5's count: m = floor(clamp(r, 0, 1) * n) per clip as wmz_sparse_draw_context_scored computes it -- r [B] and n in fp32,
+    one multiply.  -> int64 [B]."""
+    rc = torch.as_tensor(r, dtype=torch.float32).reshape(-1).clamp(0, 1)
+    return torch.floor(rc * torch.tensor(float(n), dtype=torch.float32, device=rc.device)).to(torch.int64)
+
+
+def lowest_scores_mask(scores, alpha, candidates=None, count=None):
     """Which positions go back to the mask token: per clip (row of scores [B, HW]) the min(m, #candidates) candidates with the lowest
-    scores, m = remask_count(alpha, HW); candidates: bool [B, HW] (default: all).  Order by score_keys, ties to the lower index.
-    -> bool [B, HW]."""
+    scores, m = remask_count(alpha, HW) -- or, with count (an int, or int64 [B]: context_remask_count, the sparse sampler's, whose
+    m comes from r), that count, alpha unread; candidates: bool [B, HW] (default: all).  Order by score_keys, ties to the lower
+    index.  -> bool [B, HW]."""
     B, HW = scores.shape
-    m = remask_count(alpha, HW)
+    m = remask_count(alpha, HW) if count is None else count
+    if torch.is_tensor(m):
+        m = m.to(scores.device).reshape(B, 1)
     cand = torch.ones(B, HW, dtype=torch.bool, device=scores.device) if candidates is None else candidates.to(torch.bool)
     idx = torch.arange(HW, device=scores.device)
     # one unique sort key per position: (non-candidates last, key, index)
     order = (torch.where(cand, score_keys(scores), torch.full((), 1 << 32, dtype=torch.int64, device=scores.device)) * HW + idx).argsort(dim=-1)
     rank = torch.empty_like(order).scatter_(-1, order, idx.expand(B, HW))
-    return cand & (rank < cand.sum(-1, keepdim=True).clamp(max=m))
+    return cand & (rank < torch.minimum(cand.sum(-1, keepdim=True), torch.as_tensor(m, device=scores.device)))
 
 
 REMASK_MODES = ('random', 'confidence')
@@ -115,7 +125,8 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     (confidence_scores + lowest_scores_mask above; with consistent_masking among the positions masked before), the rule of
     masked-token decoders (MaskGIT).  remask_noise >= 0 (finite) scales the Gumbel noise added to the scores, annealed by
     (1 - alpha); its uniform is u_mask[f, i] when injected.  ValueError for anything else.  (Config 5's sampler,
-    sparse_diffusion.sample_clips, takes temperature, sample_topk and sample_topp too; it has no re-mask step to order.)"""
+    sparse_diffusion.sample_clips, takes all of these too: it masks when it gathers a context, so its 'confidence' orders that
+    masking by a score kept per clip position between sub-steps.)"""
     assert batch_z.is_cuda
     if remask not in REMASK_MODES:
         raise ValueError(f'remask must be one of {REMASK_MODES} (got {remask!r})')

@@ -84,7 +84,7 @@ class VqSparseDiffusionModel(nn.Module):
 
 # ------------------------------------------------------------------------------------------------ the sampler (reference :99-202)
 def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counter=None, *, top_k=-1, top_p=1.0, temperature=1.0,
-                        known=None, uniforms=None, kept_floor=None, samples=None):
+                        known=None, uniforms=None, kept_floor=None, samples=None, scores=None):
     """One multinomial draw per row from softmax(logits) (reference :190-194), written into the clips at the rows' positions
     (:197 `full_z_flat.scatter_`): logits fp32 [B, n, C] (rows at one stride, classes contiguous), indices int64 [B, n], z_flat
     int64 [B, G] (in place).  The draw's Philox stream: (seed, rank, call_id) -- or, with counter (device int64 [1]), the call
@@ -95,7 +95,11 @@ def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counte
     logit per row) and samples int64 [B * n] (every row's draw, known or not) as there.  The route: neutral filters and no known --
     wmz_categorical_scatter, as ever; else wmz_categorical_scatter_filtered, rows off the 16-byte granule staged through a padded
     buffer; a filter acting on more classes than ops.sample_max_classes() is applied with torch ops (sample.top_k_logits /
-    top_p_logits on the scaled logits) in front of the neutral form of that entry point."""
+    top_p_logits on the scaled logits) in front of the neutral form of that entry point.
+    scores (fp32 [B, G], in place; sample_clips' remask='confidence'): the log-probability of every draw under the softmax of the
+    scaled UNFILTERED logits, written where its token is written and nowhere else (wmz_categorical_scatter_scored, which counts it
+    as a probe: the row-read-once kernels whatever the filters are); above ops.sample_max_classes(): sample.drawn_log_prob at the
+    draws, scattered with torch ops where the position is not known."""
     from . import _lib as L
     B, n, C = logits.shape
     assert logits.dtype == torch.float32 and logits.stride(2) == 1 and indices.is_contiguous() and z_flat.stride(1) == 1
@@ -103,12 +107,12 @@ def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counte
     assert ld >= C and (B == 1 or logits.stride(0) == n * ld)
     sid = (int(rank) << 40) | (0 if counter is not None else int(call_id) & ((1 << 40) - 1))
     tail = (int(seed) & 0xFFFFFFFFFFFFFFFF, sid, L.ptr(counter), L.stream())
-    dest = (L.ptr(indices), L.ptr(z_flat), z_flat.stride(0), n, L.ptr(samples))
     assert samples is None or (samples.dtype == torch.int64 and samples.is_contiguous() and samples.numel() == R)
+    assert scores is None or (scores.dtype == torch.float32 and scores.shape == z_flat.shape and scores.stride(1) == 1)
     probes = uniforms is not None or kept_floor is not None
-    acting = 0 < top_k < C or top_p < 1.0 or temperature != 1.0 or probes
+    acting = 0 < top_k < C or top_p < 1.0 or temperature != 1.0 or probes or scores is not None
     if not acting and known is None:
-        L.call('wmz_categorical_scatter', L.ptr(logits), ld, R, C, *dest, *tail)
+        L.call('wmz_categorical_scatter', L.ptr(logits), ld, R, C, L.ptr(indices), L.ptr(z_flat), z_flat.stride(0), n, L.ptr(samples), *tail)
         return
     assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.numel() == R)
     assert kept_floor is None or (kept_floor.dtype == torch.float32 and kept_floor.is_contiguous() and kept_floor.numel() == R)
@@ -116,6 +120,7 @@ def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counte
         assert known.dtype in (torch.bool, torch.uint8) and known.shape == z_flat.shape and known.stride(1) == 1
     given = (L.ptr(known), known.stride(0) if known is not None else 0)
     k, p, inv_t = int(top_k), float(top_p), 1.0 / float(temperature)
+    unfiltered = None                                   # the scaled rows whose scores torch ops compute (codebooks above the kernels' limit)
     if acting:
         from . import ops
         from .sample import top_k_logits, top_p_logits
@@ -123,6 +128,9 @@ def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counte
             if probes:
                 raise ValueError(f'uniforms / kept_floor are built for <= {ops.sample_max_classes()} classes (got {C})')
             rows = logits.reshape(R, C) * torch.tensor(inv_t, dtype=torch.float32, device=logits.device)
+            if scores is not None:
+                unfiltered = rows
+                samples = torch.empty(R, dtype=torch.int64, device=logits.device) if samples is None else samples
             if 0 < k < C:
                 rows = top_k_logits(rows, k)
             logits, ld, k, p, inv_t = top_p_logits(rows, p).contiguous(), C, -1, 1.0, 1.0
@@ -131,8 +139,20 @@ def categorical_scatter(logits, indices, z_flat, seed, call_id=0, rank=0, counte
             staged = torch.empty(R, ld, dtype=torch.float32, device=logits.device)
             staged[:, :C].copy_(logits.reshape(R, C))
             logits = staged
-    L.call('wmz_categorical_scatter_filtered', L.ptr(logits), ld, R, C, k, p, inv_t, *dest, *given, L.ptr(uniforms), L.ptr(kept_floor),
-           *tail)
+    dest = (L.ptr(indices), L.ptr(z_flat), z_flat.stride(0), n, L.ptr(samples))
+    if scores is None or unfiltered is not None:
+        L.call('wmz_categorical_scatter_filtered', L.ptr(logits), ld, R, C, k, p, inv_t, *dest, *given, L.ptr(uniforms),
+               L.ptr(kept_floor), *tail)
+    else:
+        L.call('wmz_categorical_scatter_scored', L.ptr(logits), ld, R, C, k, p, inv_t, *dest, *given, L.ptr(uniforms),
+               L.ptr(kept_floor), *tail, L.ptr(scores), scores.stride(0))
+    if unfiltered is not None:
+        from .sample import drawn_log_prob
+        s = drawn_log_prob(unfiltered, samples).view(B, n)
+        s = torch.where(s != s, torch.full_like(s, -float('inf')), s)
+        if known is not None:                           # (a known position keeps its score as it keeps its token)
+            s = torch.where(torch.gather(known, 1, indices) != 0, torch.gather(scores, 1, indices), s)
+        scores.scatter_(1, indices, s)
 
 
 def _check_sampler_arguments(temperature, sample_topp, prompt, shape, num_embeddings, device):
@@ -155,7 +175,8 @@ def _check_sampler_arguments(temperature, sample_topp, prompt, shape, num_embedd
 
 @torch.no_grad()
 def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', num_context=512, num_eval_iterations=100,
-                 generator=None, seed=None, use_graph=True, *, temperature=1.0, sample_topk=-1, sample_topp=1.0, prompt=None):
+                 generator=None, seed=None, use_graph=True, *, temperature=1.0, sample_topk=-1, sample_topp=1.0, prompt=None,
+                 remask='random', remask_noise=0.0):
     """The token side of the reference's evaluate_model (:139-202): clips [batch_size, S, H, W] that start fully masked and are
     re-drawn num_eval_iterations times -- per iteration G // num_context + 1 contexts, each gathered from the clip, masked with
     probability 1 - i / (iterations - 1), denoised by the model, sampled from softmax(logits) and scattered back.  'neighbors' (the
@@ -170,9 +191,23 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
     -- the clip starts as the prompt instead of all masks; tokens in [0, num_embeddings) are GIVEN: fed to the model as they are,
     never masked, never redrawn; num_embeddings (the mask token) marks what is generated.  ValueError for another shape, device or
     value.  Every route takes them (the fused launches become wmz_sparse_draw_context_known / wmz_categorical_scatter_filtered);
-    the defaults run the launches they always ran."""
+    the defaults run the launches they always ran.
+    remask: 'random' -- the reference's law: every context slot is hidden from the model with probability 1 - frac, a coin per slot,
+    whatever remask_noise is -- or 'confidence': per context exactly the floor((1 - frac) * num_context) slots the model was least
+    sure of are hidden (MaskGIT's rule, as in sample_frames).  The sparse sampler masks when it gathers, so the order lives in a
+    score per clip position kept between sub-steps: fp32 [batch_size, G], -inf to start with (a position never drawn is hidden
+    first), the log-probability of the position's last draw under the unfiltered tempered softmax afterwards, written by the draw
+    beside the token (wmz_categorical_scatter_scored) and read by the next gathers (wmz_sparse_draw_context_scored; include/wmz.h
+    states the law, sample.lowest_scores_mask / context_remask_count are its torch form, which the torch-drawn and 'uniform' routes
+    apply).  Given positions are never hidden.  remask_noise >= 0 (finite) scales Gumbel noise added to the slot scores, annealed by
+    1 - frac.  The captured sub-step stays one hipGraph launch: draw, forward, scored scatter.  ValueError for anything else."""
     if sampling_type not in ('uniform', 'neighbors'):
         raise ValueError('Specified sampling_type not supported')                 # reference :182
+    from .sample import REMASK_MODES, context_remask_count, gumbel_from_uniform, lowest_scores_mask
+    if remask not in REMASK_MODES:
+        raise ValueError(f'remask must be one of {REMASK_MODES} (got {remask!r})')
+    if not 0 <= remask_noise < float('inf'):
+        raise ValueError(f'remask_noise must be non-negative and finite (got {remask_noise})')
     if num_eval_iterations < 2:
         raise ValueError('num_eval_iterations must be at least 2 (the schedule divides by iterations - 1)')
     S, H, W = (int(v) for v in model.shape)
@@ -190,6 +225,11 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
         known = (prompt != int(num_embeddings)).view(batch_size, -1).to(torch.uint8)        # static: what is given stays given
     flat = full_z.view(batch_size, -1)
     draw = dict(top_k=int(sample_topk), top_p=float(sample_topp), temperature=float(temperature), known=known)
+    scores, ordered = None, {}
+    if remask == 'confidence':
+        scores = torch.full((batch_size, G), -float('inf'), dtype=torch.float32, device=dev)
+        draw['scores'] = scores
+        ordered = dict(scores=scores, noise=float(remask_noise))
     if seed is None:
         seed = generator.initial_seed() if generator is not None else torch.initial_seed()
     fused = sampling_type == 'neighbors' and bool(L.lib().wmz_sparse_draw_context_supported(S, H * W, n))
@@ -198,11 +238,21 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
     model.eval()
     graph = None
 
-    def mask_unknown(tokens, indices, frac):
-        """The torch-drawn routes' masking (:185-187), given positions left as they are."""
-        hide = torch.rand(tokens.shape, device=dev) > frac
-        if known is not None:
-            hide &= torch.gather(known, 1, indices) == 0
+    def mask_unknown(tokens, indices, frac, r):
+        """The torch-drawn routes' masking (:185-187), given positions left as they are; remask='confidence': the torch form of
+        wmz_sparse_draw_context_scored's law on the gathered scores."""
+        unknown = torch.gather(known, 1, indices) == 0 if known is not None else None
+        if scores is None:
+            hide = torch.rand(tokens.shape, device=dev) > frac
+            if unknown is not None:
+                hide &= unknown
+        else:
+            s = torch.gather(scores, 1, indices)
+            if remask_noise > 0:
+                amp = torch.tensor(remask_noise, dtype=torch.float32, device=dev) * r.clamp(0, 1)
+                s = s + amp.unsqueeze(1) * gumbel_from_uniform(torch.rand(tokens.shape, device=dev))
+                s = torch.where(s != s, torch.full_like(s, -float('inf')), s)
+            hide = lowest_scores_mask(s, None, unknown, count=context_remask_count(r, tokens.shape[1]))
         return torch.where(hide, torch.full_like(tokens, num_embeddings), tokens)
     if fused and use_graph:
         # one captured sub-step on static inputs: the noise level / window width r, the window placement o, the call counter
@@ -213,7 +263,7 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
         def substep():
             ctr.add_(1)
             indices, tokens, _ = draw_sparse_context(full_z, r_s, n, (S, H, W), num_embeddings, seed=seed, rank=0, counter=ctr, o=o_s,
-                                                     p_uniform=0.0, known=known)
+                                                     p_uniform=0.0, known=known, **ordered)
             logits = model(tokens, indices)
             categorical_scatter(logits.float().contiguous(), indices, flat, seed, counter=ctr, **draw)
         from . import config as _cfg
@@ -227,11 +277,13 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
         from .graph import capture_mode
         with torch.cuda.graph(graph, capture_error_mode=capture_mode()):
             substep()
-        # the warm-up wrote tokens: start from all masks (or the prompt), call number 0 (+ bit 38)
+        # the warm-up wrote tokens (and their scores): start from all masks (or the prompt), call number 0 (+ bit 38)
         if prompt is None:
             full_z.fill_(int(num_embeddings))
         else:
             full_z.copy_(prompt)
+        if scores is not None:
+            scores.fill_(-float('inf'))
         ctr.fill_(1 << 38)
     try:
         for i in range(num_eval_iterations):
@@ -255,13 +307,13 @@ def sample_clips(model, batch_size, num_embeddings, sampling_type='neighbors', n
                     if idx.numel() == 0:
                         continue
                     indices = idx.unsqueeze(0).expand(batch_size, -1).contiguous()
-                    tokens = mask_unknown(torch.gather(flat, 1, indices), indices, frac)
+                    tokens = mask_unknown(torch.gather(flat, 1, indices), indices, frac, r)
                 elif fused:
                     indices, tokens, _ = draw_sparse_context(full_z, r, n, (S, H, W), num_embeddings, seed=seed, rank=0, o=o_rows[k],
-                                                             p_uniform=0.0, call_id=call, known=known)
+                                                             p_uniform=0.0, call_id=call, known=known, **ordered)
                 else:
                     indices = sample_time_dependent(batch_size, n, S, H, W, r, dev, o=o_rows[k])
-                    tokens = mask_unknown(torch.gather(flat, 1, indices), indices, frac)
+                    tokens = mask_unknown(torch.gather(flat, 1, indices), indices, frac, r)
                 logits = model(tokens, indices)                                                         # [B, n, C] fp32
                 categorical_scatter(logits.float().contiguous(), indices, flat, seed, call, **draw)
     finally:
@@ -282,10 +334,11 @@ def decode(decoder_model, batch, decode_N=16):
 
 @torch.no_grad()
 def evaluate_model(device, batch_size, model, decoder_model, shape, sampling_type, num_context=512, num_eval_iterations=100, *,
-                   temperature=1.0, sample_topk=-1, sample_topp=1.0, prompt=None):
+                   temperature=1.0, sample_topk=-1, sample_topp=1.0, prompt=None, remask='random', remask_noise=0.0):
     """The reference's evaluate_model (:139-202), same positional signature: sampled clips decoded to frames.  temperature,
-    sample_topk, sample_topp and prompt (keyword-only) are sample_clips'."""
+    sample_topk, sample_topp, prompt, remask and remask_noise (keyword-only) are sample_clips'."""
     assert tuple(int(v) for v in shape) == tuple(int(v) for v in model.shape)
     z = sample_clips(model, batch_size, decoder_model.vq.num_embeddings, sampling_type, num_context, num_eval_iterations,
-                     temperature=temperature, sample_topk=sample_topk, sample_topp=sample_topp, prompt=prompt)
+                     temperature=temperature, sample_topk=sample_topk, sample_topp=sample_topp, prompt=prompt, remask=remask,
+                     remask_noise=remask_noise)
     return decode(decoder_model, z)

@@ -84,7 +84,7 @@ def corrupt_tokens(tokens, r, num_embeddings, generator=None, seed=None, rank=No
 
 
 def draw_sparse_context(z, r, num_context, shape, num_embeddings, generator=None, seed=None, rank=None, counter=None, o=None,
-                        p_uniform=0.1, call_id=None, known=None):
+                        p_uniform=0.1, call_id=None, known=None, scores=None, noise=0.0, slot_scores=None):
     """Config 5's step prologue by ONE launch (wmz_sparse_draw_context: minecraft/sparse_diffusion.py:44-72 sample_time_dependent,
     :437 gather, :440-449 perturbation & masking): z [B, S, H, W] token clips, r [B] noise levels -> (indices, corrupted tokens,
     target), each [B, num_context].  o [B]: the window placements (else drawn in the kernel).  p_uniform: the redraw probability
@@ -92,7 +92,11 @@ def draw_sparse_context(z, r, num_context, shape, num_embeddings, generator=None
     (seed, rank, per-call counter -- on the device when `counter` is given: hipGraph replays).
     known (bool / uint8 [B, S * H * W], the prompted sampler's; training passes none): a context slot at a given position keeps
     its token -- neither masked nor redrawn -- and everything else, the random streams included, is as without it
-    (wmz_sparse_draw_context_known)."""
+    (wmz_sparse_draw_context_known).
+    scores (fp32 [B, S * H * W], the sampler's remask='confidence'; needs p_uniform = 0): the masking is ordered instead of drawn --
+    per clip the floor(r * num_context) unknown slots with the lowest scores[position] (+ noise * r * Gumbel, noise >= 0) are hidden
+    (wmz_sparse_draw_context_scored; include/wmz.h states the law); slot_scores (fp32 [B, num_context], a probe) receives the score
+    every slot was ranked by.  Positions, order and target are as without it."""
     global _corrupt_calls
     assert z.is_cuda and z.dtype == torch.int64
     B = z.shape[0]
@@ -117,10 +121,17 @@ def draw_sparse_context(z, r, num_context, shape, num_embeddings, generator=None
         stream_id = (rank << 40) | (_corrupt_calls & ((1 << 40) - 1))
     args = (L.ptr(zf), zf.stride(0), L.ptr(r), L.ptr(o), L.ptr(indices), L.ptr(tokens), L.ptr(target), B, S, H * W, n,
             int(num_embeddings), float(p_uniform), int(seed) & 0xFFFFFFFFFFFFFFFF, stream_id, L.ptr(counter), L.stream())
-    if known is None:
+    if known is not None:
+        assert known.dtype in (torch.bool, torch.uint8) and known.shape == zf.shape and known.stride(1) == 1 and known.device == dev
+    if scores is not None:
+        assert scores.dtype == torch.float32 and scores.shape == zf.shape and scores.stride(1) == 1 and scores.device == dev
+        assert slot_scores is None or (slot_scores.dtype == torch.float32 and slot_scores.is_contiguous()
+                                       and slot_scores.shape == indices.shape and slot_scores.device == dev)
+        L.call('wmz_sparse_draw_context_scored', *args, L.ptr(known), known.stride(0) if known is not None else 0, L.ptr(scores),
+               scores.stride(0), float(noise), L.ptr(slot_scores))
+    elif known is None:
         L.call('wmz_sparse_draw_context', *args)
     else:
-        assert known.dtype in (torch.bool, torch.uint8) and known.shape == zf.shape and known.stride(1) == 1 and known.device == dev
         L.call('wmz_sparse_draw_context_known', *args, L.ptr(known), known.stride(0))
     return indices, tokens, target
 
