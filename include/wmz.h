@@ -168,7 +168,9 @@ int wmz_layernorm_bwd(const void* x, long ldx, const void* dyhat, long lddy, con
 int wmz_embed_pos3d_fwd(const int64_t* z, const float* emb, const float* pos_s, const float* pos_h,
                         const float* pos_w, void* x, int B, int S, int H, int W, int D, int num_classes,
                         int dtype, void* stream);
-/* its backward: scatter-add dx into the four fp32 tables (accumulated; zero them first). */
+/* its backward: scatter-add dx into the four fp32 tables (accumulated; zero them first).  H + W <= 64.  W == 16 takes a kernel
+ * that keeps the column sums in registers when D % 64 is 0 or at least 16 (every wave that works has lanes 0..15 active: they
+ * carry the plane row's token ids); any other width, and any other W, takes the general kernel.  Same sums either way. */
 int wmz_embed_pos3d_bwd(const int64_t* z, const void* dx, float* demb, float* dpos_s, float* dpos_h, float* dpos_w,
                         int B, int S, int H, int W, int D, int num_classes, int dtype, void* stream);
 /* The same gradients WITHOUT a float atomic per element (W = 16, D = 256, bf16, <= 12 288 classes; WMZ_ERR_UNSUPPORTED
@@ -831,12 +833,16 @@ int wmz_remask_lowest_dev(const float* scores, int R, long rows_per_block, const
                           int64_t* out_tokens, long block_stride, unsigned char* last_mask, const long long* counter,
                           void* stream);
 /* CrossEntropyLoss(reduction='none') over fp32 logits [R, C] (row stride ld): loss[R], lse[R]; and its gradient
- * dlogits[r,c] = (softmax - one_hot) * grad_rows[r], written in `dtype` (the GEMM operand type of the backward). */
+ * dlogits[r,c] = (softmax - one_hot) * grad_rows[r], written in `dtype` (the GEMM operand type of the backward), contiguous [R, C].
+ * Only the C classes of a row are read (ld >= C, any alignment).  A target outside [0, C-1] is not an error: the loss is taken at
+ * the target clamped to [0, C-1], and the gradient has NO one-hot term (dlogits = softmax * grad_rows on that row). */
 int wmz_ce_fwd(const float* logits, long ld, const int64_t* target, float* loss, float* lse, long R, int C, void* stream);
 int wmz_ce_bwd(const float* logits, long ld, const int64_t* target, const float* lse, const float* grad_rows, void* dlogits,
                long R, int C, int dtype, void* stream);
-/* Both in one pass over the logits (a wave keeps its row in registers; C <= 8192, else the two launches above): what the
- * training step's fused linear + cross-entropy calls. */
+/* Both in one pass over the logits (a wave keeps its row in registers): what the training step's fused linear + cross-entropy
+ * calls.  The one-pass kernel reads rows 16 bytes at a time and stores four gradients at a time, so it is taken when C <= 8192,
+ * ld % 4 == 0, logits is 16-byte aligned and dlogits is aligned to four of its elements (16 bytes fp32, 8 bytes bf16); anything
+ * else runs the two launches above, with their results.  Out-of-range targets: as above. */
 int wmz_ce_fwd_bwd(const float* logits, long ld, const int64_t* target, float* loss, float* lse, const float* grad_rows,
                    void* dlogits, long R, int C, int dtype, void* stream);
 
@@ -844,7 +850,11 @@ int wmz_ce_fwd_bwd(const float* logits, long ld, const int64_t* target, float* l
  * grad_norm (main.py:188-193): out[0] += scale^2 * sum g^2 (caller zeroes out[0]; no host sync). */
 int wmz_grad_sqnorm(const float* g, long n, float scale, float* out, void* stream);
 /* torch.optim.AdamW step as configured at main.py:433 (decoupled weight decay, amsgrad off), gradients read as
- * grad_scale * g (1/world after a SUM all-reduce); `step` is the 1-based step count for the bias corrections. */
+ * grad_scale * g (1/world after a SUM all-reduce); `step` is the 1-based step count for the bias corrections.  Per element, in
+ * fp32, with bc1 = 1 - beta1^step and sbc2 = sqrt(1 - beta2^step) computed in double and rounded once:
+ *   gi = grad_scale g;  p *= 1 - lr wd;  m = beta1 m + (1 - beta1) gi;  v = beta2 v + (1 - beta2) gi^2;
+ *   p -= (lr / bc1) * (m / (sqrt(v) / sbc2 + eps)).
+ * p, g, m, v: 16-byte aligned, any n > 0. */
 int wmz_adamw_step(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, long step, double grad_scale, void* stream);
 /* The same with the per-step scalars in device memory, hyper = [lr, 1 - beta1^t, sqrt(1 - beta2^t)] (fp32): a captured

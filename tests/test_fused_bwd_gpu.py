@@ -325,3 +325,8 @@ def test_embed_backward_sorted_gather_vs_torch(shape, classes, skew):
     for name, a, b in zip(('emb', 'pos_s', 'pos_h', 'pos_w'), tabs, ref):
         err = float((a.double() - b).abs().max() / (b.abs().max() + 1e-30))
         assert err < 2e-6, (name, err)
+    # ... and per element, each within (count + c) u sum |terms| of the fp64 sums (tests/tail_bounds.py)
+    import tail_bounds as tb
+    bounds = tb.embed_bwd_ref(zc.cpu(), *tb.pos3d_indices(B, S, H, W), dx.cpu().reshape(-1, 256), [t.cpu() for t in tabs0], calls=2)
+    for name, a, (b, e) in zip(('emb', 'pos_s', 'pos_h', 'pos_w'), tabs, bounds):
+        tb.check(f'embed_pos3d_bwd_sorted {name}', a.cpu(), b, e)

@@ -390,6 +390,11 @@ def test_fused_cross_entropy_vs_torch(wmz):
                    dt_code, L.stream())
             assert torch.allclose(lo, ref.detach(), rtol=1e-5, atol=1e-5) and torch.allclose(ls, lse, rtol=1e-5, atol=1e-5)
             assert torch.allclose(gg.float(), gref, rtol=rt, atol=1e-4 if dt_t == torch.bfloat16 else 1e-7)
+            # ... and every element within its fp64 bound (tests/tail_bounds.py)
+            import tail_bounds as tb
+            r = tb.ce_ref(logits.detach(), target, w)
+            for name, got, key in (('loss', lo, 'loss'), ('lse', ls, 'lse'), ('dlogits', gg, 'dlogits')):
+                tb.check(f'wmz_ce_fwd_bwd R={R} C={C} {name}', got.cpu(), r[key], r['e_' + key])
 
 
 @pytest.mark.parametrize('shape,depth', [((2, 4, 16, 16), 3), ((1, 3, 8, 8), 2), ((2, 2, 5, 5), 2)])

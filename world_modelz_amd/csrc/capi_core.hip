@@ -130,6 +130,9 @@ __global__ __launch_bounds__(256) void embed_pos3d_bwd_kernel(const int64_t* __r
 // one (the general kernel keeps both in LDS and every token pays two dependent LDS read-modify-writes, ~300 cycles of its
 // ~430), the token ids of a plane row arrive by one load and are handed out by v_readlane, the row's 16 dx loads are
 // independent and in flight together.
+// PRECONDITION (embed_bwd16_takes below): the ids are loaded inside the `d < D` guard and read back from lanes 0..15, so every wave
+// that enters the loop must have those lanes active: D % 64 is 0 or at least 16.  A narrower last wave (D % 64 in 1..15) would
+// read ids from lanes that never executed the load and use them, unclamped, as a row of demb: such widths take the general kernel.
 template <typename T>
 __global__ __launch_bounds__(256) void embed_pos3d_bwd16_kernel(const int64_t* __restrict__ z, const T* __restrict__ dx,
                                                                 float* __restrict__ demb, float* __restrict__ dps,
@@ -169,6 +172,8 @@ __global__ __launch_bounds__(256) void embed_pos3d_bwd16_kernel(const int64_t* _
     for (int w = 0; w < 16; ++w) atomicAdd(dpw + (long)w * D + d, aw[w]);
   }
 }
+// the shapes embed_pos3d_bwd16_kernel is launched for: its precondition above
+static bool embed_bwd16_takes(int W, int D) { return W == 16 && (D % 64 == 0 || D % 64 >= 16); }
 
 // config 5 (minecraft/sparse_diffusion.py:91-111): tokens at ARBITRARY flat grid positions `pos` (one per token):
 // x[t,:] = emb[tok[t]] + ((pos_s[p / (H*W)] + pos_h[(p / W) % H]) + pos_w[p % W])
@@ -332,7 +337,7 @@ extern "C" int wmz_embed_pos3d_bwd(const int64_t* z, const void* dx, float* demb
   const size_t smem = (size_t)(H + W) * 256 * sizeof(float);
   if (smem > 64 * 1024) { wmz_set_error("wmz_embed_pos3d_bwd: H + W = %d > 64 not built", H + W); return WMZ_ERR_UNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
-  if (W == 16) {
+  if (embed_bwd16_takes(W, D)) {
     if (dtype == WMZ_BF16)
       hipLaunchKernelGGL(embed_pos3d_bwd16_kernel<bf16_t>, dim3(B * S), dim3(256), 0, st, z, (const bf16_t*)dx, demb, dpos_s, dpos_h,
                          dpos_w, S, H, D, num_classes);

@@ -665,7 +665,9 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const float* __restrict__
       loss[row] = l - x[tc];
     }
     const float g = grow[row];
-    const int tt = (int)t;                      // (an out-of-range target matches no column, as in ce_bwd_kernel)
+    // (an out-of-range target matches no column, as in ce_bwd_kernel -- decided on the 64-bit value: truncated to int, a target of
+    //  2^32 + k would put a one-hot at column k)
+    const int tt = t >= 0 && t < C ? (int)t : -1;
     T* d = dlogits + row * (long)C;
 #pragma unroll
     for (int q = 0; q < NCH; ++q) {
@@ -919,7 +921,10 @@ extern "C" int wmz_ce_fwd_bwd(const float* logits, long ld, const int64_t* targe
                               void* dlogits, long R, int C, int dtype, void* stream) {
   WMZ_REQUIRE(logits && target && loss && lse && grad_rows && dlogits && R > 0 && C > 0, "wmz_ce_fwd_bwd: bad arguments");
   WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_ce_fwd_bwd: bad dtype %d", dtype);
-  if (C > 8192 || (ld & 3) != 0) {               // rows that do not fit a wave's registers / unaligned rows: the two passes
+  // the one-pass kernel reads 16 bytes of a row at a time and stores four gradients at a time (16 bytes fp32, 8 bytes bf16): rows
+  // that do not fit a wave's registers, a row stride or a base address that leaves a row off those boundaries: the two passes
+  const uintptr_t dmask = dtype == WMZ_F32 ? 15 : 7;
+  if (C > 8192 || (ld & 3) != 0 || ((uintptr_t)logits & 15) != 0 || ((uintptr_t)dlogits & dmask) != 0) {
     const int rc = wmz_ce_fwd(logits, ld, target, loss, lse, R, C, stream);
     return rc != WMZ_OK ? rc : wmz_ce_bwd(logits, ld, target, lse, grad_rows, dlogits, R, C, dtype, stream);
   }
