@@ -29,7 +29,7 @@ extern "C" {
 
 enum { WMZ_F32 = 0, WMZ_BF16 = 1,
        WMZ_F16 = 2 /* IEEE half activations / MFMA operands: the PRECISE fused inference mode (wmz_local3d_attn_fwd* on the
-                      16- / 8-wide-plane fast path and the *_f16 per-token entry points below; the conv encoder / decoder's
+                      16- / 8- / 32-wide-plane fast path and the *_f16 per-token entry points below; the conv encoder / decoder's
                       inference route: the *_f16 conv entry points and the element-wise ones that say so); other entry points
                       refuse it */ };
 enum { WMZ_OK = 0, WMZ_ERR_ARG = 1, WMZ_ERR_HIP = 2, WMZ_ERR_UNSUPPORTED = 3 };
@@ -71,7 +71,7 @@ int wmz_local3d_attn_fwd(const void* q, const void* k, const void* v, void* out,
                          long ldq, long ldk, long ldv, long ldo, int dtype, void* stream);
 
 /* Same contract, always on the general kernel (any W, fp32 / bf16) even where wmz_local3d_attn_fwd would pick the
- * 16-wide-plane fast path: the parity tests hold the two against each other. */
+ * row kernels' fast path (planes 16 or 32 wide, or 8 wide with an even number of rows; bf16, dim_head 32 / 64 / 128): the parity tests hold the two against each other. */
 int wmz_local3d_attn_fwd_general(const void* q, const void* k, const void* v, void* out, float* lse, float* logits_dbg,
                                  int B, int S, int H, int W, int heads, int dh, int eS, int eH, int eW,
                                  long ldq, long ldk, long ldv, long ldo, int dtype, void* stream);
@@ -86,6 +86,15 @@ int wmz_local3d_attn_bwd(const void* q, const void* k, const void* v, const void
                          int B, int S, int H, int W, int heads, int dh, int eS, int eH, int eW,
                          long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv,
                          int dtype, void* stream);
+
+/* Same contract, always on the general kernels even where wmz_local3d_attn_bwd would pick the row kernels (bf16, dim_head 32 /
+ * 64 / 128, planes 16 or 32 wide, or 8 wide with an even number of rows): the parity tests and the A/B timings hold the two
+ * against each other. */
+int wmz_local3d_attn_bwd_general(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                 const void* dout, void* dq, void* dk, void* dv, float* delta_ws,
+                                 int B, int S, int H, int W, int heads, int dh, int eS, int eH, int eW,
+                                 long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv,
+                                 int dtype, void* stream);
 
 /* ---- nn.Linear family (local_3d_attention.py:46-53 to_q/to_k/to_v/to_out, :23-29 FeedForward, main.py:31
  * logit_proj), optionally fused with the PreNorm LayerNorm in front (:14-17) and the residual add behind
@@ -354,8 +363,9 @@ int wmz_embed_qkv_fused_fwd_planes(const int64_t* z, const float* emb, const flo
  * (local_3d_attention.py:78-118); BASELINE.json asks for attention logits within 1e-3 relative of it, which bf16 operands miss
  * end to end (4e-3 on the default model) and fp32 operands pay 11x for (the exact-f32 MFMA runs at 1/16 of the rate): half
  * operands give 5e-4 at the bf16 speed.  Contracts as the entry points without the suffix, every `bf16` there read as `half`;
- * wmz_local3d_attn_fwd / _fwd_planes take dtype = WMZ_F16 for the same tensors (dim_head 32 / 64 / 128, planes 16 wide or 8
- * wide with an even number of rows; anything else returns WMZ_ERR_UNSUPPORTED).  Values beyond +-65504 become infinities. */
+ * wmz_local3d_attn_fwd / _fwd_planes take dtype = WMZ_F16 for the same tensors (dim_head 32 / 64 / 128, planes 16 wide, 32 wide
+ * -- a plane [H, 32] is read as 2H tile rows of 16, any H; no other multiple of 16 --, or 8 wide with an even number of rows;
+ * anything else returns WMZ_ERR_UNSUPPORTED).  Values beyond +-65504 become infinities. */
 int wmz_layer_fused_fwd_f16(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
                             const float* vec, int ntok, int D, int I, int M, int has_head, int has_tail, float eps,
                             void* stream);

@@ -14,7 +14,7 @@ _DTYPES = {'bf16': torch.bfloat16, 'bfloat16': torch.bfloat16, 'fp32': torch.flo
 #   float16 the PRECISE fused mode: inference at the default widths runs the fused kernels with IEEE-half MFMA operands and a half
 #           residual stream between the layers (~5e-4 at the bf16 speed: inside the 1e-3 BASELINE.json asks for); everything the
 #           half kernels are not built for (training, widths other than the default and the published ones, planes outside the row
-#           attention kernel's shapes, the conv encoder / decoder) runs the fp32 route -- never bf16.  The conv encoder / decoder
+#           attention kernel's shapes -- 16 or 32 wide, or 8 wide with an even row count --, the conv encoder / decoder) runs the fp32 route -- never bf16.  The conv encoder / decoder
 #           has a half route of its own, opt-in: precise_conv below.
 _precise = False
 _compute_dtype = None

@@ -304,10 +304,37 @@ int wmz_attn_bwd_row16_dispatch(const void* q, const void* k, const void* v, con
                                 const void* dout, void* dq, void* dk, void* dv, float* delta, const AttnGeom& G, long lddo,
                                 long lddq, long lddk, long lddv, hipStream_t st);
 
+// ... and its 32-wide plane mode (G.H = 2H tile rows, G.W = 16)
+int wmz_attn_bwd_row32_dispatch(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                const void* dout, void* dq, void* dk, void* dv, float* delta, const AttnGeom& G, long lddo,
+                                long lddq, long lddk, long lddv, hipStream_t st);
+
+static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                         const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
+                         int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
+                         long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream, bool general);
+
 extern "C" int wmz_local3d_attn_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse,
                                     const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
                                     int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
                                     long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream) {
+  return attn_bwd_impl(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, B, S, H, W, heads, dh, eS, eH, eW, ldq, ldk, ldv, ldo, lddo,
+                       lddq, lddk, lddv, dtype, stream, false);
+}
+
+// Same contract, always on the general kernels: the parity tests and the A/B timings hold the row kernels against them.
+extern "C" int wmz_local3d_attn_bwd_general(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                            const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
+                                            int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
+                                            long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream) {
+  return attn_bwd_impl(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, B, S, H, W, heads, dh, eS, eH, eW, ldq, ldk, ldv, ldo, lddo,
+                       lddq, lddk, lddv, dtype, stream, true);
+}
+
+static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                         const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
+                         int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
+                         long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream, bool general) {
   WMZ_REQUIRE(q && k && v && out && lse && dout && dq && dk && dv && delta_ws, "wmz_local3d_attn_bwd: null tensor");
   WMZ_REQUIRE(B > 0 && S > 0 && H > 0 && W > 0 && heads > 0 && dh > 0, "wmz_local3d_attn_bwd: bad shape");
   WMZ_REQUIRE(eS >= 0 && eH >= 0 && eW >= 0, "wmz_local3d_attn_bwd: negative extent");
@@ -328,9 +355,15 @@ extern "C" int wmz_local3d_attn_bwd(const void* q, const void* k, const void* v,
   PK.x1 = k; PK.x2 = v; PK.y1 = q; PK.y2 = dout; PK.o = nullptr; PK.lse = lse; PK.delta = delta_ws; PK.g1 = dk; PK.g2 = dv;
   PK.ldx1 = ldk; PK.ldx2 = ldv; PK.ldy1 = ldq; PK.ldy2 = lddo; PK.ldo = 0; PK.ldg1 = lddk; PK.ldg2 = lddv;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == WMZ_BF16 && W == 16 && (dh == 32 || dh == 64 || dh == 128) )
+  const bool row = dtype == WMZ_BF16 && (dh == 32 || dh == 64 || dh == 128) && !general;
+  if (row && W == 16)
     return wmz_attn_bwd_row16_dispatch(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, G, lddo, lddq, lddk, lddv, st);
-  if (dtype == WMZ_BF16 && W == 8 && (H & 1) == 0 && (dh == 32 || dh == 64 || dh == 128)) {
+  if (row && W == 32) {
+    AttnGeom G32 = G;                      // a 32-wide plane as 2H tile rows of 16, any H (attn_slab_walk.h: the w32 window law)
+    G32.H = 2 * H; G32.W = 16;
+    return wmz_attn_bwd_row32_dispatch(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, G32, lddo, lddq, lddk, lddv, st);
+  }
+  if (row && W == 8 && (H & 1) == 0) {
     AttnGeom G8 = G;                       // an 8-wide plane as H / 2 tile rows of 16 (attn_fwd_row16.hip)
     G8.w8 = 1; G8.H = H / 2; G8.W = 16;
     return wmz_attn_bwd_row16_dispatch(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, G8, lddo, lddq, lddk, lddv, st);

@@ -76,12 +76,20 @@ struct RBwdPtrs {
   long ldx1, ldx2, ldy1, ldy2, ldo, ldg1, ldg2;
 };
 
+// W32 (bit 1 of MODE; bit 0 is the role): planes 32 wide handed over as 2H tile rows of 16, the window law of attn_slab_walk.h
+// (w32_*).  The law is symmetric in owner and visitor, so both roles take it alike: an owner of tile row R visits the tile rows of
+// both halves of its plane rows h - eH .. h + eH, and since a slab holds one row parity the column mask -- the 16-wide one against
+// the owner's own half, the seam mask against the other -- is rebuilt once per slab (the biases, and the dq pass's accumulator
+// starts with them).
 // W8 (8-wide planes handed over as H / 2 tile rows of 16, see attn_fwd_row16.hip): the window is |D| <= eHv = ceil(eH / 2) tile
 // rows, the column mask compares c & 7, and in the two rim rows |D| = eHv a pair is inside only if |2 D + dp| <= eH with
 // dp = sub-row of the lane's visitor columns - sub-row of its owner column: one select per bias there.
 template <int DH, int MODE, int NW, int KC, bool ALIGNED, bool W8>
 __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)) void attn_bwd_row16_kernel(RBwdPtrs P, AttnGeom G) {
   using I = BImg<DH, KC>;
+  constexpr int ROLE = MODE & 1;                         // 0: the dq pass, 1: the dk | dv pass (MODE 0 / MODE 1 of the comments)
+  constexpr bool W32 = (MODE & 2) != 0;                  // planes 32 wide, handed over as 2H tile rows (above)
+  static_assert(!(W8 && W32) && (NW & 1) == 0, "one plane view at a time; workgroups start on even tile rows");
   constexpr int CH = 2 * KC, LOG_CH = CH == 16 ? 4 : 2;
   static_assert((1 << LOG_CH) == CH, "chunks of 16 or 4 rows");
   constexpr int KS = DH / 32, MT = DH / 16;
@@ -112,7 +120,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
     const int d = W8 ? ((4 * g + r) & 7) - (li & 7) : 4 * g + r - li;
     bias[r] = (d <= G.eW && -d <= G.eW) ? 0.f : -INFINITY;
   }
-  const int eHv = W8 ? (G.eH + 1) >> 1 : G.eH;
+  const int eHv = W8 ? (G.eH + 1) >> 1 : (W32 ? w32_stage_extent(G.eH) : G.eH);     // (W32: of the workgroup's staging)
   const int dp = (g >> 1) - (li >> 3);
   const bool ok_lo = (2 * eHv - dp <= G.eH) && (dp - 2 * eHv <= G.eH);    // W8: pair inside the window at D = -eHv / D = +eHv
   const bool ok_hi = (2 * eHv + dp <= G.eH) && (-2 * eHv - dp <= G.eH);
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
   };
 
   // ---- slab geometry and walk (as in attn_fwd_row16.hip; stated once and pinned on the host: attn_slab_walk.h)
-  const int my_lo = max(h - eHv, 0), my_hi = min(h + eHv, H - 1);
+  const int my_lo = max(W32 ? w32_row_lo(h, G.eH) : h - eHv, 0), my_hi = min(W32 ? w32_row_hi(h, G.eH) : h + eHv, H - 1);
   const int t_lo = max(h0 - eHv, 0), t_hi = min(min(h0 + NW - 1, H - 1) + eHv, H - 1);
   const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
   const int c_first = t_lo >> LOG_CH, c_last = t_hi >> LOG_CH;
@@ -188,7 +196,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
         __builtin_amdgcn_global_load_lds((gptr_t)(y2p + c), (lptr_t)(dbuf + I::IMG + piece * 1024), 16, 0, 0);
       }
     }
-    if constexpr (MODE == 1) {
+    if constexpr (ROLE == 1) {
       // per-visitor (query) lse / delta of the slab (slab row r = 16 t + w <-> plane row base + 2 t, column w) ride the same
       // DMA queue, one dword per lane: waves 0, 1 bring the 128 lse values, waves 2, 3 the 128 deltas.  (As plain loads parked
       // in registers they made hipcc drain vmcnt(0) -- i.e. the slab just requested -- at the first LDS read of every step.)
@@ -206,6 +214,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
 
   // ---- owner rows (after the first slab's requests: both are in flight together)
   Frag8<bf16_t> x1f[KS], x2f[KS];
+  float bl_in = 0.f;                                     // W32, dq pass: -own lse2 / c2, the start of a column inside the window
   float bl[4], nde = 0.f;                                // MODE 0: the accumulators' initial values -- (bias - own lse2) / c2 per
                                                          // column (S' = Q.K + that, exponent = c2 S') and -own delta (D' = dP - delta)
   {
@@ -217,7 +226,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
     for (int ks = 0; ks < KS; ++ks) {
       frag_load(x1f[ks], r1 + ks * 32 + g * 8);
       frag_load(x2f[ks], r2 + ks * 32 + g * 8);
-      if constexpr (MODE == 0) {
+      if constexpr (ROLE == 0) {
         Frag8<bf16_t> of;
         frag_load(of, P.o + row * P.ldo + (long)head * DH + ks * 32 + g * 8);
 #pragma unroll
@@ -227,11 +236,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) bl[r] = bias[r];
-    if constexpr (MODE == 0) {
+    if constexpr (ROLE == 0) {
       dsum = wave_groups_sum(dsum);
       const float own_lse = P.lse[row * G.heads + head] * L2E;
 #pragma unroll
       for (int r = 0; r < 4; ++r) bl[r] = (bias[r] - own_lse) / c2;
+      bl_in = -own_lse / c2;
       nde = -dsum;
       if (active && g == 0) {
         // workspace for the dk | dv pass: delta, and behind it (one row of [tokens, heads] further) -lse / scale -- the initial
@@ -242,10 +252,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
     }
   }
   f32x4 acc1[MT];
-  f32x4 acc2[MODE == 1 ? MT : 1];
+  f32x4 acc2[ROLE == 1 ? MT : 1];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) acc1[mt] = (f32x4)(0.f);
-  if constexpr (MODE == 1) {
+  if constexpr (ROLE == 1) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc2[mt] = (f32x4)(0.f);
   }
@@ -268,6 +278,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
       if (!(WMZ_ABWD_ABL & 2)) issue();
     }
     const int lo = max(0, (my_lo - base + 1) >> 1), hi = min(KC - 1, (my_hi - base) >> 1);   // slab rows this wave needs
+    if constexpr (W32) {
+      // every row of this slab is the column half base & 1: the 16-wide mask against the owner's own half, else the seam mask
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool in = w32_col_ok(h, li, base, 4 * g + r, G.eW);
+        bias[r] = in ? 0.f : -INFINITY;
+        if constexpr (ROLE == 0) bl[r] = in ? bl_in : -INFINITY;
+      }
+    }
     if (active && !(WMZ_ABWD_ABL & 1)) {
       int t0 = lo;
       for (; t0 + 1 <= hi; t0 += 2) {
@@ -276,7 +295,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
         const int to0 = tbase + t0 * 16 * I::ROWP;
         f32x4 s0 = (f32x4)(0.f), s1 = (f32x4)(0.f), d0 = (f32x4)(0.f), d1 = (f32x4)(0.f);
         float bA[4] = {bias[0], bias[1], bias[2], bias[3]}, bB[4] = {bias[0], bias[1], bias[2], bias[3]};     // MODE 1: the rows' biases
-        if constexpr (MODE == 0) {
+        if constexpr (ROLE == 0) {
           s0 = s1 = (f32x4){bl[0], bl[1], bl[2], bl[3]};           // accumulator starts; rim rows of 8-wide planes masked in place
           d0 = d1 = (f32x4)(nde);
           rim(base + 2 * t0 - h, s0);
@@ -318,8 +337,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
         }
         // MODE 1 (two waves per SIMD, 256 registers): Y2's transposed fragments are requested here as well, so that BOTH
         // accumulations run back to back behind one wait instead of read -> wait -> MFMA twice
-        s16x4 z0[MODE == 1 ? MT : 1], z1[MODE == 1 ? MT : 1];
-        if constexpr (MODE == 1) {
+        s16x4 z0[ROLE == 1 ? MT : 1], z1[ROLE == 1 ? MT : 1];
+        if constexpr (ROLE == 1) {
           const unsigned yb0 = lds_addr(Y2s + to0), yb1 = yb0 + 16 * I::ROWP;
           if constexpr (WMZ_ABWD_ABL & 4) {
 #pragma unroll
@@ -332,7 +351,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
           }
         }
         float pv[8], dsv[8];
-        if constexpr (MODE == 1) {
+        if constexpr (ROLE == 1) {
           const int r0 = t0 * 16 + 4 * g, r1 = r0 + 16;
           const f32x4 l0 = *reinterpret_cast<const f32x4*>(vlse + r0), l1 = *reinterpret_cast<const f32x4*>(vlse + r1);
           const f32x4 e0 = *reinterpret_cast<const f32x4*>(vdel + r0), e1 = *reinterpret_cast<const f32x4*>(vdel + r1);
@@ -354,7 +373,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
         }
         Frag8<bf16_t> dsf, pf;
         frag_from_f32<bf16_t>(dsf, dsv);
-        if constexpr (MODE == 1) frag_from_f32<bf16_t>(pf, pv);
+        if constexpr (ROLE == 1) frag_from_f32<bf16_t>(pf, pv);
         ds_tr_wait();
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -363,7 +382,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
           yf.v = __builtin_shufflevector(x0[mt], x1[mt], 0, 1, 2, 3, 4, 5, 6, 7);
           if constexpr (WMZ_ABWD_ABL & 8) { asm volatile("" :: "v"(yf.v), "v"(dsf.v)); } else mma16(acc1[mt], yf, dsf);
         }
-        if constexpr (MODE == 1) {
+        if constexpr (ROLE == 1) {
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             asm volatile("" : "+v"(z0[mt]), "+v"(z1[mt]));
@@ -379,7 +398,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
         const int to0 = tbase + t0 * 16 * I::ROWP;
         f32x4 s0 = (f32x4)(0.f), d0 = (f32x4)(0.f);
         float bA[4] = {bias[0], bias[1], bias[2], bias[3]};
-        if constexpr (MODE == 0) { s0 = (f32x4){bl[0], bl[1], bl[2], bl[3]}; d0 = (f32x4)(nde); rim(base + 2 * t0 - h, s0); }
+        if constexpr (ROLE == 0) { s0 = (f32x4){bl[0], bl[1], bl[2], bl[3]}; d0 = (f32x4)(nde); rim(base + 2 * t0 - h, s0); }
         else rim(base + 2 * t0 - h, bA);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -394,7 +413,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
         s16x4 x0[MT];
         static_for<MT>([&](auto mt) { x0[mt] = ds_read_tr16_asm<mt * 32>(ya0); });
         float pv[4], dsv[4];
-        if constexpr (MODE == 1) {
+        if constexpr (ROLE == 1) {
           const int r0 = t0 * 16 + 4 * g;
           const f32x4 l0 = *reinterpret_cast<const f32x4*>(vlse + r0), e0 = *reinterpret_cast<const f32x4*>(vdel + r0);
 #pragma unroll
@@ -415,7 +434,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
           asm volatile("" : "+v"(x0[mt]));
           acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(x0[mt], dsf, acc1[mt], 0, 0, 0);
         }
-        if constexpr (MODE == 1) {
+        if constexpr (ROLE == 1) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) pf[r] = (short)f32_to_bf16_bits(pv[r]);
           const unsigned yb0 = lds_addr(Y2s + to0);
@@ -437,8 +456,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
   if (!active) return;
   const long orow = plane_o + h * 16 + li;
   bf16_t* g1 = P.g1 + orow * P.ldg1 + (long)head * DH;
-  store_owner_rows<MT>(g1, acc1, MODE == 0 ? G.scale : 1.f, g);
-  if constexpr (MODE == 1) store_owner_rows<MT>(P.g2 + orow * P.ldg2 + (long)head * DH, acc2, 1.f, g);
+  store_owner_rows<MT>(g1, acc1, ROLE == 0 ? G.scale : 1.f, g);
+  if constexpr (ROLE == 1) store_owner_rows<MT>(P.g2 + orow * P.ldg2 + (long)head * DH, acc2, 1.f, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -732,10 +751,10 @@ __global__ __launch_bounds__(1024) void attn_bwd_kvplane_kernel(RBwdPtrs P, Attn
 }
 
 template <int DH, int MODE, int NW, int KC, bool W8>
-int launch_one(const RBwdPtrs& P, AttnGeom G, hipStream_t st) {
+int launch_one(const RBwdPtrs& P, AttnGeom G, hipStream_t st, bool whole_chunks_form = true) {
   G.qgroups = wmz_cdiv(G.H, NW);
   const long nwg = (long)G.B * G.heads * G.S * G.qgroups;
-  if ((G.H % (2 * KC)) == 0) hipLaunchKernelGGL((attn_bwd_row16_kernel<DH, MODE, NW, KC, true, W8>), dim3((unsigned)nwg), dim3(NW * 64), 0, st, P, G);
+  if ((G.H % (2 * KC)) == 0 && whole_chunks_form) hipLaunchKernelGGL((attn_bwd_row16_kernel<DH, MODE, NW, KC, true, W8>), dim3((unsigned)nwg), dim3(NW * 64), 0, st, P, G);
   else hipLaunchKernelGGL((attn_bwd_row16_kernel<DH, MODE, NW, KC, false, W8>), dim3((unsigned)nwg), dim3(NW * 64), 0, st, P, G);
   WMZ_LAUNCH_CHECK("wmz_local3d_attn_bwd(row16)");
   return WMZ_OK;
@@ -773,19 +792,53 @@ int launch_both(const RBwdPtrs& PQ, const RBwdPtrs& PK, const AttnGeom& G, hipSt
   return launch_one<DH, 1, 8, 8, false>(PK, G, st);
 }
 
+// 32-wide planes (G.H = 2H tile rows): the multi-workgroup forms in their W32 mode (MODE bit 1).  Up to 8 tile rows on the 4-wave
+// workgroups with 2-row slabs, like 8-wide planes; above, the dq pass on 16-wave workgroups and the dk | dv pass on the 8-wave form
+// (the whole-plane dk | dv kernel is written for 16x16 planes and keeps its window law).
+template <int DH>
+int launch_both32(const RBwdPtrs& PQ, const RBwdPtrs& PK, const AttnGeom& G, hipStream_t st) {
+  if (G.H <= 8) {
+    const int rc = launch_one<DH, 2, 4, 2, false>(PQ, G, st);
+    return rc != WMZ_OK ? rc : launch_one<DH, 3, 4, 2, false>(PK, G, st);
+  }
+  // (at dim_head 128 the dq pass's whole-chunks form, which keeps its LDS-DMA offsets in registers, would spill 16 bytes at the
+  //  128 registers of a 16-wave workgroup: the clamped form, valid for any H, holds 128 without scratch)
+  const int rc = launch_one<DH, 2, 16, 8, false>(PQ, G, st, DH < 128);
+  return rc != WMZ_OK ? rc : launch_one<DH, 3, 8, 8, false>(PK, G, st);
+}
+
 }  // namespace
 
-int wmz_attn_bwd_row16_dispatch(const void* q, const void* k, const void* v, const void* out, const float* lse,
-                                const void* dout, void* dq, void* dk, void* dv, float* delta, const AttnGeom& G, long lddo,
-                                long lddq, long lddk, long lddv, hipStream_t st) {
-  RBwdPtrs PQ, PK;
+namespace {
+void row_ptrs(RBwdPtrs& PQ, RBwdPtrs& PK, const void* q, const void* k, const void* v, const void* out, const float* lse,
+              const void* dout, void* dq, void* dk, void* dv, float* delta, const AttnGeom& G, long lddo, long lddq, long lddk,
+              long lddv) {
   PQ.x1 = (const bf16_t*)q; PQ.x2 = (const bf16_t*)dout; PQ.y1 = (const bf16_t*)k; PQ.y2 = (const bf16_t*)v;
   PQ.o = (const bf16_t*)out; PQ.lse = lse; PQ.delta = delta; PQ.g1 = (bf16_t*)dq; PQ.g2 = nullptr;
   PQ.ldx1 = G.ldq; PQ.ldx2 = lddo; PQ.ldy1 = G.ldk; PQ.ldy2 = G.ldv; PQ.ldo = G.ldo; PQ.ldg1 = lddq; PQ.ldg2 = 0;
   PK.x1 = (const bf16_t*)k; PK.x2 = (const bf16_t*)v; PK.y1 = (const bf16_t*)q; PK.y2 = (const bf16_t*)dout;
   PK.o = nullptr; PK.lse = lse; PK.delta = delta; PK.g1 = (bf16_t*)dk; PK.g2 = (bf16_t*)dv;
   PK.ldx1 = G.ldk; PK.ldx2 = G.ldv; PK.ldy1 = G.ldq; PK.ldy2 = lddo; PK.ldo = 0; PK.ldg1 = lddk; PK.ldg2 = lddv;
+}
+}  // namespace
+
+int wmz_attn_bwd_row16_dispatch(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                const void* dout, void* dq, void* dk, void* dv, float* delta, const AttnGeom& G, long lddo,
+                                long lddq, long lddk, long lddv, hipStream_t st) {
+  RBwdPtrs PQ, PK;
+  row_ptrs(PQ, PK, q, k, v, out, lse, dout, dq, dk, dv, delta, G, lddo, lddq, lddk, lddv);
   if (G.dh == 128) return launch_both<128>(PQ, PK, G, st);
   if (G.dh == 64) return launch_both<64>(PQ, PK, G, st);
   return launch_both<32>(PQ, PK, G, st);
+}
+
+// 32-wide planes: G.H = 2H tile rows, G.W = 16 (attn_bwd.hip)
+int wmz_attn_bwd_row32_dispatch(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                const void* dout, void* dq, void* dk, void* dv, float* delta, const AttnGeom& G, long lddo,
+                                long lddq, long lddk, long lddv, hipStream_t st) {
+  RBwdPtrs PQ, PK;
+  row_ptrs(PQ, PK, q, k, v, out, lse, dout, dq, dk, dv, delta, G, lddo, lddq, lddk, lddv);
+  if (G.dh == 128) return launch_both32<128>(PQ, PK, G, st);
+  if (G.dh == 64) return launch_both32<64>(PQ, PK, G, st);
+  return launch_both32<32>(PQ, PK, G, st);
 }

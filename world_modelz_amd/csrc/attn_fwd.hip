@@ -255,6 +255,12 @@ int wmz_attn_fwd_row16_dispatch(const void* q, const void* k, const void* v, voi
 int wmz_attn_fwd_row16_dispatch_f16(const void* q, const void* k, const void* v, void* out, float* lse, float* dbg,
                                     const AttnGeom& G, hipStream_t st);
 
+// the row kernel's 32-wide plane mode (attn_fwd_row32.hip, attn_fwd_row32_f16.hip): G.H = 2H tile rows, G.W = 16
+int wmz_attn_fwd_row32_dispatch(const void* q, const void* k, const void* v, void* out, float* lse, float* dbg,
+                                const AttnGeom& G, hipStream_t st);
+int wmz_attn_fwd_row32_dispatch_f16(const void* q, const void* k, const void* v, void* out, float* lse, float* dbg,
+                                    const AttnGeom& G, hipStream_t st);
+
 // development knobs (wmz_debug_attn_knobs): ablation switches and kernel-variant selector, 0 / 0 in production
 static int g_attn_dbg = 0, g_attn_variant = 0;
 extern "C" int wmz_debug_attn_knobs(int dbg, int variant) { g_attn_dbg = dbg; g_attn_variant = variant; return WMZ_OK; }
@@ -316,9 +322,17 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* out,
       G8.w8 = 1; G8.H = H / 2; G8.W = 16;
       return row16(q, k, v, out, lse, logits_dbg, G8, st);
     }
+    if (W == 32) {
+      // a 32-wide plane (the 32x32 latents of 256x256 frames at three downscale steps) is a 16-wide plane of 2H tile rows in
+      // memory, any H: the row kernel's W32 mode, with the window law of attn_slab_walk.h.  Only this width: the law is a seam
+      // between exactly two column halves.
+      AttnGeom G32 = G;
+      G32.H = 2 * H; G32.W = 16;
+      return (dtype == WMZ_F16 ? wmz_attn_fwd_row32_dispatch_f16 : wmz_attn_fwd_row32_dispatch)(q, k, v, out, lse, logits_dbg, G32, st);
+    }
   }
   if (dtype == WMZ_F16) {
-    wmz_set_error("wmz_local3d_attn_fwd: half operands are built for the row kernel's shapes (dim_head 32 / 64 / 128, planes 16 wide or 8 wide with an even number of rows)");
+    wmz_set_error("wmz_local3d_attn_fwd: half operands are built for the row kernel's shapes (dim_head 32 / 64 / 128, planes 16 or 32 wide, or 8 wide with an even number of rows)");
     return WMZ_ERR_UNSUPPORTED;
   }
   const int DHp = dh <= 32 ? 32 : (dh <= 64 ? 64 : 128);

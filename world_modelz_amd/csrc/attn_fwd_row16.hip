@@ -94,6 +94,14 @@ constexpr int kSched[8][6] = {
 // OUTERMOST tile rows (|D| = eHv) a (query, key) pair is inside the window only if |2 D + (c_k >> 3) - (c_q >> 3)| <= eH -- a
 // per-lane condition (a lane's four key columns share one sub-row), applied as one select per logit in those steps only.  There a
 // query can have nothing visible in a whole step, so the deferred running maximum is started per lane (firstl).
+//
+// W32 (bit 4 of MODE; instantiated by attn_fwd_row32.hip and attn_fwd_row32_f16.hip only): planes 32 wide, the same trick run the
+// other way.  A plane [H, 32] IS a plane [2H, 16] in memory (G.H holds 2H): tile row R = 2h + (w >> 4) is the left (even R) or right
+// (odd R) half of plane row h.  The window law in these coordinates is stated in attn_slab_walk.h (w32_*).  Staging is the 16-wide
+// plane's; a wave visits the tile rows of both halves of its plane rows h - eH .. h + eH, and because a slab holds one row parity
+// the column mask -- the 16-wide one against the wave's own half, the seam mask |c' - c +- 16| <= eW against the other -- is the
+// same for every step of a slab: the four biases are rebuilt from it (and from minus the running maximum) once per slab.  Against
+// the other half most queries see nothing for eW < 16, so the running maximum starts per lane here too.
 template <int DH, typename SH, int MODE, bool ALIGNED, bool PROBE, bool TS, bool W8>
 __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                       const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
@@ -106,6 +114,9 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
   constexpr int KS = DH / 32, MT = DH / 16;
   constexpr int SPLIT = MODE & 7;                        // where the LDS-DMA pieces of the next slab are issued (kSched)
   constexpr bool EPI16 = (MODE & 8) != 0;                // 16-byte output stores (lane pairs swap halves)
+  constexpr bool W32 = (MODE & 16) != 0;                 // planes 32 wide, handed over as 2H tile rows (above; attn_fwd_row32.hip)
+  constexpr bool LANE_FIRST = W8 || W32;                 // the running maximum starts per lane
+  static_assert(!(W8 && W32) && (!W32 || (RS == 2 && (NW & 1) == 0)), "a slab of the 32-wide mode holds one column half");
   __shared__ __attribute__((aligned(1024))) char smem[NBUF * I::BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -134,13 +145,13 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int d = W8 ? ((4 * g + r) & 7) - (li & 7) : 4 * g + r - li;
-    bm[r] = (d <= G.eW && -d <= G.eW) ? 0.f : -INFINITY;
+    bm[r] = (d <= G.eW && -d <= G.eW) ? 0.f : -INFINITY;                  // (W32: rebuilt at every slab, for its column half)
   }
-  const int eHv = W8 ? (G.eH + 1) >> 1 : G.eH;          // window extent in tile rows
+  const int eHv = W8 ? (G.eH + 1) >> 1 : (W32 ? w32_stage_extent(G.eH) : G.eH);   // window extent in tile rows (W32: of the workgroup's staging)
   const int dp = (g >> 1) - (li >> 3);                  // W8: sub-row of the lane's key columns minus sub-row of its query
   const bool ok_lo = (2 * eHv - dp <= G.eH) && (dp - 2 * eHv <= G.eH);    // W8: pair inside the window at D = -eHv / D = +eHv
   const bool ok_hi = (2 * eHv + dp <= G.eH) && (-2 * eHv - dp <= G.eH);
-  bool firstl = true;                                   // W8: this lane's query has not seen a logit yet
+  bool firstl = true;                                   // W8, W32: this lane's query has not seen a logit yet
 
   Frag8<bf16_t> qf[KS];
   f32x4 o[MT];
@@ -151,7 +162,7 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
 
   const int kbase = li * I::KROW + g * 16;
   const int vbase = I::KIMG + (4 * g + (li >> 2)) * I::VROW + (li & 3) * 8;
-  const int my_lo = max(hq - eHv, 0), my_hi = min(hq + eHv, H - 1);
+  const int my_lo = max(W32 ? w32_row_lo(hq, G.eH) : hq - eHv, 0), my_hi = min(W32 ? w32_row_hi(hq, G.eH) : hq + eHv, H - 1);
   // key rows the workgroup stages (this geometry, the plane order and next_state() / advance() below: attn_slab_walk.h states them
   // once and tests/test_attn_slab_walk_cpu.py pins them -- keep the two in step)
   const int t_lo = max(h0 - eHv, 0), t_hi = min(min(h0 + NW - 1, H - 1) + eHv, H - 1);
@@ -246,7 +257,7 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
   auto rescale = [&](float mx, auto& t) {
     constexpr int nt = (int)(sizeof(t) / sizeof(float));
     float gm = wave_groups_max(mx);
-    if constexpr (W8) {
+    if constexpr (LANE_FIRST) {
       // per lane: a query with nothing visible in this step (gm = -inf) neither moves nor starts its reference
       const bool dead = gm == -INFINITY;
       gm = dead ? 0.f : (firstl ? gm : fmaxf(gm, 0.f));
@@ -330,6 +341,11 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
     issue_at(C0{}, false);
     if (j < 14) WMZ_ATS(5 + 4 * j);
     const int lo = max(0, (my_lo - base + RS - 1) >> LOG_RS), hi = min(KC - 1, (my_hi - base) >> LOG_RS);   // slab rows this wave needs
+    if constexpr (W32) {
+      // every row of this slab is the column half base & 1: the 16-wide mask if that is the wave's own half, else the seam mask
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bm[r] = w32_col_ok(hq, li, base, 4 * g + r, G.eW) ? -m_run : -INFINITY;
+    }
     if (act && !(G.dbg & 1)) {
       int t0 = lo;
       for (; t0 + 1 <= hi; t0 += 2) {
@@ -367,11 +383,12 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
           const int nk = (2 * G.eS + 1) * kh * kw;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int dw = W8 ? ((4 * g + r) & 7) - (li & 7) : 4 * g + r - li;
+            const int dw = W8 ? ((4 * g + r) & 7) - (li & 7) : (W32 ? w32_dw(hq, li, base, 4 * g + r) : 4 * g + r - li);
             if (dw <= G.eW && -dw <= G.eW) {
               const int ds = (sk_lo + pl) - s;
               const int D0 = base + RS * t0 - hq;
-              const int dh0 = W8 ? 2 * D0 + dp : D0, dh1 = W8 ? dh0 + 2 * RS : dh0 + RS;      // in plane rows
+              const int dh0 = W8 ? 2 * D0 + dp : (W32 ? w32_dh(hq, base + RS * t0) : D0);
+              const int dh1 = W8 ? dh0 + 2 * RS : (W32 ? dh0 + RS / 2 : dh0 + RS);             // in plane rows
               float* row = DBG + (qn * G.heads + head) * nk;
               if (dh0 <= G.eH && -dh0 <= G.eH) row[((ds + G.eS) * kh + (dh0 + G.eH)) * kw + dw + G.eW] = sc0[r] * G.scale;
               if (dh1 <= G.eH && -dh1 <= G.eH) row[((ds + G.eS) * kh + (dh1 + G.eH)) * kw + dw + G.eW] = sc1[r] * G.scale;
@@ -436,11 +453,11 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
           const int nk = (2 * G.eS + 1) * kh * kw;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int dw = W8 ? ((4 * g + r) & 7) - (li & 7) : 4 * g + r - li;
+            const int dw = W8 ? ((4 * g + r) & 7) - (li & 7) : (W32 ? w32_dw(hq, li, base, 4 * g + r) : 4 * g + r - li);
             if (dw <= G.eW && -dw <= G.eW) {
               const int ds = (sk_lo + pl) - s;
               const int D0 = base + RS * t0 - hq;
-              const int dh0 = W8 ? 2 * D0 + dp : D0;
+              const int dh0 = W8 ? 2 * D0 + dp : (W32 ? w32_dh(hq, base + RS * t0) : D0);
               if (dh0 <= G.eH && -dh0 <= G.eH)
                 DBG[(qn * G.heads + head) * nk + ((ds + G.eS) * kh + (dh0 + G.eH)) * kw + dw + G.eW] = sc0[r] * G.scale;
             }
@@ -539,7 +556,7 @@ int by_dh(const void* q, const void* k, const void* v, void* out, float* lse, fl
 
 // Development probe: per-wave s_memtime stamps of workgroup 0 (tools/ts_attn.py); nullptr switches back to the product
 // instantiation, which carries no stamp code at all.
-#ifndef WMZ_OP16_F16
+#if !defined(WMZ_OP16_F16) && !defined(WMZ_ATTN_ROW32)
 extern "C" int wmz_debug_attn_timestamps(void* buf) { g_attn_ts = (long long*)buf; return WMZ_OK; }
 #endif
 
@@ -547,6 +564,24 @@ extern "C" int wmz_debug_attn_timestamps(void* buf) { g_attn_ts = (long long*)bu
 #define WMZ_ATTN_MODE 9          // kSched[1]: K pieces behind the barrier, V pieces inside the first step; 16-byte output stores
 #endif
 
+#ifdef WMZ_ATTN_ROW32
+// The 32-wide units (attn_fwd_row32.hip, attn_fwd_row32_f16.hip compile this source with WMZ_ATTN_ROW32: the instantiations of the
+// W32 mode and nothing else, so that the 16-wide units keep exactly their kernels).  Called by wmz_local3d_attn_fwd for W == 32
+// with G.H = 2H tile rows and G.W = 16; dbg as below.  Workgroup shapes as for 8-wide planes, by the number of tile rows: up to 8 of
+// them (planes of up to 4 rows) take the 4-wave shape with 2-row slabs -- the big shape would run at most half full and stage 8-row
+// slabs holding at most 4 rows --, everything above, the 32x32 latents' 64 tile rows among them, takes the 16-wave shape, four
+// workgroups to a 32x32 plane.  (Both choices follow the 8-wide measurement of DESIGN.md 4.1; the threshold was not re-measured.)
+int WMZ_FN(wmz_attn_fwd_row32_dispatch)(const void* q, const void* k, const void* v, void* out, float* lse, float* dbg,
+                                const AttnGeom& G, hipStream_t st) {
+  constexpr int M32 = WMZ_ATTN_MODE | 16;
+  if (G.H <= 8) {
+    if (dbg != nullptr) return by_dh<Small, M32, true, false, false>(q, k, v, out, lse, dbg, G, st);
+    return by_dh<Small, M32, false, false, false>(q, k, v, out, lse, nullptr, G, st);
+  }
+  if (dbg != nullptr) return by_dh<Big, M32, true, false, false>(q, k, v, out, lse, dbg, G, st);
+  return by_dh<Big, M32, false, false, false>(q, k, v, out, lse, nullptr, G, st);
+}
+#else
 // Called by wmz_local3d_attn_fwd when the shape qualifies (bf16, dim_head in {32,64,128}; W == 16, or W == 8 with an even number
 // of rows: G.w8 set and G.H = H / 2 tile rows).  dbg: optional logits probe [N, heads, window] (natural-log-domain scaled logits of
 // the in-window slots, pre-filled with -1e9 by the caller).
@@ -567,3 +602,4 @@ int WMZ_FN(wmz_attn_fwd_row16_dispatch)(const void* q, const void* k, const void
   //  tools/build_variant.py <tag> attn_fwd_row16.hip -DWMZ_ATTN_MODE=<0..15> and load the library through WMZ_LIB_PATH)
   return by_dh<Big, WMZ_ATTN_MODE, false, false, false>(q, k, v, out, lse, nullptr, G, st);
 }
+#endif  // WMZ_ATTN_ROW32

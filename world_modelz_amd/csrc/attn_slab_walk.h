@@ -79,6 +79,26 @@ template <int CH, int KC, bool CLAMP = true> struct SlabWalk {
   }
 };
 
+// ---- Planes 32 wide.  A plane [H, 32] IS a plane [2H, 16] in memory, and is handed to the row kernels as 2H tile rows of 16: token
+// (h, w) sits in tile row R = 2h + (w >> 4), tile column c = w & 15, and a = R & 1 says which column half the tile row is.  Staging,
+// fragments, clamps and piece_voff are those of the 16-wide plane of 2H rows; only the window is stated in tile coordinates:
+//   rows     an owner of tile row R visits the tile rows [R - a - 2 eH, R - a + 2 eH + 1] (both halves of the plane rows h - eH ..
+//            h + eH), clipped to the plane by the caller;
+//   columns  (R, c) sees (R', c') iff |16 ((R' & 1) - a) + c' - c| <= eW: the 16-wide mask against a row of the owner's half, the
+//            seam mask against a row of the other half.  A slab holds ONE row parity (RS = 2), so which of the two applies is
+//            uniform per wave and slab;
+//   slot     the pair sits at dh = (R' - R + a - a') / 2 (the numerator is even), dw = 16 (a' - a) + c' - c of the window.
+// tests/test_attn_32_wide_cpu.py checks all three against the plain rule |h' - h| <= eH and |w' - w| <= eW.
+WMZ_HD int w32_row_lo(int R, int eH) { return R - (R & 1) - 2 * eH; }
+WMZ_HD int w32_row_hi(int R, int eH) { return R - (R & 1) + 2 * eH + 1; }
+WMZ_HD int w32_dw(int R, int c, int Rk, int ck) { return 16 * ((Rk & 1) - (R & 1)) + ck - c; }
+WMZ_HD int w32_dh(int R, int Rk) { return (Rk - R + (R & 1) - (Rk & 1)) / 2; }
+WMZ_HD bool w32_col_ok(int R, int c, int Rk, int ck, int eW) { const int d = w32_dw(R, c, Rk, ck); return d <= eW && -d <= eW; }
+// What slab_geom takes as eHv in this mode.  A workgroup starts on an even tile row and owns an even number of them (NW is 4 or 16,
+// and the plane has 2H tile rows), so its first owner is a left half (reaching down to h0 - 2 eH) and its last one a right half
+// (reaching up to itself + 2 eH): the symmetric extent 2 eH covers every owner's rows; 2 eH + 1 would only stage one row more.
+WMZ_HD int w32_stage_extent(int eH) { return 2 * eH; }
+
 // Byte offset (inside a plane, relative to plane row `base`) of the 16 bytes this lane fetches for DMA piece `piece` of a padded
 // image (rows of ROWP bytes): the lane landing on (slab row, 16-byte chunk) fetches that chunk of plane row base + RS * (slab row
 // / 16), column slab row % 16; pad chunks fetch chunk 0 (never read).  `row_lim`: rows past the plane are redirected to the last

@@ -90,9 +90,10 @@ def chain_pays(widths, ntok, training):
 
 
 def half_attention_ok(transformer, H, W):
-    """The half attention unit (csrc/attn_fwd_row16_f16.hip) is built for these planes and heads (csrc/attn_fwd.hip)."""
+    """The half attention units (csrc/attn_fwd_row16_f16.hip, and csrc/attn_fwd_row32_f16.hip for 32-wide planes) are built for
+    these planes and heads (csrc/attn_fwd.hip)."""
     dh = {a.fn.to_q.weight.shape[0] // a.fn.heads for a, _ in transformer.layers}
-    return dh <= {32, 64, 128} and (W == 16 or (W == 8 and H % 2 == 0))
+    return dh <= {32, 64, 128} and (W in (16, 32) or (W == 8 and H % 2 == 0))
 
 
 def inference_route(transformer, dtype, H, W, ntok):

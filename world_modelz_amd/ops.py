@@ -414,9 +414,10 @@ def vq_ema_update(embedding, cluster_size, activation_count, counts, dw, decay, 
 
 # ------------------------------------------------------------------------------------------------ backward
 
-def local3d_attention_bwd(q, k, v, out, lse, dout, extents, heads, dqkv=None):
+def local3d_attention_bwd(q, k, v, out, lse, dout, extents, heads, dqkv=None, general=False):
     """Returns (dq, dkv) with dkv = [..., 2I] holding dk | dv (the layout the fused k|v projection wants).
-    dqkv (optional, [..., 3I]): write dq | dk | dv into its column thirds instead (fused to_qkv of config 5)."""
+    dqkv (optional, [..., 3I]): write dq | dk | dv into its column thirds instead (fused to_qkv of config 5).
+    general: take the general kernels even where the row kernels apply (parity tests, A/B timings)."""
     B, S, H, W, I = q.shape
     dh = I // heads
     dt = L.dtype_code(q.dtype)
@@ -436,7 +437,7 @@ def local3d_attention_bwd(q, k, v, out, lse, dout, extents, heads, dqkv=None):
         dq, dk, dv = dqkv[..., :I], dqkv[..., I:2 * I], dqkv[..., 2 * I:]
         dkv = dqkv[..., I:]
         lddq = lddkv = 3 * I
-    L.call('wmz_local3d_attn_bwd', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(dout), L.ptr(dq),
+    L.call('wmz_local3d_attn_bwd_general' if general else 'wmz_local3d_attn_bwd', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(dout), L.ptr(dq),
            L.ptr(dk), L.ptr(dv), L.ptr(delta), B, S, H, W, heads, dh, int(extents[0]), int(extents[1]),
            int(extents[2]), ldq, ldk, ldv, ldo, lddo, lddq, lddkv, lddkv, dt, L.stream())
     return dq, dkv
