@@ -872,6 +872,33 @@ int wmz_adamw_step(float* p, const float* g, float* m, float* v, long n, double 
  * gradient norm sum (grad_scale g)^2, computed in the same pass (zero it first). */
 int wmz_adamw_step_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, double beta1, double beta2,
                        double eps, double weight_decay, double grad_scale, float* sqnorm_out, void* stream);
+/* torch.optim.Adam step (amsgrad off), the reference's `--optimizer Adam` (main.py:432-439, train_vqae.py, minecraft/main2.py,
+ * minecraft/sparse_diffusion.py, minecraft/train_vqae.py: torch.optim.Adam(..., weight_decay=opt.weight_decay)): the weight decay
+ * is an L2 term of the gradient, NOT decoupled -- there is no p *= 1 - lr wd.  Arguments, alignment and bias corrections as for
+ * the AdamW step above.  Per element, in fp32:
+ *   gi = grad_scale g + wd p;  m = beta1 m + (1 - beta1) gi;  v = beta2 v + (1 - beta2) gi^2;
+ *   p -= (lr / bc1) * (m / (sqrt(v) / sbc2 + eps)). */
+int wmz_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
+                  double eps, double weight_decay, long step, double grad_scale, void* stream);
+/* The same with hyper = [lr, 1 - beta1^t, sqrt(1 - beta2^t)] in device memory.  sqnorm_out (optional): += sum (grad_scale g)^2,
+ * the GRADIENT's squared norm as in the AdamW form (main.py:188-193), not that of gi. */
+int wmz_adam_step_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, double beta1, double beta2,
+                      double eps, double weight_decay, double grad_scale, float* sqnorm_out, void* stream);
+/* Either law behind global-norm gradient clipping, torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) in front of
+ * optimizer.step(), with an optional skip of a step whose gradient norm is not finite; per-step scalars in device memory (hyper
+ * as above), so that an eager and a captured step can share it and the norm never visits the host.
+ *   sqnorm_in[0]    the COMPLETE squared norm of grad_scale g, written by a preceding wmz_grad_sqnorm on the same stream (every
+ *                   element needs it before the first update: it cannot ride in this pass);
+ *   max_norm        <= 0: no clipping;
+ *   decoupled       1: the AdamW law, 0: the Adam law above;
+ *   skip_nonfinite  != 0 and sqnorm_in[0] inf or NaN: nothing is written, p, m and v stay bit for bit.
+ * Every thread computes coef = min(1, max_norm / (sqrt(sq) + 1e-6)) in fp32 from the one loaded word and reads the gradient as
+ * fl(grad_scale coef) g; Adam's L2 term wd p is added after the clip (torch's optimizer adds it, not the clip).  With coef == 1
+ * (sq below max_norm^2, or max_norm <= 0) fl(grad_scale coef) IS grad_scale and the pass is the unclipped one's: the results are
+ * bit-identical to wmz_adamw_step_dev / wmz_adam_step_dev. */
+int wmz_optim_step_clipped_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, double beta1,
+                               double beta2, double eps, double weight_decay, double grad_scale, const float* sqnorm_in,
+                               double max_norm, int decoupled, int skip_nonfinite, void* stream);
 
 #ifdef __cplusplus
 }
