@@ -1,9 +1,11 @@
 """Micro-driver for profiling single kernels under rocprofv3 (not part of the product).
 
-    python3 tools/prof_kernels.py {fused|fused_infer|attn|attn_bwd|vq} N        config-4 shapes (65 536 tokens, dh 128, window 7x7x7)
+    python3 tools/prof_kernels.py {fused|fused_infer|attn|attn_infer|attn_infer_rt|attn_bwd|vq} N        config-4 shapes (65 536 tokens, dh 128, window 7x7x7)
 
 fused: the head + tail launch on row-major streams (the run-time kernel); fused_infer: on the tiled stream, as the inference step
-launches it (the inference unit, layer_fused_infer_kernel).
+launches it (the inference unit, layer_fused_infer_kernel).  attn: k | v the column halves of one buffer (row stride 256: the run-time
+row kernel); attn_infer: q, k, v with row stride 128, as the inference step launches it (the inference unit,
+attn_fwd_row16_infer_kernel); attn_infer_rt: the same launch kept on the run-time kernel by wmz_debug_attn_knobs(0, 1).
 """
 import sys
 import torch
@@ -24,6 +26,11 @@ layers = list(m.transformer.layers)
 q = torch.randn(8, 32, 16, 16, 128, device='cuda').bfloat16()
 kv = torch.randn(8, 32, 16, 16, 256, device='cuda').bfloat16()
 k, v = kv[..., :128], kv[..., 128:]
+if which in ('attn_infer', 'attn_infer_rt'):
+    k, v = k.contiguous(), v.contiguous()
+    if which == 'attn_infer_rt':
+        from world_modelz_amd import _lib
+        _lib.call('wmz_debug_attn_knobs', 0, 1)
 if which == 'attn_bwd':
     out, lse, _ = ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1, need_lse=True)
     dout = torch.randn_like(out)
@@ -35,7 +42,7 @@ for _ in range(int(sys.argv[2]) if len(sys.argv) > 2 else 5):
         fused.layer_fused(o, x, layers[0], layers[1])
     elif which == 'fused_infer':
         fused.layer_fused(o, x, layers[0], layers[1], xflags=3)
-    elif which == 'attn':
+    elif which in ('attn', 'attn_infer', 'attn_infer_rt'):
         ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1)
     elif which == 'attn_bwd':
         ops.local3d_attention_bwd(q, k, v, out, lse, dout, (3, 3, 3), 1)

@@ -251,6 +251,11 @@ int launch(const void* q, const void* k, const void* v, void* out, float* lse, f
 // fast path for 16-wide planes: one query row per wave (attn_fwd_row16.hip)
 int wmz_attn_fwd_row16_dispatch(const void* q, const void* k, const void* v, void* out, float* lse, float* dbg,
                                 const AttnGeom& G, hipStream_t st);
+// ... its inference unit (attn_fwd_row16_infer.hip: bf16, whole 16x16 planes, dim_head 128, one head, strides 128, extents 3,3 or
+// 1,1 in the plane, compiled without LSE / probe / stamps / ablations; same O bit for bit) and what decides the hand-over
+bool wmz_attn_fwd_row16_infer_takes(const AttnGeom& G);
+int wmz_attn_fwd_row16_infer_dispatch(const void* q, const void* k, const void* v, void* out, const AttnGeom& G, hipStream_t st);
+bool wmz_attn_fwd_row16_stamping();      // attn_fwd_row16.hip: a stamp buffer is set (wmz_debug_attn_timestamps)
 // ... and its IEEE-half instantiation (attn_fwd_row16_f16.hip: the precise fused mode, dtype WMZ_F16)
 int wmz_attn_fwd_row16_dispatch_f16(const void* q, const void* k, const void* v, void* out, float* lse, float* dbg,
                                     const AttnGeom& G, hipStream_t st);
@@ -313,6 +318,10 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* out,
   G.w8 = 0;
   hipStream_t st = (hipStream_t)stream;
   if (dtype != WMZ_F32 && (dh == 32 || dh == 64 || dh == 128) && !general) {
+    // the plain inference launch goes to the unit that has its geometry compiled in; wmz_debug_attn_knobs(0, 1) keeps it here
+    if (dtype == WMZ_BF16 && lse == nullptr && logits_dbg == nullptr && wmz_attn_fwd_row16_infer_takes(G) &&
+        !wmz_attn_fwd_row16_stamping())
+      return wmz_attn_fwd_row16_infer_dispatch(q, k, v, out, G, st);
     const auto row16 = dtype == WMZ_F16 ? wmz_attn_fwd_row16_dispatch_f16 : wmz_attn_fwd_row16_dispatch;
     if (W == 16) return row16(q, k, v, out, lse, logits_dbg, G, st);
     if (W == 8 && (H & 1) == 0) {

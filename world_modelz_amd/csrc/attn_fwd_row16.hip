@@ -558,6 +558,7 @@ int by_dh(const void* q, const void* k, const void* v, void* out, float* lse, fl
 // instantiation, which carries no stamp code at all.
 #if !defined(WMZ_OP16_F16) && !defined(WMZ_ATTN_ROW32)
 extern "C" int wmz_debug_attn_timestamps(void* buf) { g_attn_ts = (long long*)buf; return WMZ_OK; }
+bool wmz_attn_fwd_row16_stamping() { return g_attn_ts != nullptr; }      // attn_fwd_impl: such a launch stays on this unit
 #endif
 
 #ifndef WMZ_ATTN_MODE
