@@ -1,4 +1,5 @@
-"""Phase timeline of the row16 attention forward kernel (workgroup 0), from the s_memtime probe."""
+"""Phase timeline of the row16 attention forward kernel (workgroup 0), from the s_memtime probe: the run-time kernel's stamped
+instantiation, or -- with a -DWMZ_ATTN_INFER_TS build of attn_fwd_row16_infer.hip loaded through WMZ_LIB_PATH -- the inference unit."""
 import sys, torch
 sys.path.insert(0, '.')
 from world_modelz_amd import ops, _lib as L
@@ -12,10 +13,22 @@ ts = torch.zeros(16 * 64, dtype=torch.int64, device='cuda')
 for _ in range(3): ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1)
 L.call('wmz_debug_attn_knobs', DBG, 0)
 for _ in range(300): ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1)
-L.call('wmz_debug_attn_timestamps', ts.data_ptr())
-ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1)
-torch.cuda.synchronize()
-L.call('wmz_debug_attn_timestamps', None)
+if getattr(L.lib(), 'wmz_debug_attn_infer_stamps', None) is not None:
+    # a stamped build of the inference unit (tools/build_variant.py <tag> attn_fwd_row16_infer.hip -DWMZ_ATTN_INFER_TS, loaded through
+    # WMZ_LIB_PATH): the launch stays on the unit, whose workgroup 0 leaves the same slots in an array of its own
+    import ctypes, numpy as np
+    print('stamps of the inference unit (attn_fwd_row16_infer_kernel<3, 3>)')
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1)
+    torch.cuda.synchronize()
+    buf = (ctypes.c_ulonglong * (16 * 64))()
+    assert L.lib().wmz_debug_attn_infer_stamps(buf, 16 * 64) == 0
+    ts = torch.from_numpy(np.frombuffer(buf, dtype=np.uint64).astype(np.int64))
+else:
+    L.call('wmz_debug_attn_timestamps', ts.data_ptr())
+    ops.local3d_attention_fwd(q, k, v, (3, 3, 3), 1)
+    torch.cuda.synchronize()
+    L.call('wmz_debug_attn_timestamps', None)
 t = ts.cpu().view(16, 64)
 for w in (0, 8):
     dc, dr = int(t[w, 62] - t[w, 0]), int(t[w, 61] - t[w, 60])

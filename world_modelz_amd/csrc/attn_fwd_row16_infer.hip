@@ -11,6 +11,10 @@
 //   * per plane the K and V plane pointers take one 64-bit add each; the wrap of the rotated plane order is the trip index at
 //     which the pointers step back (t_wrap), known before the loop;
 //   * the slab behind the last one is never requested: the issue is predicated (`more`), nothing else is;
+//   * <3, 3> only: who owns a query row and who requests the next slab follow the work per slab (attn_slab_walk.h) -- wave w owns
+//     row slab_wave_row(w), so that no SIMD carries more than 13 key rows of a slab, and the nine lightest waves of a slab request
+//     the whole next one right behind the barrier, a class of pieces mod 9 each from ONE offset register; a wave with four key
+//     rows requests nothing (profiles/attn_issue_plan/README.md);
 //   * block -> (batch, query plane) and the rotated order's phase by the host's multipliers (div_m31), token indices in 32 bits:
 //     wmz_attn_fwd_row16_infer_takes bounds the launch accordingly.
 // Left at run time: B, S, eS, the query planes (qs0, Sq: the cone and the sampler pass trailing planes) and the pointers.
@@ -21,10 +25,34 @@
 #ifdef WMZ_OP16_F16
 #error "attn_fwd_row16_infer.hip is a bfloat16 unit"
 #endif
+// Two scheduling levers of the <3, 3> kernel (attn_slab_walk.h: slab_wave_row, slab_issue_class), each a switch so that one source
+// builds the A/B variants (tools/build_variant.py <tag> attn_fwd_row16_infer.hip -DWMZ_ATTN_ROWMAP=0 ...).  Neither enters O.
+#ifndef WMZ_ATTN_ROWMAP
+#define WMZ_ATTN_ROWMAP 1                                   // query row = slab_wave_row(wave) instead of wave
+#endif
+#ifndef WMZ_ATTN_PLAN
+#define WMZ_ATTN_PLAN 1                                     // the next slab is requested by the nine lightest waves of the current one
+#endif
+// Diagnostic build only (tools/build_variant.py <tag> attn_fwd_row16_infer.hip -DWMZ_ATTN_INFER_TS; never the product, whose listing
+// carries none of this): workgroup 0 stamps the shader clock per wave at the slots tools/ts_attn.py reads -- per slab j < 14 its own
+// pieces landed (3 + 4 j), through the barrier (4 + 4 j), requests issued (5 + 4 j), steps done (6 + 4 j) -- into a device array
+// that wmz_debug_attn_infer_stamps copies out.
+#ifdef WMZ_ATTN_INFER_TS
+__device__ unsigned long long attn_infer_stamps[16 * 64];
+#define WMZ_ITS(slot) do { if (blockIdx.x == 0 && lane == 0) attn_infer_stamps[wave * 64 + (slot)] = __builtin_readcyclecounter(); } while (0)
+#define WMZ_ITS_REAL(slot) do { if (blockIdx.x == 0 && lane == 0) attn_infer_stamps[wave * 64 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define WMZ_ITS_SLAB(k) do { if (its_j < 14) WMZ_ITS((k) + 4 * its_j); } while (0)
+#define WMZ_ITS_NEXT() (void)++its_j
+#else
+#define WMZ_ITS(slot) do { } while (0)
+#define WMZ_ITS_REAL(slot) do { } while (0)
+#define WMZ_ITS_SLAB(k) do { } while (0)
+#define WMZ_ITS_NEXT() do { } while (0)
+#endif
 
 namespace {
 
-constexpr int DH = 128, NW = 16, KCR = 8, RS = 2;          // dim_head, waves = query rows, rows per slab, row stride of a slab
+constexpr int DH = 128, NW = 16, KCR = 8, RS = 2;         // dim_head, waves = query rows, rows per slab, row stride of a slab
 constexpr int KROW = DH * 2 + 32, VROW = DH * 2 + 32;      // padded LDS rows (attn_fwd_row16.hip: Img)
 constexpr int KIMG = KCR * 16 * KROW, VIMG = KCR * 16 * VROW, BUF = KIMG + VIMG;
 constexpr int PK = KIMG / 1024, PV = VIMG / 1024;          // 1 KB DMA pieces per image: 36 and 36, a wave's are wave + 16 i
@@ -40,6 +68,22 @@ constexpr long PLANE_B = 256l * LD_B;                      // bytes per key plan
 __device__ __forceinline__ unsigned div_m31(unsigned n, unsigned m) { return __umulhi(n << 1, m); }
 unsigned magic_m31(unsigned d) { return (unsigned)(((1ull << 31) + d - 1) / d); }
 
+// The issue plan of attn_slab_walk.h by wave, as literals: a nibble per wave with its class of pieces (0 where it never issues), and
+// the waves that issue during the slab of parity `par`
+constexpr unsigned long issue_classes(bool rowmap) {
+  unsigned long t = 0;
+  for (int w = 0; w < NW; ++w) {
+    const int c = slab_issue_class(rowmap ? slab_wave_row(w) : w);
+    t |= (unsigned long)(c < 0 ? 0 : c) << (4 * w);
+  }
+  return t;
+}
+constexpr unsigned issuers(bool rowmap, int par) {
+  unsigned m = 0;
+  for (int w = 0; w < NW; ++w) m |= (unsigned)slab_issues(rowmap ? slab_wave_row(w) : w, par) << w;
+  return m;
+}
+
 template <int EH, int EW>
 __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                         const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
@@ -50,6 +94,10 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, li = lane & 15;
+#ifdef WMZ_ATTN_INFER_TS
+  int its_j = 0;                                        // slab index of the stamps
+#endif
+  WMZ_ITS(0); WMZ_ITS_REAL(60);
 
   // xcd_remap (wmz_common.h) without its branch: XCD x takes the logical ids from x q + min(x, r) on (q = grid / 8, r = grid % 8)
   const unsigned xcd = blockIdx.x & 7u;
@@ -57,7 +105,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
   const int b = (int)div_m31(lid, m_sq);                // lid / Sq
   const int sq = (int)(lid - (unsigned)b * (unsigned)Sq);
   const int s = qs0 + sq;
-  const int hq = wave;                                  // this wave's query row
+  constexpr bool ROWMAP = EH == 3 && WMZ_ATTN_ROWMAP, PLAN = EH == 3 && WMZ_ATTN_PLAN;
+  int hq = wave;                                        // this wave's query row
+  if constexpr (ROWMAP) hq = slab_wave_row(wave);       // ... spread so that no SIMD carries more than 13 key rows of a slab
   const unsigned tok_q = (unsigned)(b * S + s) * 256u + (unsigned)(hq * 16);     // first token of this wave's query row, of its output row
   const unsigned tok_o = lid * 256u + (unsigned)(hq * 16);                       // (32-bit token indices: the hand-over bounds them)
   const float c2 = scale * 1.4426950408889634f;
@@ -88,6 +138,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
   const bool has2 = wave + 2 * NW < PK;                 // this wave's third piece of either image exists
 
   // per-lane source offsets of the wave's DMA pieces (whole planes: they never change)
+  // (issue plan: only the first slab is requested this way; from then on a wave owns one class of pieces mod 9, both images from pvo)
   unsigned kvo[3], vvo[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) kvo[i] = piece_voff<DH, KROW, RS>(wave + NW * i, lane, LD_B, 16 - RS);
@@ -112,6 +163,24 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
   const long back = -(long)(nplanes - 1) * PLANE_B;
 
   int wdst = wave * 1024;                                // LDS offset of the wave's piece 0 of the K image of buffer 0
+  // issue plan: the wave's class of pieces (0 where it never issues), whether it issues during the slab of parity 0 / 1, its per-lane
+  // source offset (the K and the V image share row pitch and width, hence the offsets) and the LDS offset of its piece 0
+  static_assert(KROW == VROW, "one offset register serves both images");
+  int cdst = 0;
+  unsigned pvo = 0;
+  bool iss0 = false, iss1 = false;
+  if constexpr (PLAN) {
+    constexpr unsigned long CLS = issue_classes(ROWMAP);
+    constexpr unsigned ISS0 = issuers(ROWMAP, 0), ISS1 = issuers(ROWMAP, 1);
+    const int cls = (int)(CLS >> (4 * wave)) & 15;
+    iss0 = (ISS0 >> wave) & 1u; iss1 = (ISS1 >> wave) & 1u;
+    pvo = piece_voff<DH, KROW, RS>(cls, lane, LD_B, 16 - RS);
+    cdst = cls * 1024;
+  }
+  auto issue_c = [&](auto par, auto jc, int img, const char* p) {
+    constexpr int PAR = decltype(par)::value, j = decltype(jc)::value;
+    __builtin_amdgcn_global_load_lds((gptr_t)((p + PAR * ROW_B) + (pvo + j * SLAB_CLASS_STEP)), (lptr_t)(smem + cdst + PAR * BUF + img + j * 9 * 1024), 16, 0, 0);
+  };
   // request this wave's pieces of a slab: K image of parity PAR from kp, V image from vp, into LDS buffer PAR
   auto issue_k = [&](auto par, auto ic, const char* kp) {
     constexpr int PAR = decltype(par)::value, i = decltype(ic)::value;
@@ -233,19 +302,31 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
     }
   };
   // ---- one slab: buffer PAR holds parity PAR of the current plane; `more`: the next slab (parity 1 - PAR, of the plane kp / vp
-  // point at) is requested into the other buffer -- K behind the barrier, V inside the first step, the rest behind the last
+  // point at) is requested into the other buffer -- K behind the barrier, V inside the first step, the rest behind the last; under
+  // the issue plan K and V behind the barrier, by the waves that have fewer than four rows in this slab
   auto slab = [&](auto par, bool more, const char* kp, const char* vp) {
     constexpr int PAR = decltype(par)::value;
     using NX = std::integral_constant<int, 1 - PAR>;
     // (the offsets are taken afresh in every slab: hoisted out of the plane loop, the compiler keeps twelve more scalars for the
     //  destinations and widens the source offsets to register pairs, which costs the DMA its scalar-base + 32-bit-offset form)
-    asm volatile("" : "+s"(wdst), "+v"(kvo[0]), "+v"(kvo[1]), "+v"(kvo[2]), "+v"(vvo[0]), "+v"(vvo[1]), "+v"(vvo[2]));
+    if constexpr (PLAN) asm volatile("" : "+s"(cdst), "+v"(pvo));
+    else asm volatile("" : "+s"(wdst), "+v"(kvo[0]), "+v"(kvo[1]), "+v"(kvo[2]), "+v"(vvo[0]), "+v"(vvo[1]), "+v"(vvo[2]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's pieces of the slab landed
+    WMZ_ITS_SLAB(3);
     __builtin_amdgcn_s_barrier();                        // ... everyone's did, and the slab before is retired: refill its buffer
-    if (more) {
+    WMZ_ITS_SLAB(4);
+    if constexpr (PLAN) {
+      // a wave with fewer than four rows in this slab requests its class of the next one, K then V, before its own step; a wave
+      // with four rows requests nothing and starts computing at once
+      if (more && (PAR ? iss1 : iss0)) {
+        static_for<4>([&](auto j) { issue_c(NX{}, j, 0, kp); });
+        static_for<4>([&](auto j) { issue_c(NX{}, j, KIMG, vp); });
+      }
+    } else if (more) {
       issue_k(NX{}, C0{}, kp); issue_k(NX{}, C1{}, kp);
       if (has2) issue_k(NX{}, C2{}, kp);
     }
+    WMZ_ITS_SLAB(5);
     // the wave's rows lo .. hi of this slab: two a step from lo, an odd last row as the 16-key step.  Of the window's 2 EH + 1 rows no
     // fewer than EH + 1 lie in the plane, so a parity has (EH + 1) / 2 .. EH + 1 of them.
     const int lo = PAR ? lo1 : lo0, hi = PAR ? hi1 : hi0;
@@ -253,7 +334,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
       // 2 .. 4 rows: one or two two-row steps, the first of which carries the requests for V pieces 0 and 1.  (One copy of either
       // step per slab: a peeled first step would double the listing for the sake of two uniform branches.)
       int t0 = lo;
-      bool vnow = more;
+      bool vnow = more && !PLAN;
 #pragma clang loop unroll(disable)
       do { step2(par, t0, vnow, vp); vnow = false; t0 += 2; } while (t0 + 1 <= hi);
       if (t0 <= hi) step1(par, t0);
@@ -267,13 +348,15 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
       }
     }
     // whatever of the next slab has not been requested yet
-    if (more && has2) issue_v(NX{}, C2{}, vp);
+    if (!PLAN && more && has2) issue_v(NX{}, C2{}, vp);
+    WMZ_ITS_SLAB(6); WMZ_ITS_NEXT();
   };
 
   // the first slab is requested up front
   issue_k(C0{}, C0{}, kpl); issue_k(C0{}, C1{}, kpl);
   issue_v(C0{}, C0{}, vpl); issue_v(C0{}, C1{}, vpl);
   if (has2) { issue_k(C0{}, C2{}, kpl); issue_v(C0{}, C2{}, vpl); }
+  WMZ_ITS(2);
   {
     // Q right behind the first slab's requests
     const bf16_t* qrow = Q + (unsigned long)tok_q * 128ul + (unsigned)(li * 128);
@@ -290,6 +373,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
     kpl += mv; vpl += mv;                                // the next plane of the rotated order
     slab(C1{}, t + 1 < nplanes, kpl, vpl);               // parity 1; requests parity 0 of the next plane, if there is one
   } while (++t < nplanes);
+  WMZ_ITS(63);
 
   {
     float l = wave_groups_sum(l_run);
@@ -311,6 +395,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
       *reinterpret_cast<i32x4*>(orow + col) = pk;
     }
   }
+  WMZ_ITS(62); WMZ_ITS_REAL(61);
 }
 
 template <int EH, int EW>
@@ -332,6 +417,12 @@ bool wmz_attn_fwd_row16_infer_takes(const AttnGeom& G) {
          ((G.eH == 3 && G.eW == 3) || (G.eH == 1 && G.eW == 1)) && G.dbg == 0 && G.variant == 0 && G.w8 == 0 &&
          (long)G.B * G.S * 256 <= (1l << 31) && (long)G.B * G.Sq * G.Sq <= (1l << 31) && ((long)G.S + G.eS) * (2l * G.eS + 1) <= (1l << 31);       // 32-bit tokens, div_m31's range
 }
+
+#ifdef WMZ_ATTN_INFER_TS
+extern "C" int wmz_debug_attn_infer_stamps(unsigned long long* out, int n) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(attn_infer_stamps), (size_t)n * sizeof(unsigned long long));
+}
+#endif
 
 int wmz_attn_fwd_row16_infer_dispatch(const void* q, const void* k, const void* v, void* out, const AttnGeom& G, hipStream_t st) {
   if (G.eH == 3) return launch_infer<3, 3>(q, k, v, out, G, st);

@@ -99,6 +99,32 @@ WMZ_HD bool w32_col_ok(int R, int c, int Rk, int ck, int eW) { const int d = w32
 // (reaching up to itself + 2 eH): the symmetric extent 2 eH covers every owner's rows; 2 eH + 1 would only stage one row more.
 WMZ_HD int w32_stage_extent(int eH) { return 2 * eH; }
 
+// ---- The whole-plane forward with one wave per query row (16 waves, H = 16, row extent 3, two parity slabs of 8 rows a plane:
+// attn_fwd_row16_infer.hip).  Which wave owns which query row, and which wave requests which DMA pieces of the next slab, enter no
+// result; they decide who waits for whom at the slab's barrier.  tests/attn_issue_plan_host.cpp checks what is promised here.
+//
+// Row map.  Waves w, w + 4, w + 8, w + 12 share a SIMD.  A query row's window holds 2, 3 or 4 key rows of a parity slab; with row =
+// wave the four SIMDs carry 11, 14, 11, 14 key rows of the even slab (14, 11, 14, 11 of the odd one).  Swapping the two waves of a
+// pair in every second group of four gives 12, 13, 12, 13 in both slabs -- in steps (two rows a step, an odd row half a step) 6,
+// 6.5, 6, 6.5 of 25, and since the sums are multiples of a half no map does better than 6.5.
+constexpr int slab_wave_row(int wave) { return wave ^ ((wave >> 2) & 1); }
+// key rows of parity `par` in the window [row - eH, row + eH] of a plane of H rows
+constexpr int slab_rows_of_parity(int row, int eH, int par, int H = 16) {
+  const int lo = row - eH > 0 ? row - eH : 0, hi = row + eH < H - 1 ? row + eH : H - 1;
+  return (hi - par + 2) / 2 - (lo - par + 1) / 2;
+}
+// Issue plan.  The 36 one-KB pieces of a slab image fall into 9 classes mod 9; nine pieces are 32 padded rows = two slab rows, so
+// the pieces c, c + 9, c + 18, c + 27 of a class are fetched from one per-lane offset plus 0, 1, 2, 3 times SLAB_CLASS_STEP (see
+// piece_voff) and land 9 KB apart.  While the slab of parity P is computed, class c of the K and of the V image of the NEXT slab is
+// requested by the one wave whose row has slab_issue_class(row) == c and fewer than four key rows in P: rows 0 .. 2 and 13 .. 15
+// (never four rows) serve both parities, rows 4, 6, 8 (three even rows) and 11, 9, 7 (three odd rows) one each, rows 3, 5, 10, 12
+// none.  A row keeps ONE class, hence one offset register, whichever parity it serves.
+constexpr unsigned SLAB_CLASS_STEP = 16384u;
+constexpr int slab_issue_class(int row) {
+  return row <= 2 ? row : row >= 13 ? row - 10 : (row == 4 || row == 11) ? 6 : (row == 6 || row == 9) ? 7 : (row == 7 || row == 8) ? 8 : -1;
+}
+constexpr bool slab_issues(int row, int par) { return slab_issue_class(row) >= 0 && slab_rows_of_parity(row, 3, par) < 4; }
+
 // Byte offset (inside a plane, relative to plane row `base`) of the 16 bytes this lane fetches for DMA piece `piece` of a padded
 // image (rows of ROWP bytes): the lane landing on (slab row, 16-byte chunk) fetches that chunk of plane row base + RS * (slab row
 // / 16), column slab row % 16; pad chunks fetch chunk 0 (never read).  `row_lim`: rows past the plane are redirected to the last

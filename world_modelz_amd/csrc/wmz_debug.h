@@ -45,6 +45,9 @@ int wmz_debug_stamp(void* buf, int slot, void* stream);
  * array out.  Exported by such builds only (tools/build_variant.py, tools/conv_stamps.py). */
 int wmz_debug_conv_stamps(unsigned long long* out, int n);
 int wmz_debug_w3_stamps(unsigned long long* out, int n);
+/* Likewise the per-wave slab stamps of the attention forward's inference unit (csrc/attn_fwd_row16_infer.hip, built with
+ * -DWMZ_ATTN_INFER_TS; 16 waves x 64 words in the slot layout of wmz_debug_attn_timestamps; tools/ts_attn.py). */
+int wmz_debug_attn_infer_stamps(unsigned long long* out, int n);
 
 #ifdef __cplusplus
 }
