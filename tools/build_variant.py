@@ -2,7 +2,6 @@
 other objects into tools/variants/libwmz_<tag>.so (load it with WMZ_LIB_PATH).
 
     python tools/build_variant.py <tag> <file.hip> -DWMZ_ATTN_ABL=7 [...]
-    python tools/build_variant.py rows attn_fwd_row16_infer.hip -DWMZ_ATTN_PLAN=0        (row map only; -DWMZ_ATTN_ROWMAP=0: issue plan only)
     python tools/build_variant.py ts attn_fwd_row16_infer.hip -DWMZ_ATTN_INFER_TS        (stamped unit for tools/ts_attn.py)
 """
 import os, subprocess, sys

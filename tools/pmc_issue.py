@@ -19,9 +19,9 @@ PASSES = [['SQ_VALU_MFMA_BUSY_CYCLES', 'SQ_BUSY_CYCLES', 'SQ_WAVE_CYCLES', 'GRBM
           ['SQ_INSTS_VALU', 'SQ_INSTS_LDS', 'SQ_INSTS_SALU', 'SQ_INSTS_VMEM'],
           ['SQ_INSTS_VALU_MFMA_MOPS_BF16', 'SQ_VALU_MFMA_COEXEC_CYCLES', 'SQ_LDS_BANK_CONFLICT', 'SQ_LDS_IDX_ACTIVE']]
 KERNELS = [   # key, prof_kernels.py driver, kernel-name substring, sources
-    ('attn_fwd_row16_kernel', 'attn', 'attn_fwd_row16_kernel', ['attn_fwd_row16.hip', 'attn_common.h', 'wmz_common.h']),
-    ('attn_fwd_row16_kernel, strides 128', 'attn_infer_rt', 'attn_fwd_row16_kernel', ['attn_fwd_row16.hip', 'attn_common.h', 'wmz_common.h']),
-    ('attn_fwd_row16_infer_kernel<3, 3>', 'attn_infer', 'attn_fwd_row16_infer_kernel<3, 3>', ['attn_fwd_row16_infer.hip', 'attn_common.h', 'wmz_common.h']),
+    ('attn_fwd_row16_kernel', 'attn', 'attn_fwd_row16_kernel', ['attn_fwd_row16.hip', 'attn_row16_step.h', 'attn_common.h', 'wmz_common.h']),
+    ('attn_fwd_row16_kernel, strides 128', 'attn_infer_rt', 'attn_fwd_row16_kernel', ['attn_fwd_row16.hip', 'attn_row16_step.h', 'attn_common.h', 'wmz_common.h']),
+    ('attn_fwd_row16_infer_kernel<3, 3>', 'attn_infer', 'attn_fwd_row16_infer_kernel<3, 3>', ['attn_fwd_row16_infer.hip', 'attn_row16_step.h', 'attn_common.h', 'wmz_common.h']),
     ('attn_bwd_row16_kernel<dq>', 'attn_bwd', 'attn_bwd_row16_kernel<128, 0', ['attn_bwd_row16.hip', 'attn_common.h', 'wmz_common.h']),
     ('attn_bwd_kvplane_kernel<dk|dv>', 'attn_bwd', 'attn_bwd_kvplane_kernel<128', ['attn_bwd_row16.hip', 'attn_common.h', 'wmz_common.h']),
     ('layer_fused_kernel<head,tail>', 'fused', 'layer_fused_kernel<256, 128, 256, true, true>', ['layer_fused.hip', 'fused_common.h', 'wmz_common.h']),

@@ -25,54 +25,13 @@
 //   * the LDS-DMA descriptors (per-lane source offsets of the wave's pieces) are computed once; per slab a piece costs
 //     one scalar base and one instruction, and the pieces are spread over the step instead of queueing at the texture
 //     addresser right behind the barrier (SPLIT).
-#include "attn_common.h"
+#include "attn_row16_step.h"
 #include "wmz_debug.h"
-
-// Compile-time ablations for timing experiments (tools/variants builds; results are garbage): bit 0 no LDS fragment reads,
-// bit 1 no softmax arithmetic, bit 2 no MFMAs, bit 3 no V staging, bit 4 no K staging, bit 5 no slab loop at all, bit 6 one key plane only,
-// bit 7 odd waves stage but do not compute.  0 in the product.
-#ifndef WMZ_ATTN_ABL
-#define WMZ_ATTN_ABL 0
-#endif
 
 namespace {
 
-template <typename A, typename B>
-__device__ __forceinline__ void mma16_abl(f32x4& acc, const A& a, const B& b) {
-  if constexpr (WMZ_ATTN_ABL & 4) { asm volatile("" :: "v"(a.v), "v"(b.v)); } else { mma16(acc, a, b); }
-}
-
 // development probes (the only process-wide state of the library, see include/wmz.h): stamp buffer and A/B knobs
 long long* g_attn_ts = nullptr;     // 16 waves x 64 int64, wmz_debug_attn_timestamps
-
-// Workgroup shapes.  A plane is cut into chunks of CH rows, a slab holds every RS-th row of a chunk (KC = CH / RS rows: plane
-// row = base + RS * slab row), two slabs (K and V images each) in LDS, one in flight.
-//   Big   (NW 16, CH 16, KC 8): a workgroup = 16 query rows = a whole 16x16 plane, two 74 KB slabs, one workgroup per CU;
-//   Small (NW  4, CH  4, KC 2): a workgroup = 4 query rows, two 18 KB slabs, four workgroups per CU -- planes of up to 8 tile rows
-//         (8-wide planes, below), where the big shape would run a quarter full and stage 8-row slabs holding 2 rows.
-// (Round 2 / 3 measured and dropped, now removed: 4-row slabs in a ring of four with three in flight, two 8-wave half-plane
-//  workgroups per CU, a two-query-rows-per-wave kernel on MFMA 32x32x16: all equal or slower.)
-template <int NW_, int CH_, int KC_> struct Shape {
-  static constexpr int NW = NW_, CH = CH_, KC = KC_, RS = CH_ / KC_, LOG_RS = RS == 2 ? 1 : (RS == 1 ? 0 : 2);
-  static_assert(KC_ * RS == CH_ && (1 << LOG_RS) == RS, "a slab is one phase of a chunk");
-};
-using Big = Shape<16, 16, 8>;
-using Small = Shape<4, 4, 2>;
-constexpr int NBUF = 2;               // LDS slab pair
-constexpr float DEFER = 8.f;          // log2 units
-
-template <int DH, typename SH> struct Img {
-#ifndef WMZ_ATTN_KPAD
-#define WMZ_ATTN_KPAD 32
-#endif
-  static constexpr int NW = SH::NW, KC = SH::KC;
-  static constexpr int KROW = DH * 2 + WMZ_ATTN_KPAD, VROW = DH * 2 + 32;
-  static constexpr int KIMG = KC * 16 * KROW, VIMG = KC * 16 * VROW;
-  static constexpr int BUF = KIMG + VIMG;
-  static constexpr int PK = KIMG / 1024, PV = VIMG / 1024;            // 1 KB DMA pieces per image
-  static constexpr int NPK = (PK + NW - 1) / NW, NPV = (PV + NW - 1) / NW;   // ... per wave
-  static_assert(KIMG % 1024 == 0 && VIMG % 1024 == 0, "images must be whole 1 KB DMA pieces");
-};
 
 // Issue points of the next slab's LDS-DMA pieces inside a slab iteration: 0 = right behind the barrier, 1 = behind the
 // first step's QK^T MFMAs, 2 = behind its softmax, 3 = behind its PV MFMAs, 4 = after the wave's last step.  A wave has up
@@ -348,140 +307,42 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
     }
     if (act && !(G.dbg & 1)) {
       int t0 = lo;
-      for (; t0 + 1 <= hi; t0 += 2) {
-        // ---- S^T = K Q^T for key rows t0, t0 + 1
-        const int ko = kbase + t0 * 16 * I::KROW;
-        const unsigned va0 = lds_addr(Sb + vbase + t0 * 16 * I::VROW), va1 = va0 + 16 * I::VROW;
-        f32x4 sc0 = (f32x4)(0.f), sc1 = (f32x4)(0.f);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          Frag8<bf16_t> ka, kb;
-          if constexpr (WMZ_ATTN_ABL & 1) { ka.v = qf[ks].v; kb.v = qf[ks].v; }
-          else {
-            ka.v = *reinterpret_cast<const s16x8*>(Sb + ko + ks * 64);
-            kb.v = *reinterpret_cast<const s16x8*>(Sb + ko + 16 * I::KROW + ks * 64);
-          }
-          mma16_abl(sc0, ka, qf[ks]);
-          mma16_abl(sc1, kb, qf[ks]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- V^T fragments requested now: their LDS latency runs under the softmax
-        s16x4 x0[MT], x1[MT];
-        if constexpr (WMZ_ATTN_ABL & 1) {
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) { x0[mt] = (s16x4)((short)va0); x1[mt] = (s16x4)((short)va1); }
-        } else {
-          static_for<MT>([&](auto mt) {
-            x0[mt] = ds_read_tr16_asm<mt * 32>(va0);
-            x1[mt] = ds_read_tr16_asm<mt * 32>(va1);
-          });
-        }
-        issue_at(C1{}, false);
-        if constexpr (PROBE) {
-          const int kw = (2 * G.eW + 1), kh = (2 * G.eH + 1);
-          const long qn = plane_o + hq * 16 + li;
-          const int nk = (2 * G.eS + 1) * kh * kw;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int dw = W8 ? ((4 * g + r) & 7) - (li & 7) : (W32 ? w32_dw(hq, li, base, 4 * g + r) : 4 * g + r - li);
-            if (dw <= G.eW && -dw <= G.eW) {
-              const int ds = (sk_lo + pl) - s;
-              const int D0 = base + RS * t0 - hq;
-              const int dh0 = W8 ? 2 * D0 + dp : (W32 ? w32_dh(hq, base + RS * t0) : D0);
-              const int dh1 = W8 ? dh0 + 2 * RS : (W32 ? dh0 + RS / 2 : dh0 + RS);             // in plane rows
-              float* row = DBG + (qn * G.heads + head) * nk;
-              if (dh0 <= G.eH && -dh0 <= G.eH) row[((ds + G.eS) * kh + (dh0 + G.eH)) * kw + dw + G.eW] = sc0[r] * G.scale;
-              if (dh1 <= G.eH && -dh1 <= G.eH) row[((ds + G.eS) * kh + (dh1 + G.eH)) * kw + dw + G.eW] = sc1[r] * G.scale;
-            }
-          }
-        }
-        // ---- softmax: exponent of 2 by one fma per logit; deferred running max
-        float t[8];
+      // what this kernel supplies to the steps of attn_row16_step.h: the deferred-maximum vote, the logits probe of slab row t, the
+      // rim mask of 8-wide planes and the issue points of the next slab's pieces
+      auto hot = [&](float mx) { return first || __any(mx > DEFER); };
+      auto probe_row = [&](int t, const f32x4& sc) {
+        const int kw = (2 * G.eW + 1), kh = (2 * G.eH + 1);
+        const long qn = plane_o + hq * 16 + li;
+        const int nk = (2 * G.eS + 1) * kh * kw;
+        const int ds = (sk_lo + pl) - s;
+        const int D = base + RS * t - hq;
+        const int dh = W8 ? 2 * D + dp : (W32 ? w32_dh(hq, base + RS * t) : D);                  // in plane rows
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          t[r] = fmaf(sc0[r], c2, bm[r]);
-          t[4 + r] = fmaf(sc1[r], c2, bm[r]);
+          const int dw = W8 ? ((4 * g + r) & 7) - (li & 7) : (W32 ? w32_dw(hq, li, base, 4 * g + r) : 4 * g + r - li);
+          if (dw <= G.eW && -dw <= G.eW && dh <= G.eH && -dh <= G.eH)
+            DBG[(qn * G.heads + head) * nk + ((ds + G.eS) * kh + (dh + G.eH)) * kw + dw + G.eW] = sc[r] * G.scale;
         }
+      };
+      auto probe2 = [&](const f32x4& sc0, const f32x4& sc1) { if constexpr (PROBE) { probe_row(t0, sc0); probe_row(t0 + 1, sc1); } };
+      auto probe1 = [&](const f32x4& sc0) { if constexpr (PROBE) probe_row(t0, sc0); };
+      auto mask = [&](auto& t) {
         if constexpr (W8) {
           const int D0 = base + RS * t0 - hq;
           rim_mask(D0, t);
-          rim_mask(D0 + RS, t + 4);
+          if constexpr (sizeof(t) == 8 * sizeof(float)) rim_mask(D0 + RS, t + 4);
         }
-        const float mx = fmaxf(__builtin_fmaxf(__builtin_fmaxf(t[0], t[1]), __builtin_fmaxf(t[2], t[3])),
-                               __builtin_fmaxf(__builtin_fmaxf(t[4], t[5]), __builtin_fmaxf(t[6], t[7])));
-        if (first || __any(mx > DEFER)) rescale(mx, t);
-        float p[8];
-        Frag8<bf16_t> pf;
-        if constexpr (WMZ_ATTN_ABL & 2) {
-#pragma unroll
-          for (int r = 0; r < 8; ++r) pf.v[r] = (short)__builtin_bit_cast(int, sc0[r & 3]);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 8; ++r) p[r] = __builtin_amdgcn_exp2f(t[r]);
-          l_run += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-          frag_from_f32<bf16_t>(pf, p);
-        }
-        issue_at(C2{}, false);
-        // ---- O^T += V^T P^T
-        ds_tr_wait();
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          asm volatile("" : "+v"(x0[mt]), "+v"(x1[mt]));       // uses stay behind the wait
-          Frag8<bf16_t> vf;
-          vf.v = __builtin_shufflevector(x0[mt], x1[mt], 0, 1, 2, 3, 4, 5, 6, 7);
-          mma16_abl(o[mt], vf, pf);
-        }
-        issue_at(C3{}, false);
+      };
+      auto at = [&](auto pc) { issue_at(pc, false); };
+      for (; t0 + 1 <= hi; t0 += 2) {                        // key rows t0, t0 + 1
+        const int ko = kbase + t0 * 16 * I::KROW;
+        const unsigned va0 = lds_addr(Sb + vbase + t0 * 16 * I::VROW), va1 = va0 + 16 * I::VROW;
+        attn_step32<I::KROW>(Sb, ko, va0, va1, qf, o, bm, c2, l_run, hot, rescale, probe2, mask, at);
       }
-      if (t0 <= hi) {
-        // ---- odd last key row of the slab: a 16-key step
+      if (t0 <= hi) {                                        // odd last key row of the slab
         const int ko = kbase + t0 * 16 * I::KROW;
         const unsigned va0 = lds_addr(Sb + vbase + t0 * 16 * I::VROW);
-        f32x4 sc0 = (f32x4)(0.f);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          Frag8<bf16_t> ka;
-          ka.v = *reinterpret_cast<const s16x8*>(Sb + ko + ks * 64);
-          mma16(sc0, ka, qf[ks]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        s16x4 x0[MT];
-        static_for<MT>([&](auto mt) { x0[mt] = ds_read_tr16_asm<mt * 32>(va0); });
-        if constexpr (PROBE) {
-          const int kw = (2 * G.eW + 1), kh = (2 * G.eH + 1);
-          const long qn = plane_o + hq * 16 + li;
-          const int nk = (2 * G.eS + 1) * kh * kw;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int dw = W8 ? ((4 * g + r) & 7) - (li & 7) : (W32 ? w32_dw(hq, li, base, 4 * g + r) : 4 * g + r - li);
-            if (dw <= G.eW && -dw <= G.eW) {
-              const int ds = (sk_lo + pl) - s;
-              const int D0 = base + RS * t0 - hq;
-              const int dh0 = W8 ? 2 * D0 + dp : (W32 ? w32_dh(hq, base + RS * t0) : D0);
-              if (dh0 <= G.eH && -dh0 <= G.eH)
-                DBG[(qn * G.heads + head) * nk + ((ds + G.eS) * kh + (dh0 + G.eH)) * kw + dw + G.eW] = sc0[r] * G.scale;
-            }
-          }
-        }
-        float t[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) t[r] = fmaf(sc0[r], c2, bm[r]);
-        if constexpr (W8) rim_mask(base + RS * t0 - hq, t);
-        const float mx = __builtin_fmaxf(__builtin_fmaxf(t[0], t[1]), __builtin_fmaxf(t[2], t[3]));
-        if (first || __any(mx > DEFER)) rescale(mx, t);
-        float p[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) p[r] = __builtin_amdgcn_exp2f(t[r]);
-        l_run += (p[0] + p[1]) + (p[2] + p[3]);
-        s16x4 pf;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pf[r] = (short)f32_to_bf16_bits(p[r]);
-        ds_tr_wait();
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          asm volatile("" : "+v"(x0[mt]));
-          o[mt] = op16_mfma_16x16x16(x0[mt], pf, o[mt]);
-        }
+        attn_step16(Sb, ko, va0, qf, o, bm, c2, l_run, hot, rescale, probe1, mask);
       }
     }
     // whatever of slab j + 1 has not been requested yet
@@ -499,21 +360,7 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
     const float inv = 1.f / l;
     bf16_t* orow = O + (plane_o + hq * 16 + li) * G.ldo + (long)head * DH;
     if constexpr (EPI16) {
-      // lane (g, li) holds dh 16 mt + 4g .. +3 of query li; lanes g and g ^ 1 swap halves of an (mt, mt + 1) pair, so that the
-      // even lane owns dh 16 mt + 4g .. +7 and the odd lane dh 16 (mt + 1) + 4 (g - 1) .. +7: one 16-byte store each
-#pragma unroll
-      for (int mt = 0; mt < MT; mt += 2) {
-        unsigned a0 = (unsigned)f32_to_bf16_bits(o[mt][0] * inv) | ((unsigned)f32_to_bf16_bits(o[mt][1] * inv) << 16);
-        unsigned a1 = (unsigned)f32_to_bf16_bits(o[mt][2] * inv) | ((unsigned)f32_to_bf16_bits(o[mt][3] * inv) << 16);
-        unsigned b0 = (unsigned)f32_to_bf16_bits(o[mt + 1][0] * inv) | ((unsigned)f32_to_bf16_bits(o[mt + 1][1] * inv) << 16);
-        unsigned b1 = (unsigned)f32_to_bf16_bits(o[mt + 1][2] * inv) | ((unsigned)f32_to_bf16_bits(o[mt + 1][3] * inv) << 16);
-        const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);     // odd rows of a <-> even rows of b
-        const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-        i32x4 pk;
-        pk[0] = (int)s0[0]; pk[1] = (int)s1[0]; pk[2] = (int)s0[1]; pk[3] = (int)s1[1];
-        const int col = (g & 1) ? (mt + 1) * 16 + 4 * (g - 1) : mt * 16 + 4 * g;
-        *reinterpret_cast<i32x4*>(orow + col) = pk;
-      }
+      WMZ_ATTN_STORE_EPI16(o, inv, orow, g);
     } else {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {

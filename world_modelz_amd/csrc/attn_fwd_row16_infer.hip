@@ -1,7 +1,8 @@
 // Inference unit of the row16 attention forward (attn_fwd_row16.hip): the launch of the denoising step -- bf16, whole 16x16 planes,
 // dim_head 128, one head, every row stride 128, no LSE / probe / stamps / ablations -- with the slab walk decided at compile time.
-// Same algorithm, same arithmetic expressions in the same order as attn_fwd_row16_kernel<128, Big, 9, true, ...>: O is bit-identical
-// (tests/test_attn_infer_unit_gpu.py compares the two routes; wmz_debug_attn_knobs(0, 1) keeps a launch on the run-time kernel).
+// Same algorithm as attn_fwd_row16_kernel<128, Big, 9, true, ...> and the same step bodies, slab images and epilogue, which both take
+// from attn_row16_step.h: O is bit-identical (tests/test_attn_infer_unit_gpu.py compares the two routes; wmz_debug_attn_knobs(0, 1)
+// keeps a launch on the run-time kernel).
 //
 // What the geometry fixes (H = W = 16, 16 waves, one chunk of 16 rows, two parity slabs of 8 rows per key plane):
 //   * slab parity == LDS buffer: the walk is a loop over the workgroup's key planes whose body is the two slabs written out, every
@@ -20,18 +21,10 @@
 // Left at run time: B, S, eS, the query planes (qs0, Sq: the cone and the sampler pass trailing planes) and the pointers.
 // Measurements, the listing's instruction counts and what was tried: profiles/attn_infer_unit/README.md.
 // bfloat16 only: no *_f16.hip unit includes this file.
-#include "attn_common.h"
+#include "attn_row16_step.h"
 
 #ifdef WMZ_OP16_F16
 #error "attn_fwd_row16_infer.hip is a bfloat16 unit"
-#endif
-// Two scheduling levers of the <3, 3> kernel (attn_slab_walk.h: slab_wave_row, slab_issue_class), each a switch so that one source
-// builds the A/B variants (tools/build_variant.py <tag> attn_fwd_row16_infer.hip -DWMZ_ATTN_ROWMAP=0 ...).  Neither enters O.
-#ifndef WMZ_ATTN_ROWMAP
-#define WMZ_ATTN_ROWMAP 1                                   // query row = slab_wave_row(wave) instead of wave
-#endif
-#ifndef WMZ_ATTN_PLAN
-#define WMZ_ATTN_PLAN 1                                     // the next slab is requested by the nine lightest waves of the current one
 #endif
 // Diagnostic build only (tools/build_variant.py <tag> attn_fwd_row16_infer.hip -DWMZ_ATTN_INFER_TS; never the product, whose listing
 // carries none of this): workgroup 0 stamps the shader clock per wave at the slots tools/ts_attn.py reads -- per slab j < 14 its own
@@ -52,13 +45,10 @@ __device__ unsigned long long attn_infer_stamps[16 * 64];
 
 namespace {
 
-constexpr int DH = 128, NW = 16, KCR = 8, RS = 2;         // dim_head, waves = query rows, rows per slab, row stride of a slab
-constexpr int KROW = DH * 2 + 32, VROW = DH * 2 + 32;      // padded LDS rows (attn_fwd_row16.hip: Img)
-constexpr int KIMG = KCR * 16 * KROW, VIMG = KCR * 16 * VROW, BUF = KIMG + VIMG;
-constexpr int PK = KIMG / 1024, PV = VIMG / 1024;          // 1 KB DMA pieces per image: 36 and 36, a wave's are wave + 16 i
-static_assert(PK == 36 && PV == 36, "pieces 0 and 1 exist for every wave, piece 2 for waves 0 .. 3");
+constexpr int DH = 128, NW = Big::NW, KCR = Big::KC, RS = Big::RS;   // dim_head, waves = query rows, rows per slab, row stride of a slab
+using I = Img<DH, Big>;                                    // padded LDS slab images; 1 KB DMA pieces, a wave's are wave + 16 i
+static_assert(I::PK == 36 && I::PV == 36, "pieces 0 and 1 exist for every wave, piece 2 for waves 0 .. 3");
 constexpr int KS = DH / 32, MT = DH / 16;
-constexpr float DEFER = 8.f;                               // log2 units
 constexpr unsigned LD_B = 128u * 2u;                       // bytes per token row of q, k, v, o
 constexpr unsigned ROW_B = 16u * LD_B;                     // bytes per plane row of 16 keys
 constexpr long PLANE_B = 256l * LD_B;                      // bytes per key plane
@@ -70,17 +60,17 @@ unsigned magic_m31(unsigned d) { return (unsigned)(((1ull << 31) + d - 1) / d); 
 
 // The issue plan of attn_slab_walk.h by wave, as literals: a nibble per wave with its class of pieces (0 where it never issues), and
 // the waves that issue during the slab of parity `par`
-constexpr unsigned long issue_classes(bool rowmap) {
+constexpr unsigned long issue_classes() {
   unsigned long t = 0;
   for (int w = 0; w < NW; ++w) {
-    const int c = slab_issue_class(rowmap ? slab_wave_row(w) : w);
+    const int c = slab_issue_class(slab_wave_row(w));
     t |= (unsigned long)(c < 0 ? 0 : c) << (4 * w);
   }
   return t;
 }
-constexpr unsigned issuers(bool rowmap, int par) {
+constexpr unsigned issuers(int par) {
   unsigned m = 0;
-  for (int w = 0; w < NW; ++w) m |= (unsigned)slab_issues(rowmap ? slab_wave_row(w) : w, par) << w;
+  for (int w = 0; w < NW; ++w) m |= (unsigned)slab_issues(slab_wave_row(w), par) << w;
   return m;
 }
 
@@ -90,7 +80,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
                                                                         int S, int eS, int qs0, int Sq, float scale,
                                                                         unsigned m_sq, unsigned m_win) {
   static_assert(EH == 3 || EH == 1, "the steps of a slab are written out for these row extents");
-  __shared__ __attribute__((aligned(1024))) char smem[2 * BUF];
+  __shared__ __attribute__((aligned(1024))) char smem[2 * I::BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, li = lane & 15;
@@ -105,9 +95,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
   const int b = (int)div_m31(lid, m_sq);                // lid / Sq
   const int sq = (int)(lid - (unsigned)b * (unsigned)Sq);
   const int s = qs0 + sq;
-  constexpr bool ROWMAP = EH == 3 && WMZ_ATTN_ROWMAP, PLAN = EH == 3 && WMZ_ATTN_PLAN;
+  constexpr bool PLAN = EH == 3;                        // <3, 3>: row map and issue plan of attn_slab_walk.h
   int hq = wave;                                        // this wave's query row
-  if constexpr (ROWMAP) hq = slab_wave_row(wave);       // ... spread so that no SIMD carries more than 13 key rows of a slab
+  if constexpr (PLAN) hq = slab_wave_row(wave);         // ... spread so that no SIMD carries more than 13 key rows of a slab
   const unsigned tok_q = (unsigned)(b * S + s) * 256u + (unsigned)(hq * 16);     // first token of this wave's query row, of its output row
   const unsigned tok_o = lid * 256u + (unsigned)(hq * 16);                       // (32-bit token indices: the hand-over bounds them)
   const float c2 = scale * 1.4426950408889634f;
@@ -129,21 +119,21 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
   // very first step, whatever the logits: until then the threshold is -inf (wave-uniform; a step always holds a finite logit)
   float thr = -INFINITY;
 
-  const int kbase = li * KROW + g * 16;
-  const int vbase = KIMG + (4 * g + (li >> 2)) * VROW + (li & 3) * 8;
+  const int kbase = li * I::KROW + g * 16;
+  const int vbase = I::KIMG + (4 * g + (li >> 2)) * I::VROW + (li & 3) * 8;
   // slab rows this wave needs, per parity (slab row r of parity p is plane row p + 2 r)
   const int my_lo = max(hq - EH, 0), my_hi = min(hq + EH, 15);
   const int lo0 = max(0, (my_lo + RS - 1) >> 1), hi0 = min(KCR - 1, my_hi >> 1);
   const int lo1 = max(0, (my_lo - 1 + RS - 1) >> 1), hi1 = min(KCR - 1, (my_hi - 1) >> 1);
-  const bool has2 = wave + 2 * NW < PK;                 // this wave's third piece of either image exists
+  const bool has2 = wave + 2 * NW < I::PK;              // this wave's third piece of either image exists
 
   // per-lane source offsets of the wave's DMA pieces (whole planes: they never change)
   // (issue plan: only the first slab is requested this way; from then on a wave owns one class of pieces mod 9, both images from pvo)
   unsigned kvo[3], vvo[3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) kvo[i] = piece_voff<DH, KROW, RS>(wave + NW * i, lane, LD_B, 16 - RS);
+  for (int i = 0; i < 3; ++i) kvo[i] = piece_voff<DH, I::KROW, RS>(wave + NW * i, lane, LD_B, 16 - RS);
 #pragma unroll
-  for (int i = 0; i < 3; ++i) vvo[i] = piece_voff<DH, VROW, RS>(wave + NW * i, lane, LD_B, 16 - RS);
+  for (int i = 0; i < 3; ++i) vvo[i] = piece_voff<DH, I::VROW, RS>(wave + NW * i, lane, LD_B, 16 - RS);
 
   // key planes in the rotated order of attn_slab_walk.h (slab_first_plane): from p_first up to the window's last plane, then from
   // its first one up to p_first - 1
@@ -165,30 +155,30 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
   int wdst = wave * 1024;                                // LDS offset of the wave's piece 0 of the K image of buffer 0
   // issue plan: the wave's class of pieces (0 where it never issues), whether it issues during the slab of parity 0 / 1, its per-lane
   // source offset (the K and the V image share row pitch and width, hence the offsets) and the LDS offset of its piece 0
-  static_assert(KROW == VROW, "one offset register serves both images");
+  static_assert(I::KROW == I::VROW, "one offset register serves both images");
   int cdst = 0;
   unsigned pvo = 0;
   bool iss0 = false, iss1 = false;
   if constexpr (PLAN) {
-    constexpr unsigned long CLS = issue_classes(ROWMAP);
-    constexpr unsigned ISS0 = issuers(ROWMAP, 0), ISS1 = issuers(ROWMAP, 1);
+    constexpr unsigned long CLS = issue_classes();
+    constexpr unsigned ISS0 = issuers(0), ISS1 = issuers(1);
     const int cls = (int)(CLS >> (4 * wave)) & 15;
     iss0 = (ISS0 >> wave) & 1u; iss1 = (ISS1 >> wave) & 1u;
-    pvo = piece_voff<DH, KROW, RS>(cls, lane, LD_B, 16 - RS);
+    pvo = piece_voff<DH, I::KROW, RS>(cls, lane, LD_B, 16 - RS);
     cdst = cls * 1024;
   }
   auto issue_c = [&](auto par, auto jc, int img, const char* p) {
     constexpr int PAR = decltype(par)::value, j = decltype(jc)::value;
-    __builtin_amdgcn_global_load_lds((gptr_t)((p + PAR * ROW_B) + (pvo + j * SLAB_CLASS_STEP)), (lptr_t)(smem + cdst + PAR * BUF + img + j * 9 * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gptr_t)((p + PAR * ROW_B) + (pvo + j * SLAB_CLASS_STEP)), (lptr_t)(smem + cdst + PAR * I::BUF + img + j * 9 * 1024), 16, 0, 0);
   };
   // request this wave's pieces of a slab: K image of parity PAR from kp, V image from vp, into LDS buffer PAR
   auto issue_k = [&](auto par, auto ic, const char* kp) {
     constexpr int PAR = decltype(par)::value, i = decltype(ic)::value;
-    __builtin_amdgcn_global_load_lds((gptr_t)((kp + PAR * ROW_B) + kvo[i]), (lptr_t)(smem + wdst + PAR * BUF + i * NW * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gptr_t)((kp + PAR * ROW_B) + kvo[i]), (lptr_t)(smem + wdst + PAR * I::BUF + i * NW * 1024), 16, 0, 0);
   };
   auto issue_v = [&](auto par, auto ic, const char* vp) {
     constexpr int PAR = decltype(par)::value, i = decltype(ic)::value;
-    __builtin_amdgcn_global_load_lds((gptr_t)((vp + PAR * ROW_B) + vvo[i]), (lptr_t)(smem + wdst + PAR * BUF + KIMG + i * NW * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gptr_t)((vp + PAR * ROW_B) + vvo[i]), (lptr_t)(smem + wdst + PAR * I::BUF + I::KIMG + i * NW * 1024), 16, 0, 0);
   };
   using C0 = std::integral_constant<int, 0>;
   using C1 = std::integral_constant<int, 1>;
@@ -213,97 +203,31 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
     for (int r = 0; r < nt; ++r) t[r] -= gm;
   };
 
-  // ---- two key rows (slab rows t0, t0 + 1 of buffer PAR): 32 keys.  vnow: this is the wave's first step of the slab and carries the
+  auto hot = [&](float mx) { return __any(mx > thr); };
+  // ---- two key rows (slab rows t0, t0 + 1 of buffer PAR): 32 keys.  vnow (<1, 1>): this is the wave's step of the slab and carries the
   // requests for V pieces 0 and 1 of the next slab (schedule 1 of attn_fwd_row16.hip: behind the QK^T MFMAs and behind the softmax)
   auto step2 = [&](auto par, int t0, bool vnow, const char* vp) {
     constexpr int PAR = decltype(par)::value;
     using NX = std::integral_constant<int, 1 - PAR>;
-    const char* Sb = smem + PAR * BUF;
-    // ---- S^T = K Q^T for key rows t0, t0 + 1
-    const int ko = kbase + t0 * 16 * KROW;
-    const unsigned va0 = lds_addr(Sb + vbase + t0 * 16 * VROW), va1 = va0 + 16 * VROW;
-    f32x4 sc0 = (f32x4)(0.f), sc1 = (f32x4)(0.f);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      Frag8<bf16_t> ka, kb;
-      ka.v = *reinterpret_cast<const s16x8*>(Sb + ko + ks * 64);
-      kb.v = *reinterpret_cast<const s16x8*>(Sb + ko + 16 * KROW + ks * 64);
-      mma16(sc0, ka, qf[ks]);
-      mma16(sc1, kb, qf[ks]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- V^T fragments requested now: their LDS latency runs under the softmax
-    s16x4 x0[MT], x1[MT];
-    static_for<MT>([&](auto mt) {
-      x0[mt] = ds_read_tr16_asm<mt * 32>(va0);
-      x1[mt] = ds_read_tr16_asm<mt * 32>(va1);
+    const char* Sb = smem + PAR * I::BUF;
+    const int ko = kbase + t0 * 16 * I::KROW;
+    const unsigned va0 = lds_addr(Sb + vbase + t0 * 16 * I::VROW), va1 = va0 + 16 * I::VROW;
+    attn_step32<I::KROW>(Sb, ko, va0, va1, qf, o, bm, c2, l_run, hot, rescale, StepNop{}, StepNop{}, [&](auto pc) {
+      constexpr int pt = decltype(pc)::value;
+      if constexpr (pt <= 2) { if (vnow) issue_v(NX{}, std::integral_constant<int, pt - 1>{}, vp); }
     });
-    if (vnow) issue_v(NX{}, C0{}, vp);
-    // ---- softmax: exponent of 2 by one fma per logit; deferred running max
-    float t[8];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      t[r] = fmaf(sc0[r], c2, bm[r]);
-      t[4 + r] = fmaf(sc1[r], c2, bm[r]);
-    }
-    const float mx = fmaxf(__builtin_fmaxf(__builtin_fmaxf(t[0], t[1]), __builtin_fmaxf(t[2], t[3])),
-                           __builtin_fmaxf(__builtin_fmaxf(t[4], t[5]), __builtin_fmaxf(t[6], t[7])));
-    if (__any(mx > thr)) rescale(mx, t);
-    float p[8];
-    Frag8<bf16_t> pf;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) p[r] = __builtin_amdgcn_exp2f(t[r]);
-    l_run += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-    frag_from_f32<bf16_t>(pf, p);
-    if (vnow) issue_v(NX{}, C1{}, vp);
-    // ---- O^T += V^T P^T
-    ds_tr_wait();
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      asm volatile("" : "+v"(x0[mt]), "+v"(x1[mt]));       // uses stay behind the wait
-      Frag8<bf16_t> vf;
-      vf.v = __builtin_shufflevector(x0[mt], x1[mt], 0, 1, 2, 3, 4, 5, 6, 7);
-      mma16(o[mt], vf, pf);
-    }
   };
   // ---- odd last key row of the slab: a 16-key step
   auto step1 = [&](auto par, int t0) {
     constexpr int PAR = decltype(par)::value;
-    const char* Sb = smem + PAR * BUF;
-    const int ko = kbase + t0 * 16 * KROW;
-    const unsigned va0 = lds_addr(Sb + vbase + t0 * 16 * VROW);
-    f32x4 sc0 = (f32x4)(0.f);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      Frag8<bf16_t> ka;
-      ka.v = *reinterpret_cast<const s16x8*>(Sb + ko + ks * 64);
-      mma16(sc0, ka, qf[ks]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    s16x4 x0[MT];
-    static_for<MT>([&](auto mt) { x0[mt] = ds_read_tr16_asm<mt * 32>(va0); });
-    float t[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) t[r] = fmaf(sc0[r], c2, bm[r]);
-    const float mx = __builtin_fmaxf(__builtin_fmaxf(t[0], t[1]), __builtin_fmaxf(t[2], t[3]));
-    if (__any(mx > thr)) rescale(mx, t);
-    float p[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[r] = __builtin_amdgcn_exp2f(t[r]);
-    l_run += (p[0] + p[1]) + (p[2] + p[3]);
-    s16x4 pf;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) pf[r] = (short)f32_to_bf16_bits(p[r]);
-    ds_tr_wait();
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      asm volatile("" : "+v"(x0[mt]));
-      o[mt] = op16_mfma_16x16x16(x0[mt], pf, o[mt]);
-    }
+    const char* Sb = smem + PAR * I::BUF;
+    const int ko = kbase + t0 * 16 * I::KROW;
+    const unsigned va0 = lds_addr(Sb + vbase + t0 * 16 * I::VROW);
+    attn_step16(Sb, ko, va0, qf, o, bm, c2, l_run, hot, rescale, StepNop{}, StepNop{});
   };
   // ---- one slab: buffer PAR holds parity PAR of the current plane; `more`: the next slab (parity 1 - PAR, of the plane kp / vp
-  // point at) is requested into the other buffer -- K behind the barrier, V inside the first step, the rest behind the last; under
-  // the issue plan K and V behind the barrier, by the waves that have fewer than four rows in this slab
+  // point at) is requested into the other buffer -- <1, 1>: K behind the barrier, V inside the step, the rest behind it; <3, 3>,
+  // the issue plan: K and V behind the barrier, by the waves that have fewer than four rows in this slab
   auto slab = [&](auto par, bool more, const char* kp, const char* vp) {
     constexpr int PAR = decltype(par)::value;
     using NX = std::integral_constant<int, 1 - PAR>;
@@ -320,7 +244,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
       // with four rows requests nothing and starts computing at once
       if (more && (PAR ? iss1 : iss0)) {
         static_for<4>([&](auto j) { issue_c(NX{}, j, 0, kp); });
-        static_for<4>([&](auto j) { issue_c(NX{}, j, KIMG, vp); });
+        static_for<4>([&](auto j) { issue_c(NX{}, j, I::KIMG, vp); });
       }
     } else if (more) {
       issue_k(NX{}, C0{}, kp); issue_k(NX{}, C1{}, kp);
@@ -331,12 +255,11 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
     // fewer than EH + 1 lie in the plane, so a parity has (EH + 1) / 2 .. EH + 1 of them.
     const int lo = PAR ? lo1 : lo0, hi = PAR ? hi1 : hi0;
     if constexpr (EH == 3) {
-      // 2 .. 4 rows: one or two two-row steps, the first of which carries the requests for V pieces 0 and 1.  (One copy of either
-      // step per slab: a peeled first step would double the listing for the sake of two uniform branches.)
+      // 2 .. 4 rows: one or two two-row steps, none of which carries a request.  (One copy of either step per slab: a peeled first
+      // step would double the listing for the sake of two uniform branches.)
       int t0 = lo;
-      bool vnow = more && !PLAN;
 #pragma clang loop unroll(disable)
-      do { step2(par, t0, vnow, vp); vnow = false; t0 += 2; } while (t0 + 1 <= hi);
+      do { step2(par, t0, false, vp); t0 += 2; } while (t0 + 1 <= hi);
       if (t0 <= hi) step1(par, t0);
     } else {
       // 1 or 2 rows: one step; what the odd one does not carry goes out behind it
@@ -346,9 +269,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
         step1(par, t0);
         if (more) { issue_v(NX{}, C0{}, vp); issue_v(NX{}, C1{}, vp); }
       }
+      // whatever of the next slab has not been requested yet
+      if (more && has2) issue_v(NX{}, C2{}, vp);
     }
-    // whatever of the next slab has not been requested yet
-    if (!PLAN && more && has2) issue_v(NX{}, C2{}, vp);
     WMZ_ITS_SLAB(6); WMZ_ITS_NEXT();
   };
 
@@ -379,21 +302,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_row16_infer_kernel(const 
     float l = wave_groups_sum(l_run);
     const float inv = 1.f / l;
     bf16_t* orow = O + (unsigned long)tok_o * 128ul + (unsigned)(li * 128);
-    // lane (g, li) holds dh 16 mt + 4g .. +3 of query li; lanes g and g ^ 1 swap halves of an (mt, mt + 1) pair, so that the
-    // even lane owns dh 16 mt + 4g .. +7 and the odd lane dh 16 (mt + 1) + 4 (g - 1) .. +7: one 16-byte store each
-#pragma unroll
-    for (int mt = 0; mt < MT; mt += 2) {
-      unsigned a0 = (unsigned)f32_to_bf16_bits(o[mt][0] * inv) | ((unsigned)f32_to_bf16_bits(o[mt][1] * inv) << 16);
-      unsigned a1 = (unsigned)f32_to_bf16_bits(o[mt][2] * inv) | ((unsigned)f32_to_bf16_bits(o[mt][3] * inv) << 16);
-      unsigned b0 = (unsigned)f32_to_bf16_bits(o[mt + 1][0] * inv) | ((unsigned)f32_to_bf16_bits(o[mt + 1][1] * inv) << 16);
-      unsigned b1 = (unsigned)f32_to_bf16_bits(o[mt + 1][2] * inv) | ((unsigned)f32_to_bf16_bits(o[mt + 1][3] * inv) << 16);
-      const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);     // odd rows of a <-> even rows of b
-      const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-      i32x4 pk;
-      pk[0] = (int)s0[0]; pk[1] = (int)s1[0]; pk[2] = (int)s0[1]; pk[3] = (int)s1[1];
-      const int col = (g & 1) ? (mt + 1) * 16 + 4 * (g - 1) : mt * 16 + 4 * g;
-      *reinterpret_cast<i32x4*>(orow + col) = pk;
-    }
+    WMZ_ATTN_STORE_EPI16(o, inv, orow, g);
   }
   WMZ_ITS(62); WMZ_ITS_REAL(61);
 }
