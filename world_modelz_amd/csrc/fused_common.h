@@ -2,6 +2,7 @@
 // weight ring, the register-chained GEMM stage, operand packing, LDS-staged row I/O, lane-local LayerNorm.
 #pragma once
 #include "wmz_common.h"
+#include "mem_policy.h"
 #include <stdlib.h>
 
 // Compiler + scheduler fence: neither IR passes (memory clobber) nor the machine scheduler (sched_barrier) may move
@@ -305,7 +306,9 @@ __device__ __forceinline__ void load_bop_tiled(Frag8<bf16_t> (&bop)[KS], const b
 }
 // (WHOLE, here and in the row I/O below: the caller vouches for whole 256-token workgroups, so `tile` / the row base is
 //  wave-uniform and every row exists -- 32-bit per-lane byte offsets from that scalar base, no guards, no clamps)
-template <int KS, bool WHOLE = false>
+// (POL, here and in the row stores below: the cache policy of the global stores, mem_policy.h -- plain unless the caller names
+//  another, which only whole workgroups can: the written-through store takes the scalar base)
+template <int KS, bool WHOLE = false, MemPolicy POL = MemPolicy::Plain>
 __device__ __forceinline__ void store_bop_tiled(bf16_t* tile, const Frag8<bf16_t> (&bop)[KS], int lane, HalfGuard& hg) {
   if (hg.on()) {
 #pragma unroll
@@ -315,8 +318,9 @@ __device__ __forceinline__ void store_bop_tiled(bf16_t* tile, const Frag8<bf16_t
   if constexpr (WHOLE) {
 #pragma unroll
     for (int s = 0; s < KS; ++s)
-      *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(tile) + (unsigned)(s * 1024 + lane * 16)) = bop[s].v;
+      gstore_at<POL>(reinterpret_cast<char*>(tile), (unsigned)((s >> 2) * 4096 + lane * 16), (s & 3) * 1024, bop[s].v);
   } else {
+    static_assert(WHOLE || POL == MemPolicy::Plain, "a policy needs whole workgroups");
 #pragma unroll
     for (int s = 0; s < KS; ++s) *reinterpret_cast<s16x8*>(tile + (s * 64 + lane) * 8) = bop[s].v;
   }
@@ -354,11 +358,12 @@ __device__ __forceinline__ void stage_put(char* stg, const s16x8& v, int t, int 
   *reinterpret_cast<s16x8*>(stg + t * 256 + ((c ^ (t & 15)) << 4)) = v;
 }
 // copy the 8 KB image out: row r of the image -> dst + (tok0 + r) * ROWF + col0, 128 features (256 B) per row
-template <int ROWF, bool WHOLE = false>
+template <int ROWF, bool WHOLE = false, MemPolicy POL = MemPolicy::Plain>
 __device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long tok0, int ntok, int col0, int lane, HalfGuard& hg,
                                             unsigned kind) {
   asm volatile("" : "+s"(tok0), "+v"(lane));   // compute the store addresses HERE (hoisted / shared with the prologue's
                                                // index math they only get spilled)
+  static_assert(WHOLE || POL == MemPolicy::Plain, "a policy needs whole workgroups");
   // all eight LDS reads first, unconditionally, then the predicated stores: with the read inside the predicate hipcc
   // emits branch / read / wait / store per KB, eight LDS round trips in a row
   s16x8 v[8];
@@ -374,7 +379,7 @@ __device__ __forceinline__ void stage_flush(const char* stg, bf16_t* dst, long t
     const int r = p * 4 + (lane >> 4), pc = lane & 15;
     const int c = pc ^ (r & 15);
     if constexpr (WHOLE)
-      *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(dst + tok0 * ROWF) + (unsigned)((r * ROWF + col0 + c * 8) * 2)) = v[p];
+      gstore_at<POL>(reinterpret_cast<char*>(dst + tok0 * ROWF), (unsigned)((r * ROWF + col0 + c * 8) * 2), 0, v[p]);
     else if (tok0 + r < ntok) *reinterpret_cast<s16x8*>(dst + (tok0 + r) * ROWF + col0 + c * 8) = v[p];
   }
 }
@@ -394,14 +399,14 @@ __device__ __forceinline__ Frag8<bf16_t> frag_unpark(const char* stg, int slot, 
 }
 
 // an I-feature tile (q, k, v: 128 features, every lane holds 8 chunks of its row): one pass
-template <bool WHOLE = false>
+template <bool WHOLE = false, MemPolicy POL = MemPolicy::Plain>
 __device__ __forceinline__ void store_tile128(char* stg, bf16_t* dst, int rowf, long tok0, int ntok, int col0,
                                               const Frag8<bf16_t> (&b)[8], int lane, HalfGuard& hg) {
   const int t = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int s = 0; s < 8; ++s) stage_put(stg, b[s].v, t, h * 8 + s);
-  if (rowf == 128) stage_flush<128, WHOLE>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
-  else stage_flush<256, WHOLE>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
+  if (rowf == 128) stage_flush<128, WHOLE, POL>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
+  else stage_flush<256, WHOLE, POL>(stg, dst, tok0, ntok, col0, lane, hg, WMZ_HG_QKV);
 }
 __device__ __forceinline__ void store_tile128(char* stg, bf16_t* dst, int rowf, long tok0, int ntok, int col0,
                                               const Frag8<bf16_t> (&b)[8], int lane) {

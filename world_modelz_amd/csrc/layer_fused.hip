@@ -73,6 +73,8 @@ struct OptRuntime {
   static constexpr bool kFixed = false;
   static constexpr int kXflags = 0;          // (unused: the layout is an argument)
   typedef WStreamT<false> Stream;
+  // cache policy of the stores by class (mem_policy.h) -- the tiled stream, q, k | v: plain
+  static constexpr MemPolicy kStX = MemPolicy::Plain, kStQ = MemPolicy::Plain, kStKV = MemPolicy::Plain;
   __device__ static __forceinline__ int xflags(const FusedParams& P) { return P.xflags; }
   __device__ static __forceinline__ bool embed(const FusedParams& P) { return P.z != nullptr; }
   template <typename T> __device__ static __forceinline__ T* train(T* p) { return p; }     // a training output (NULL = off)
@@ -95,6 +97,9 @@ struct OptInfer {
   static constexpr bool kFixed = true;
   static constexpr int kXflags = XFLAGS;
   typedef WStreamT<true> Stream;
+  // the tiled stream, q and k | v are read once, by the next launch, almost always on another XCD: written through (sc1).  The last
+  // layer's row-major stream stays plain: written through it measured no different (class by class: profiles/handoff_policy/README.md)
+  static constexpr MemPolicy kStX = MemPolicy::SC1, kStQ = MemPolicy::SC1, kStKV = MemPolicy::SC1;
   __device__ static __forceinline__ int xflags(const FusedParams&) { return XFLAGS; }
   __device__ static __forceinline__ bool embed(const FusedParams&) { return true; }
   template <typename T> __device__ static __forceinline__ T* train(T*) { return nullptr; }
@@ -381,7 +386,7 @@ __device__ __forceinline__ void layer_fused_body(const FusedParams& P) {
     }
     else bop_from_acc<D / 32>(x2b, xr);
     WMZ_TS(30);
-    if (xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16, WH>(P.xo + tok0 * D, x2b, lane, hg); }
+    if (xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16, WH, O::kStX>(P.xo + tok0 * D, x2b, lane, hg); }
     else store_tile256<WH>(stg, P.xo, tok0, P.ntok, x2b, lane, hg);
     ws_extra(ws, 16);
     if (xo_rm != nullptr) {          // training: the row-major copy for the backward -- x2 itself, or (WMZ_FUSED_XRM_NORMALISED)
@@ -414,7 +419,7 @@ __device__ __forceinline__ void layer_fused_body(const FusedParams& P) {
     for (int i = 0; i < 8 / FW; ++i) *reinterpret_cast<f32x4*>(vecs + (tid + i * NTHR) * 4) = vecv[i];
     __syncthreads();
     if (O::embed(P)) {
-      if (xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16, WH>(P.xo + tok0 * D, xb, lane, hg); }
+      if (xflags & WMZ_FUSED_X_OUT_TILED) { if (tile_ok) store_bop_tiled<D / 16, WH, O::kStX>(P.xo + tok0 * D, xb, lane, hg); }
       else store_tile256<WH>(stg, P.xo, tok0, P.ntok, xb, lane, hg);
       ws_extra(ws, 16);
       if (xo_rm != nullptr && !(xflags & WMZ_FUSED_XRM_NORMALISED)) { store_tile256(stg, xo_rm, tok0, P.ntok, xb, lane, hg); ws_extra(ws, 16); }
@@ -434,14 +439,14 @@ __device__ __forceinline__ void layer_fused_body(const FusedParams& P) {
     f32x16 ka[I / 32];
     Frag8<bf16_t> kb[I / 16];
     init_vec<I / 32>(ka, v_bk);
-    store_tile128<WH>(stg, P.q, I, tok0, P.ntok, 0, qkvb, lane, hg);     // q rows (as side work under the to_k MFMAs: slower)
+    store_tile128<WH, O::kStQ>(stg, P.q, I, tok0, P.ntok, 0, qkvb, lane, hg);     // q rows (as side work under the to_k MFMAs: slower)
     ws_extra(ws, 8);
     WMZ_TS(33);
     gemm_stage<I / 32, D / 16>(ka, xb, ring0, ws, lane);               // to_k
     WMZ_TS(34);
     bop_from_acc<I / 32>(kb, ka);
     if (O::kv_combined(P)) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, 0, kb, lane, hg);   // k | v column halves of [ntok, 2I]
-    else store_tile128<WH>(stg, P.kv, I, tok0, P.ntok, 0, kb, lane, hg);   // k rows
+    else store_tile128<WH, O::kStKV>(stg, P.kv, I, tok0, P.ntok, 0, kb, lane, hg);   // k rows
     ws_extra(ws, 8);
     init_vec<I / 32>(ka, v_bv);
     WMZ_TS(35);
@@ -449,7 +454,7 @@ __device__ __forceinline__ void layer_fused_body(const FusedParams& P) {
     WMZ_TS(36);
     bop_from_acc<I / 32>(kb, ka);
     if (O::kv_combined(P)) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, I, kb, lane, hg);
-    else store_tile128<WH>(stg, P.kv + (long)P.ntok * I, I, tok0, P.ntok, 0, kb, lane, hg);    // v rows, behind the k rows
+    else store_tile128<WH, O::kStKV>(stg, P.kv + (long)P.ntok * I, I, tok0, P.ntok, 0, kb, lane, hg);    // v rows, behind the k rows
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the padding slabs still in flight target this workgroup's LDS
   hg.commit();
