@@ -137,9 +137,9 @@ def test_header_declares_the_entry_points():
 
 
 def test_new_kernels_use_no_scratch():
-    """hipcc's resource report (tools/kres.py) of loss.hip: every scored instantiation of the two draw kernels and both forms of the
+    """hipcc's resource report (tools/kres.py) of sampler.hip: every scored instantiation of the two draw kernels and both forms of the
     selection kernel are there and spill nothing; nor does any other sampler kernel."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'kres.py'), os.path.join(ROOT, 'world_modelz_amd', 'csrc', 'loss.hip')],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'kres.py'), os.path.join(ROOT, 'world_modelz_amd', 'csrc', 'sampler.hip')],
                        capture_output=True, text=True)
     rows = {}
     for line in r.stdout.splitlines():
@@ -147,8 +147,8 @@ def test_new_kernels_use_no_scratch():
         t = line.split()
         rows[name] = int(t[t.index('scratch') + 1])
     assert rows, r.stdout + r.stderr                                        # (kres exits 1 when ANY kernel of the unit spills: not read here)
-    want = [f'sample_tokens_kernel<{nv}, {t}, {p}, SampleExtras, ScoreOut>' for nv in (4, 8, 16, 32) for t in ('false', 'true')
-            for p in ('false', 'true')] + ['sample_tokens_wide_kernel<ScoreOut>', 'remask_lowest_kernel<1>', 'remask_lowest_kernel<4>']
+    want = [f'sample_tokens_kernel<{nv}, {t}, {p}, true, ScoredDest>' for nv in (4, 8, 16, 32) for t in ('false', 'true')
+            for p in ('false', 'true')] + ['sample_tokens_wide_kernel<ScoredDest>', 'remask_lowest_kernel<1>', 'remask_lowest_kernel<4>']
     for name in want:
         assert name in rows, (name, sorted(rows))
         assert rows[name] == 0, name

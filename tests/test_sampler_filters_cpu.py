@@ -53,7 +53,7 @@ def test_top_p_logits_keeps_ties_at_the_boundary_and_p_one_is_the_identity():
 
 
 def test_the_class_limit_is_the_librarys():
-    """The widest codebook the sampler step takes is stated once, in loss.hip, and read from the library
+    """The widest codebook the sampler step takes is stated once, in sampler.hip, and read from the library
     (wmz_sample_tokens_max_classes): sample.py asks ops, and carries no copy of the number."""
     from world_modelz_amd import _lib, ops
     assert _lib.DECLARATIONS['wmz_sample_tokens_max_classes'] == (_lib.c_int, [])

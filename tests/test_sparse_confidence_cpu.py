@@ -176,14 +176,14 @@ def kres_rows(unit):
 def test_new_kernels_use_no_scratch():
     """hipcc's resource report (tools/kres.py): the scored variant of sparse_context_kernel spills nothing and asks for exactly the
     LDS of the form without a score, which is still there under its own name; every scored sparse instantiation of the two draw
-    kernels of loss.hip is there and spills nothing."""
+    kernels of sampler.hip is there and spills nothing."""
     ctx = kres_rows('sparse_context.hip')
-    assert 'sparse_context_kernel<>' in ctx and 'sparse_context_kernel<ScScore>' in ctx, sorted(ctx)
-    assert ctx['sparse_context_kernel<ScScore>']['scratch'] == 0 and ctx['sparse_context_kernel<>']['scratch'] == 0
-    assert ctx['sparse_context_kernel<ScScore>']['lds'] == ctx['sparse_context_kernel<>']['lds']
-    loss = kres_rows('loss.hip')
-    want = [f'sample_tokens_kernel<{nv}, {t}, {p}, SampleExtras, WmzSparseOut, WmzSparseScore>' for nv in (4, 8, 16, 32)
-            for t in ('false', 'true') for p in ('false', 'true')] + ['sample_tokens_wide_kernel<WmzSparseOut, WmzSparseScore>']
+    assert 'sparse_context_kernel<false>' in ctx and 'sparse_context_kernel<true>' in ctx, sorted(ctx)
+    assert ctx['sparse_context_kernel<true>']['scratch'] == 0 and ctx['sparse_context_kernel<false>']['scratch'] == 0
+    assert ctx['sparse_context_kernel<true>']['lds'] == ctx['sparse_context_kernel<false>']['lds']
+    loss = kres_rows('sampler.hip')
+    want = [f'sample_tokens_kernel<{nv}, {t}, {p}, true, SparseScoredDest>' for nv in (4, 8, 16, 32)
+            for t in ('false', 'true') for p in ('false', 'true')] + ['sample_tokens_wide_kernel<SparseScoredDest>']
     for name in want:
         assert name in loss, (name, sorted(loss))
         assert loss[name]['scratch'] == 0, name

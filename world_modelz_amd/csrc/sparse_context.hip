@@ -18,23 +18,26 @@
 //   * indices, gathered tokens (targets) and their corrupted copies are written from the sorted prefix.
 // Deterministic in (seed, stream id, device counter): a hipGraph replay with the counter advanced draws a fresh context.
 //
-// The scored form (wmz_sparse_draw_context_scored; include/wmz.h states the law), a compile-time variant -- one ScScore behind the
-// ScParams --: the sampler's masking ordered by confidence instead of a coin per slot.  Everything up to the sorted prefix is the
-// same code reading the same Philox words; the last phase differs.  Slot i = thread i (n <= 512) gathers its position's score
+// The scored form (wmz_sparse_draw_context_scored; include/wmz.h states the law), a compile-time variant -- SCORED, which reads the
+// ScScore at the end of the ScParams --: the sampler's masking ordered by confidence instead of a coin per slot.  Everything up to
+// the sorted prefix is the same code reading the same Philox words; the last phase differs.  Slot i = thread i (n <= 512) gathers its position's score
 // (+ the annealed Gumbel term from the very uniform the coin rule compares with r) and leaves its key and candidate flag in LDS --
 // in the words of `hist`, which is dead behind the scan: the variant adds no LDS --; wave 0 then holds all <= 512 keys in 8
 // registers a lane and runs wmz_select_lowest (wmz_select.h: 32 search steps of 8 ballots, no barrier, no memory access -- the
 // one-wave form of remask_lowest_kernel); two barriers around it, and every slot writes its token.
 #include "wmz_common.h"
-#include "wmz_internal.h"
 #include "wmz_philox.h"
 #include "wmz_select.h"
 
 namespace {
 
 constexpr int SC_THREADS = 1024;
-constexpr unsigned long long SC_KEY_DOMAIN = 1ull << 63;      // stream-id bits that separate the three uses of the generator
-constexpr unsigned long long SC_WIN_DOMAIN = 1ull << 62;      // (rank sits in bits 40.., the per-call counter in bits 0..39)
+
+struct ScScore {
+  const float* scores; long stride;                 // [B, S * HW] fp32, addressed like z: the score of the token drawn there
+  float noise;
+  float* slot_scores;                               // optional probe [B, n]: the score each slot was ranked by
+};
 
 struct ScParams {
   const int64_t* z; long clip_stride;
@@ -45,29 +48,21 @@ struct ScParams {
   unsigned long long seed, stream;
   const unsigned long long* counter;
   const unsigned char* known; long known_stride;   // optional bytes [B, S * HW]: a non-zero position is given -- gathered as it is
-};
-
-struct ScScore {
-  const float* scores; long stride;                 // [B, S * HW] fp32, addressed like z: the score of the token drawn there
-  float noise;
-  float* slot_scores;                               // optional probe [B, n]: the score each slot was ranked by
+  ScScore score;                                   // the scored form's: not read when !SCORED
 };
 
 constexpr int SC_BINS = 2048, SC_CAND = 1024;
 constexpr int SC_SLOTS = 512;                       // context positions at the most (wmz_sparse_draw_context_supported)
 
-template <typename... Score>
-__global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P, Score... score) {
-  static_assert(sizeof...(Score) <= 1, "one ScScore at the most");
-  constexpr bool SCORED = sizeof...(Score) == 1;
+template <bool SCORED>
+__global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P) {
   __shared__ unsigned hist[SC_BINS];
   __shared__ unsigned long long cand[SC_CAND];                 // packed (key << 32 | position inside the window)
   __shared__ unsigned wave_tot[SC_THREADS / 64];
   __shared__ int win[2];
   __shared__ unsigned sel[2];                                  // the bin of the n-th smallest key; candidates taken so far
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long stream = P.stream;
-  if (P.counter != nullptr) stream |= *P.counter & ((1ull << 40) - 1);
+  const unsigned long long stream = philox_stream(P.stream, P.counter);
   if (tid == 0) {
     // the window (sparse_diffusion.py:53-64), in the reference's fp32 arithmetic
     const float t = fminf(fmaxf(P.r[b], 0.f), 1.f);
@@ -78,7 +73,7 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P, 
     if (P.o != nullptr) o = fminf(fmaxf(P.o[b], 0.f), 1.f - 1e-5f);
     else {
       unsigned c[4];
-      philox4((unsigned long long)b, stream | SC_WIN_DOMAIN, P.seed, c);
+      philox4((unsigned long long)b, stream | PHILOX_WIN_DOMAIN, P.seed, c);
       o = philox_unit(c[0]);
     }
     const float first = floorf(o * ((float)P.S - frames + 1.f));
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P, 
   // ---- pass 1: histogram of the keys' top 11 bits
   for (int q = tid; q < nq; q += SC_THREADS) {
     unsigned c[4];
-    philox4(kbase + q, stream | SC_KEY_DOMAIN, P.seed, c);
+    philox4(kbase + q, stream | PHILOX_KEY_DOMAIN, P.seed, c);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (4 * q + e < Wn) atomicAdd(&hist[c[e] >> 21], 1u);
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P, 
   // ---- pass 2: the candidates (every key up to that bin: >= n of them, <= n + one bin's worth), regenerated and compacted
   for (int q = tid; q < nq; q += SC_THREADS) {
     unsigned c[4];
-    philox4(kbase + q, stream | SC_KEY_DOMAIN, P.seed, c);
+    philox4(kbase + q, stream | PHILOX_KEY_DOMAIN, P.seed, c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int i = 4 * q + e;
@@ -151,7 +146,7 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P, 
   // ---- the n smallest: positions, targets, corrupted tokens (the law and the stream layout of corrupt_kernel, loss.hip)
   const float rb = P.r[b];
   if constexpr (SCORED) {
-    const ScScore X = (score, ...);
+    const ScScore& X = P.score;
     static_assert(2 * SC_SLOTS <= SC_BINS && SC_SLOTS % 64 == 0 && SC_SLOTS <= SC_THREADS, "keys and flags of every slot fit the histogram's words");
     unsigned* skey = hist;                                     // [SC_SLOTS] the slot's key; 0xFFFFFFFF: no candidate / past n
     unsigned* sflag = hist + SC_SLOTS;                         // [SC_SLOTS] in: candidate; out: masked
@@ -218,51 +213,6 @@ __global__ __launch_bounds__(SC_THREADS) void sparse_context_kernel(ScParams P, 
   }
 }
 
-// The other end of config 5's sampler step (sparse_diffusion.py:190-198): p = softmax(logits), one multinomial draw per row,
-// scattered back into the clip at the row's position.  One wave per row of C fp32 logits (C = 8192 at config 5: too wide for
-// registers, so three passes over the row, which sits in L2): the maximum, the sum of exp(l - max), then the inverse CDF in class
-// order -- the first class whose cumulative weight exceeds u * total (lane l owns the contiguous classes [l C / 64, (l + 1) C / 64):
-// lane sums -> a wave prefix -> the owning lane walks its classes).
-__global__ __launch_bounds__(256) void categorical_scatter_kernel(const float* __restrict__ logits, long ld, long R, int C,
-                                                                  WmzSparseOut out, unsigned long long seed) {
-  const unsigned long long stream = wmz_sparse_stream(out);
-  const int lane = threadIdx.x & 63;
-  const int per = (C + 63) / 64, c0 = lane * per, c1 = min(c0 + per, C);
-  for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < R; row += (long)gridDim.x * 4) {
-    const float* x = logits + row * ld;
-    float m = -INFINITY;
-    for (int c = c0; c < c1; ++c) m = fmaxf(m, x[c]);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) m = fmaxf(m, __shfl_xor(m, d));
-    float s = 0.f;
-    for (int c = c0; c < c1; ++c) s += __expf(x[c] - m);
-    float incl = s;                                             // inclusive prefix of the lane sums
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const float up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    const float total = __shfl(incl, 63);
-    unsigned cc[4];
-    philox4((unsigned long long)row, stream, seed, cc);
-    const float want = philox_unit(cc[0]) * total;
-    // the owning lane: the first whose inclusive prefix exceeds `want` (the last lane if rounding leaves none)
-    const unsigned long long owners = __ballot(incl > want);
-    const int owner = owners ? (int)__builtin_ctzll(owners) : 63;
-    int pick = C - 1;
-    if (lane == owner) {
-      float acc = incl - s;
-      pick = c1 - 1 < 0 ? 0 : c1 - 1;
-      for (int c = c0; c < c1; ++c) {
-        acc += __expf(x[c] - m);
-        if (acc > want) { pick = c; break; }
-      }
-    }
-    pick = __shfl(pick, owner);
-    if (lane == 0) wmz_sparse_write(out, row, pick);
-  }
-}
-
 }  // namespace
 
 // 1 when wmz_sparse_draw_context holds the shape: n <= 512 context positions of a grid of <= 65 536 (the candidates -- n plus one
@@ -305,14 +255,14 @@ static int sparse_context_launch(const int64_t* z, long clip_stride, const float
   while (np < S * HW) np <<= 1;
   P.NP = np;
   P.seed = seed;
-  P.stream = counter != nullptr ? (stream_id & ~((1ull << 40) - 1)) : stream_id;
-  P.stream &= ~(SC_KEY_DOMAIN | SC_WIN_DOMAIN);
+  P.stream = philox_stream_base(stream_id, counter != nullptr) & ~(PHILOX_KEY_DOMAIN | PHILOX_WIN_DOMAIN);
   P.counter = counter;
   P.known = known; P.known_stride = known_stride;
+  P.score = score != nullptr ? *score : ScScore{};
   if (score == nullptr)
-    hipLaunchKernelGGL(sparse_context_kernel<>, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P);
+    hipLaunchKernelGGL(sparse_context_kernel<false>, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P);
   else
-    hipLaunchKernelGGL(sparse_context_kernel<ScScore>, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P, *score);
+    hipLaunchKernelGGL(sparse_context_kernel<true>, dim3(B), dim3(SC_THREADS), 0, (hipStream_t)stream, P);
   WMZ_LAUNCH_CHECK("wmz_sparse_draw_context");
   return WMZ_OK;
 }
@@ -341,75 +291,4 @@ extern "C" int wmz_sparse_draw_context_scored(const int64_t* z, long clip_stride
   const ScScore score = {scores, scores_stride, noise, slot_scores};
   return sparse_context_launch(z, clip_stride, r, o, indices, tokens, target, B, S, HW, n, C, p_uniform, seed, stream_id, counter, stream,
                                known, known_stride, &score);
-}
-
-// One multinomial draw per row of fp32 logits [R, C] (row stride ld) from softmax(logits) -- sparse_diffusion.py:190-194 -- and,
-// with z != NULL, its scatter into the clips (:197): z[row / rows_per_clip][indices[row]] = the drawn class.  samples (optional):
-// the draws [R].  Philox keyed as wmz_sparse_draw_context.
-extern "C" int wmz_categorical_scatter(const float* logits, long ld, long R, int C, const int64_t* indices, int64_t* z,
-                                       long clip_stride, long rows_per_clip, int64_t* samples, unsigned long long seed,
-                                       unsigned long long stream_id, const unsigned long long* counter, void* stream) {
-  return wmz_categorical_scatter_filtered(logits, ld, R, C, -1, 1.f, 1.f, indices, z, clip_stride, rows_per_clip, samples, nullptr, 0,
-                                          nullptr, nullptr, seed, stream_id, counter, stream);
-}
-
-// The same with a temperature, top-k, a nucleus and given positions (include/wmz.h states the law).  Neutral filters and no probe:
-// categorical_scatter_kernel, the three passes over the global row at any C and any alignment -- the draws of the entry point
-// above.  Else the two row bodies of wmz_sample_tokens_filtered_dev (loss.hip) with this sampler's uniform and destination.
-static int categorical_scatter_launch(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
-                                      const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip, int64_t* samples,
-                                      const unsigned char* known, long known_stride, const float* uniforms, float* kept_floor,
-                                      unsigned long long seed, unsigned long long stream_id, const unsigned long long* counter,
-                                      void* stream, const WmzSparseScore* score) {
-  WMZ_REQUIRE(logits && R > 0 && C > 0 && ld >= C, "wmz_categorical_scatter: bad arguments");
-  WMZ_REQUIRE(z == nullptr || (indices != nullptr && rows_per_clip > 0), "wmz_categorical_scatter: the scatter needs indices and rows_per_clip");
-  WMZ_REQUIRE(z != nullptr || samples != nullptr, "wmz_categorical_scatter: nothing to write");
-  WMZ_REQUIRE(inv_temperature > 0.f && inv_temperature < INFINITY,
-              "wmz_categorical_scatter_filtered: inv_temperature must be positive and finite (got %g)", (double)inv_temperature);
-  WMZ_REQUIRE(top_p > 0.f, "wmz_categorical_scatter_filtered: top_p must be positive (got %g)", (double)top_p);
-  const unsigned long long sid = (counter != nullptr ? (stream_id & ~((1ull << 40) - 1)) : stream_id) & ~(SC_KEY_DOMAIN | SC_WIN_DOMAIN);
-  const WmzSparseOut out = {indices, z, clip_stride, rows_per_clip, samples, z != nullptr ? known : nullptr, known_stride,
-                            sid | (SC_KEY_DOMAIN | SC_WIN_DOMAIN), counter};
-  const bool neutral = !(top_k > 0 && top_k < C) && !(top_p < 1.f) && inv_temperature == 1.f && uniforms == nullptr && kept_floor == nullptr &&
-                       score == nullptr;
-  if (neutral) {
-    const int grid = (int)((R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048);
-    hipLaunchKernelGGL(categorical_scatter_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, R, C, out, seed);
-    WMZ_LAUNCH_CHECK("wmz_categorical_scatter");
-    return WMZ_OK;
-  }
-  if (C > wmz_sample_tokens_max_classes()) {
-    wmz_set_error("wmz_categorical_scatter_filtered: filters are built for <= %d classes (got %d)", wmz_sample_tokens_max_classes(), C);
-    return WMZ_ERR_UNSUPPORTED;
-  }
-  WMZ_REQUIRE(ld % 4 == 0 && (((uintptr_t)logits) & 15) == 0, "wmz_categorical_scatter_filtered: logits rows must be 16-byte aligned");
-  WMZ_REQUIRE(R <= 0x7fffffffL, "wmz_categorical_scatter_filtered: more than 2^31 - 1 rows");
-  return wmz_sparse_sample_launch("wmz_categorical_scatter_filtered", logits, ld, (int)R, C, top_k, top_p, inv_temperature, uniforms,
-                                  kept_floor, seed, out, (hipStream_t)stream, score);
-}
-
-extern "C" int wmz_categorical_scatter_filtered(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
-                                                const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip,
-                                                int64_t* samples, const unsigned char* known, long known_stride,
-                                                const float* uniforms, float* kept_floor, unsigned long long seed,
-                                                unsigned long long stream_id, const unsigned long long* counter, void* stream) {
-  return categorical_scatter_launch(logits, ld, R, C, top_k, top_p, inv_temperature, indices, z, clip_stride, rows_per_clip, samples, known,
-                                    known_stride, uniforms, kept_floor, seed, stream_id, counter, stream, nullptr);
-}
-
-// The same draw with the score of every draw written beside its token (include/wmz.h states the law): `scores` counts as a probe,
-// so the row-read-once kernels run whatever the filters are.
-extern "C" int wmz_categorical_scatter_scored(const float* logits, long ld, long R, int C, int top_k, float top_p, float inv_temperature,
-                                              const int64_t* indices, int64_t* z, long clip_stride, long rows_per_clip,
-                                              int64_t* samples, const unsigned char* known, long known_stride,
-                                              const float* uniforms, float* kept_floor, unsigned long long seed,
-                                              unsigned long long stream_id, const unsigned long long* counter, void* stream,
-                                              float* scores, long scores_stride) {
-  if (scores == nullptr)
-    return wmz_categorical_scatter_filtered(logits, ld, R, C, top_k, top_p, inv_temperature, indices, z, clip_stride, rows_per_clip, samples,
-                                            known, known_stride, uniforms, kept_floor, seed, stream_id, counter, stream);
-  WMZ_REQUIRE(z != nullptr, "wmz_categorical_scatter_scored: a score is written where a token is: z expected");
-  const WmzSparseScore score = {scores, scores_stride};
-  return categorical_scatter_launch(logits, ld, R, C, top_k, top_p, inv_temperature, indices, z, clip_stride, rows_per_clip, samples, known,
-                                    known_stride, uniforms, kept_floor, seed, stream_id, counter, stream, &score);
 }

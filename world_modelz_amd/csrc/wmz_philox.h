@@ -1,5 +1,6 @@
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC 2011), stated once: the generator of the
-// token corruption, the sampler step (loss.hip) and the sparse context draw and its categorical sampler (sparse_context.hip).  The
+// token corruption (loss.hip), the sampler step and config 5's categorical sampler (sampler.hip) and the sparse context draw
+// (sparse_context.hip).  The
 // trainers and sample.py build their stream ids on the three drawing from ONE generator.  Plain integer code without HIP types:
 // tests/philox_host.cpp runs it on the host and tests/test_philox_cpu.py checks its words against the published algorithm.
 #pragma once
@@ -39,4 +40,18 @@ WMZ_HD void philox4_unit(unsigned long long idx, unsigned long long stream, unsi
   unsigned c[4];
   philox4(idx, stream, seed, c);
   for (int i = 0; i < 4; ++i) u[i] = philox_unit(c[i]);
+}
+
+// The layout of a stream id: the rank from bit 40 up, the per-call counter in bits 0..39, and in bits 62 and 63 the domain that
+// separates config 5's uses of the generator (none: a context slot's corruption words; KEY: the position keys; WIN: the window
+// offset; both: the categorical sampler's rows).
+constexpr unsigned long long PHILOX_KEY_DOMAIN = 1ull << 63, PHILOX_WIN_DOMAIN = 1ull << 62;
+constexpr unsigned long long PHILOX_COUNTER_BITS = (1ull << 40) - 1;
+// the id a launch hands its kernel: with a device counter, its bits cleared for ...
+WMZ_HD unsigned long long philox_stream_base(unsigned long long stream_id, bool has_counter) {
+  return has_counter ? stream_id & ~PHILOX_COUNTER_BITS : stream_id;
+}
+// ... the kernel to or the low 40 bits of *counter in (counter != NULL: the per-call id lives in device memory, hipGraph replay)
+WMZ_HD unsigned long long philox_stream(unsigned long long stream, const unsigned long long* counter) {
+  return counter != nullptr ? stream | (*counter & PHILOX_COUNTER_BITS) : stream;
 }

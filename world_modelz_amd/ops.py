@@ -310,6 +310,20 @@ def sample_max_classes():
     return L.lib().wmz_sample_tokens_max_classes()
 
 
+def _sample_step_args(logits, top_k, alphas, last_frame, denoised, counter, seed, uniforms, kept_floor):
+    """What the entry points of the dense sampler step share: the checks of their tensors and the argument groups
+    (logits and top-k, alphas, destination, probes, seed .. stream) in the order include/wmz.h declares them."""
+    R, C = logits.shape
+    B = last_frame.shape[0]
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and last_frame.dtype == torch.int64
+    assert last_frame[0].is_contiguous() and R % B == 0 and denoised.numel() == R and counter.dtype == torch.int64
+    assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.shape == (R, 2))
+    assert kept_floor is None or (kept_floor.dtype == torch.float32 and kept_floor.is_contiguous() and kept_floor.numel() == R)
+    return ((L.ptr(logits), logits.stride(0), R, C, int(top_k)), (L.ptr(alphas), alphas.numel()),
+            (L.ptr(last_frame), R // B, last_frame.stride(0), L.ptr(denoised)), (L.ptr(uniforms), L.ptr(kept_floor)),
+            (int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream()))
+
+
 def sample_tokens(logits, top_k, alphas, mask_token, last_frame, denoised, counter, seed, last_mask=None, *, top_p=1.0,
                   temperature=1.0, uniforms=None, kept_floor=None):
     """wmz_sample_tokens_dev: logits fp32 [R, C]; last_frame: the [B, H, W] int64 view batch_z[:, -1] the tokens are written
@@ -317,20 +331,13 @@ def sample_tokens(logits, top_k, alphas, mask_token, last_frame, denoised, count
     top_p (nucleus, (0, 1]), temperature (> 0), uniforms fp32 [R, 2] (u0, u1 per row instead of the in-kernel generator) and
     kept_floor fp32 [R] (probe: receives the smallest kept scaled logit per row), or more than 2048 classes, go to
     wmz_sample_tokens_filtered_dev (include/wmz.h states its law); the kernel scales by the fp32 value of 1 / temperature."""
-    R, C = logits.shape
-    B = last_frame.shape[0]
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and last_frame.dtype == torch.int64
-    assert last_frame[0].is_contiguous() and R % B == 0 and denoised.numel() == R and counter.dtype == torch.int64
-    head = (L.ptr(logits), logits.stride(0), R, C, int(top_k))
-    tail = (L.ptr(alphas), alphas.numel(), int(mask_token), L.ptr(last_frame), R // B, last_frame.stride(0), L.ptr(denoised),
-            L.ptr(last_mask))
+    C = logits.shape[1]
+    head, alpha, out, probes, end = _sample_step_args(logits, top_k, alphas, last_frame, denoised, counter, seed, uniforms, kept_floor)
     if top_p >= 1.0 and temperature == 1.0 and uniforms is None and kept_floor is None and C <= SAMPLE_REGISTER_CLASSES:
-        L.call('wmz_sample_tokens_dev', *head, *tail, int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream())
+        L.call('wmz_sample_tokens_dev', *head, *alpha, int(mask_token), *out, L.ptr(last_mask), *end)
         return
-    assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.shape == (R, 2))
-    assert kept_floor is None or (kept_floor.dtype == torch.float32 and kept_floor.is_contiguous() and kept_floor.numel() == R)
-    L.call('wmz_sample_tokens_filtered_dev', *head, float(top_p), 1.0 / float(temperature), *tail, L.ptr(uniforms), L.ptr(kept_floor),
-           int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream())
+    L.call('wmz_sample_tokens_filtered_dev', *head, float(top_p), 1.0 / float(temperature), *alpha, int(mask_token), *out,
+           L.ptr(last_mask), *probes, *end)
 
 
 def remask_max_rows():
@@ -370,18 +377,13 @@ def sample_tokens_confidence(logits, top_k, alphas, mask_token, last_frame, deno
     noise * (1 - alpha) * Gumbel(u1) with noise > 0) and no re-mask (wmz_sample_tokens_scored_dev), then per clip the
     floor((1 - alpha) * rows) lowest-scored candidates back to mask_token (wmz_remask_lowest_dev).  The arguments of sample_tokens
     keep their meaning; scores: fp32 [R] buffer of the caller's (tests), else a per-device workspace."""
-    R, C = logits.shape
-    B = last_frame.shape[0]
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and last_frame.dtype == torch.int64
-    assert last_frame[0].is_contiguous() and R % B == 0 and denoised.numel() == R and counter.dtype == torch.int64
-    assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.shape == (R, 2))
-    assert kept_floor is None or (kept_floor.dtype == torch.float32 and kept_floor.is_contiguous() and kept_floor.numel() == R)
+    R = logits.shape[0]
+    head, alpha, out, probes, end = _sample_step_args(logits, top_k, alphas, last_frame, denoised, counter, seed, uniforms, kept_floor)
     if scores is None:
         scores = _scores(logits.device, R)
     assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == R
-    L.call('wmz_sample_tokens_scored_dev', L.ptr(logits), logits.stride(0), R, C, int(top_k), float(top_p), 1.0 / float(temperature),
-           L.ptr(alphas), alphas.numel(), L.ptr(last_frame), R // B, last_frame.stride(0), L.ptr(denoised), L.ptr(scores), float(noise),
-           L.ptr(uniforms), L.ptr(kept_floor), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(counter), L.stream())
+    L.call('wmz_sample_tokens_scored_dev', *head, float(top_p), 1.0 / float(temperature), *alpha, *out, L.ptr(scores), float(noise),
+           *probes, *end)
     remask_lowest(scores, alphas, mask_token, last_frame, counter, last_mask)
 
 
