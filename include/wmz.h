@@ -604,6 +604,23 @@ int wmz_dilate_nhwc(const void* dy, void* dz, int B, int Ho, int Wo, int C, int 
 /* F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) (autoencoder.py:138) on NHWC. */
 int wmz_bilinear2x_nhwc(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 
+/* ---- byte frames in and out (csrc/frame_bytes.hip; the two laws: csrc/frame_bytes.h).  The reference turns the trajectory
+ * sampler's uint8 [B, T, 64, 64, 3] batches into NCHW fp32 in [0, 1] on the host -- permute, .to(float32), / 255: main2.py:51-56
+ * (transform_batch) and minecraft/sparse_diffusion.py:23-28 -- and uploads four bytes per byte; generated frames come back as fp32
+ * and reach uint8 [H, W, C] through save_image's mul(255).add_(0.5).clamp_(0, 255).to(uint8) and a permute (main.py:121-132).
+ * These two launches replace both host sides: the raw bytes are uploaded, finished bytes are downloaded.
+ * wmz_frames_u8_to_nhwc8: x uint8, N frames, frame n at x + n * frame_stride bytes (frame_stride >= C H W: a [B, T] batch sliced
+ * in T needs no copy), each contiguous [H, W, C] (channels_last != 0) or [C, H, W]; any alignment of x.  y [N, H, W, C8], C8 = C
+ * rounded up to a multiple of 8, 16-byte aligned, out_dtype WMZ_F32 / WMZ_BF16 / WMZ_F16: fl(byte / 255) -- the correctly rounded fp32
+ * quotient, what the reference computes on the CPU -- rounded to nearest even into out_dtype; padding channels zero.  Bit for bit
+ * what wmz_nchw_to_nhwc8 makes of the reference's fp32 frames.
+ * wmz_nhwc8_to_frames_u8: y [N, H, W, C8] in in_dtype (the decoder's last convolution as it wrote it), 16-byte aligned; out uint8
+ * [N, H, W, C] (channels_last != 0) or [N, C, H, W], contiguous: each value exactly to fp32, then t = fl(v * 255), t = fl(t + 0.5)
+ * (two roundings), clamped to [0, 255], truncated; NaN -> 0.  The padding channels are dropped. */
+int wmz_frames_u8_to_nhwc8(const void* x, void* y, long N, int C, int H, int W, long frame_stride, int channels_last,
+                           int out_dtype, void* stream);
+int wmz_nhwc8_to_frames_u8(const void* y, void* out, long N, int C, int H, int W, int channels_last, int in_dtype, void* stream);
+
 /* ---- the conv encoder / decoder's half inference route (the precise mode with config.precise_conv on).  The reference computes
  * these layers in fp32 (autoencoder.py:8-15 conv3x3 / conv1x1 inside Residual :18-42, the 2x2 / stride 2 down-sampling :29-33,
  * SimpleResidualEncoder's conv_1 :60-86, UpscaleResidual :89-131, SimpleResidualDecoder :134-152); bf16 operands leave the latents

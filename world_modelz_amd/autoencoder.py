@@ -68,6 +68,14 @@ def _to_nhwc(x, dtype):
     return x.to(dtype).contiguous()
 
 
+def _byte_frames_nchw(x, channels_last):
+    """The logical NCHW shape of uint8 frames [..., H, W, C] (channels_last) / [..., C, H, W], leading dimensions flattened."""
+    if x.dim() < 3:
+        raise WmzError(f'byte frames have at least three dimensions, not {tuple(x.shape)}')
+    H, W, C = x.shape[-3:] if channels_last else (x.shape[-2], x.shape[-1], x.shape[-3])
+    return (x.numel() // max(H * W * C, 1), C, H, W)
+
+
 def _to_nchw_view(y):
     """[B,H,W,C] contiguous -> logical NCHW view (channels_last memory format, no copy)."""
     return y.permute(0, 3, 1, 2)
@@ -420,21 +428,29 @@ class SimpleResidualEncoder(nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
-    def forward_nhwc(self, x):
+    def forward_nhwc(self, x, channels_last=True):
         """NCHW frames -> [B,h,w,E] latents (what VectorQuantizerEMA wants: no NCHW<->NHWC flips), in the pass's dtype
-        (conv_route: the compute dtype, or float16 on the precise mode's half conv route)."""
+        (conv_route: the compute dtype, or float16 on the precise mode's half conv route).
+        x uint8: byte frames [..., H, W, C] (channels_last) or [..., C, H, W], the leading dimensions flattened into the batch --
+        ops.frames_u8_to_nhwc8 (byte / 255, flip, pad and cast: one launch) stands in front of _conv_1 in place of the layout
+        flip, everything behind it is the same pass, routed on the logical NCHW shape.  channels_last is read for bytes only."""
+        u8 = x.dtype == torch.uint8
+        shape = _byte_frames_nchw(x, channels_last) if u8 else x.shape
+        if u8 and shape[1] != self._conv_1.in_channels:
+            raise WmzError(f'byte frames of {shape[1]} channels (channels_last={channels_last}) for an encoder of {self._conv_1.in_channels}')
         grad = _grad_path(x, self)
-        dt = conv_route(self, x.shape, grad)
+        dt = conv_route(self, shape, grad)
         if dt == torch.float16:
             from . import half_guard
             if half_guard.wanted():            # config.half_guard: this pass again, guarded (inside, wanted() is False)
-                return half_guard.guarded('SimpleResidualEncoder', self, x.device, lambda: self.forward_nhwc(x),
-                                          half_guard.with_buffers_restored(self, lambda: self.forward_nhwc(x)))
+                return half_guard.guarded('SimpleResidualEncoder', self, x.device, lambda: self.forward_nhwc(x, channels_last),
+                                          half_guard.with_buffers_restored(self, lambda: self.forward_nhwc(x, channels_last)))
         with ops.stat_arena():                                     # (one zero fill for every BatchNorm statistic of the pass)
+            x8 = ops.frames_u8_to_nhwc8(x, dt, channels_last) if u8 else _to_nhwc(x, dt)
             if grad:
-                h = F.leaky_relu(_conv_g(_to_nhwc(x, dt), self._conv_1), LEAKY)
+                h = F.leaky_relu(_conv_g(x8, self._conv_1), LEAKY)
             else:
-                h = _conv(_to_nhwc(x, dt), self._conv_1, dt, leaky=True, slope=LEAKY)
+                h = _conv(x8, self._conv_1, dt, leaky=True, slope=LEAKY)
             return self._residual_stack.forward_nhwc(h, dt)
 
     def forward(self, x):

@@ -126,8 +126,8 @@ class GraphedForward:
 class _EncodeAdaptor:
     """VqAutoEncoder.encode behind the interface GraphedForward captures (a callable with parameters() / buffers())."""
 
-    def __init__(self, ae):
-        self.ae = ae
+    def __init__(self, ae, channels_last=True):
+        self.ae, self.channels_last = ae, channels_last
 
     def parameters(self):
         return self.ae.parameters()
@@ -136,6 +136,8 @@ class _EncodeAdaptor:
         return self.ae.buffers()
 
     def __call__(self, frames):
+        if frames.dtype == torch.uint8:
+            return self.ae.encode_frames(frames, self.channels_last)
         return self.ae.encode(frames)
 
 
@@ -150,7 +152,12 @@ class GraphedEncoder(GraphedForward):
     A captured encoder keeps the conv route it was captured with (autoencoder.conv_route: in the precise mode, the half route of
     config.precise_conv or the fp32 one): toggling config.precise_conv afterwards does not re-capture it -- build a new one.  A
     change of compute dtype does re-capture (the stamp holds the mode).
+
+    With a uint8 example -- byte frames [..., H, W, C] (channels_last) or [..., C, H, W], as VqAutoEncoder.encode_frames takes them
+    -- the static input is uint8 and the graph starts with the byte ingest (wmz_frames_u8_to_nhwc8).  A replay copies whatever it
+    is given into the static input without blocking, so a PINNED uint8 host batch costs one asynchronous copy of N H W C bytes and
+    one graph launch per batch: no fp32 frames on either side of the host link.  The tokens are [..., h, w].
     """
 
-    def __init__(self, ae, example_frames, warmup=2):
-        super().__init__(_EncodeAdaptor(ae), example_frames, warmup=warmup)
+    def __init__(self, ae, example_frames, warmup=2, channels_last=True):
+        super().__init__(_EncodeAdaptor(ae, channels_last), example_frames, warmup=warmup)

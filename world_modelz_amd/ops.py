@@ -995,6 +995,65 @@ def nchw_to_nhwc8(x, dtype):
     return y
 
 
+def _uniform_frame_stride(x, nlead):
+    """Byte frames x [*lead, d0, d1, d2] -> the one element stride that takes frame n (lead dimensions flattened) to frame n + 1, or
+    None when the frames are not contiguous each or the lead dimensions do not fold into one stride (then the caller copies)."""
+    sizes, strides = list(x.shape), list(x.stride())
+    frame = 1
+    for n, s in zip(reversed(sizes[nlead:]), reversed(strides[nlead:])):
+        if n != 1 and s != frame:
+            return None
+        frame *= n
+    lead = [(n, s) for n, s in zip(sizes[:nlead], strides[:nlead]) if n != 1]
+    if not lead:
+        return frame
+    for (_, s_out), (n_in, s_in) in zip(lead[:-1], lead[1:]):
+        if s_out != n_in * s_in:
+            return None
+    return lead[-1][1] if lead[-1][1] >= frame else None
+
+
+def frames_u8_to_nhwc8(x, dtype, channels_last=True):
+    """uint8 frames [..., H, W, C] (channels_last) or [..., C, H, W] on the GPU -> [N, H, W, C8] in `dtype` (fp32, bf16 or half), N
+    the product of the leading dimensions, C8 = C rounded up to a multiple of 8: byte / 255 (the fp32 quotient the reference
+    computes on the CPU, main2.py:51-56) rounded into dtype, padding channels zero -- bit for bit nchw_to_nhwc8 of the reference's
+    fp32 frames, in one launch.  Frames that are contiguous each and one stride apart (a [B, T] batch with one frame selected, or
+    sliced to one frame per clip, ...) are read where they are, at any alignment; anything else is made contiguous first."""
+    if not x.is_cuda:
+        raise L.WmzError('the conv encoder/decoder runs on the GPU only (no CPU fallback)')
+    if x.dtype != torch.uint8 or x.dim() < 3:
+        raise L.WmzError(f'frames_u8_to_nhwc8: uint8 frames of at least three dimensions, not {x.dtype} {tuple(x.shape)}')
+    H, W, C = x.shape[-3:] if channels_last else (x.shape[-2], x.shape[-1], x.shape[-3])
+    N = x.numel() // (H * W * C) if x.numel() else 0
+    if N == 0:
+        raise L.WmzError(f'frames_u8_to_nhwc8: empty frames {tuple(x.shape)}')
+    stride = H * W * C if x.is_contiguous() else _uniform_frame_stride(x, x.dim() - 3)
+    if stride is None:
+        x = x.contiguous()
+        stride = H * W * C
+    y = torch.empty((N, H, W, (C + 7) // 8 * 8), dtype=dtype, device=x.device)
+    L.call('wmz_frames_u8_to_nhwc8', L.ptr(x), L.ptr(y), N, C, H, W, stride, int(bool(channels_last)), L.dtype_code(dtype), L.stream())
+    return y
+
+
+def nhwc8_to_frames_u8(y, C, channels_last=True):
+    """The decoder's raw output [..., H, W, C8] (fp32, bf16 or half; SimpleResidualDecoder.forward_nhwc(raw=True)) -> uint8 frames
+    [N, H, W, C] (channels_last) or [N, C, H, W] by save_image's law in fp32 -- mul(255), add(0.5), clamp(0, 255), truncate; NaN
+    gives 0 -- the C8 - C padding channels dropped: one launch."""
+    if not y.is_cuda:
+        raise L.WmzError('the conv encoder/decoder runs on the GPU only (no CPU fallback)')
+    if y.dim() < 3 or C < 1 or y.shape[-1] != (C + 7) // 8 * 8:
+        raise L.WmzError(f'nhwc8_to_frames_u8: [..., H, W, {(C + 7) // 8 * 8}] for C = {C}, not {tuple(y.shape)}')
+    H, W, C8 = y.shape[-3:]
+    N = y.numel() // (H * W * C8) if y.numel() else 0
+    if N == 0:
+        raise L.WmzError(f'nhwc8_to_frames_u8: empty tensor {tuple(y.shape)}')
+    y = y.contiguous()
+    out = torch.empty((N, H, W, C) if channels_last else (N, C, H, W), dtype=torch.uint8, device=y.device)
+    L.call('wmz_nhwc8_to_frames_u8', L.ptr(y), L.ptr(out), N, C, H, W, int(bool(channels_last)), L.dtype_code(y.dtype), L.stream())
+    return out
+
+
 def channel_stats_nhwc(x):
     C = x.shape[-1]
     M = x.numel() // C

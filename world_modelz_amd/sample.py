@@ -213,6 +213,23 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     return out, (batch_z.clone() if fwd is not None else batch_z)   # (never hand out the graph's own buffer)
 
 
+@torch.no_grad()
+def predict_frames(model, ae, context, num_embeddings, num_frames, channels_last=True, **sampler_kwargs):
+    """The reference's evaluate_model (main.py:50-132) with the context frames given instead of drawn from a dataset, bytes in and
+    bytes out: context uint8 [B, S-1, H, W, C] (channels_last; else [B, S-1, C, H, W]) on the GPU -> (frames uint8
+    [B, num_frames, H, W, C] (or [B, num_frames, C, H, W]), the final batch_z).  VqAutoEncoder.encode_frames on the context (one
+    encoder batch of B (S-1) frames), a mask frame appended, sample_frames(**sampler_kwargs), VqAutoEncoder.decode_frames on ONE
+    generated frame -- B images -- at a time as main.py:113 does: the decoder's BatchNorm runs in training mode there (quirk Q3),
+    and another decode batch would be other statistics."""
+    if context.dim() != 5:
+        raise ValueError(f'context is uint8 [B, S-1, H, W, C] or [B, S-1, C, H, W], not {tuple(context.shape)}')
+    z = ae.encode_frames(context, channels_last)                                      # [B, S-1, h, w]
+    batch_z = torch.cat([z, torch.full_like(z[:, :1], num_embeddings)], dim=1)        # (sample_frames masks the last frame itself)
+    latents, batch_z = sample_frames(model, batch_z, num_embeddings, num_frames, **sampler_kwargs)
+    frames = torch.stack([ae.decode_frames(zf, channels_last) for zf in latents], dim=1)
+    return frames, batch_z
+
+
 MAX_SESSIONS = 2          # captured sampler steps kept per model (least recently used beyond that are dropped: a graph, its
 #                           buffers and its references to the operand copies are ~tens of MB each)
 

@@ -2,6 +2,7 @@
 import torch
 import torch.nn as nn
 
+from ._lib import WmzError
 from .autoencoder import SimpleResidualDecoder, SimpleResidualEncoder, _grad_path, _pad8, conv_route
 from .config import get_compute_dtype
 from .vq import VectorQuantizerEMA
@@ -56,3 +57,31 @@ class VqAutoEncoder(nn.Module):
 
     def decode(self, z):
         return self._decode_latents(self.vq.decode(z))
+
+    # Byte frames at both ends (the reference's data arrives as uint8 [B, T, H, W, C] -- minecraft/main2.py:51-56 -- and every
+    # consumer of generated frames wants uint8 [H, W, C] -- main.py:121-132): the raw bytes are uploaded and finished bytes come
+    # back; / 255 on the way in and save_image's mul(255).add(0.5).clamp(0, 255) on the way out ride in the two layout launches.
+
+    def encode_frames(self, frames, channels_last=True):
+        """uint8 frames [..., H, W, C] (channels_last) or [..., C, H, W] on the GPU -> int64 tokens [..., h, w]: encode() of the
+        frames as the reference's transform_batch prepares them (NCHW fp32, byte / 255), without that tensor."""
+        if frames.dtype != torch.uint8:
+            raise WmzError(f'encode_frames takes uint8 frames, not {frames.dtype} (float frames: encode)')
+        h = self.encoder.forward_nhwc(frames, channels_last).float()
+        return self.vq.encode(h).view(*frames.shape[:-3], *h.shape[1:-1])
+
+    def decode_frames(self, z, channels_last=True):
+        """int64 tokens [..., h, w] -> uint8 frames [..., H, W, C] (channels_last) or [..., C, H, W]: decode() followed by
+        save_image's law (ops.nhwc8_to_frames_u8 on the decoder's raw output: no fp32 image, no permute).  All of z is ONE decoder
+        batch: with BatchNorm in training mode (quirk Q3) decode what the reference decodes together."""
+        from . import ops
+        q = self.vq.decode(z)
+        lead = q.shape[:-3]
+        q = q.reshape(-1, *q.shape[-3:])
+        E = q.shape[-1]
+        if _pad8(E) != E:
+            q = torch.nn.functional.pad(q, (0, _pad8(E) - E))
+        dt = conv_route(self.decoder, q.shape, _grad_path(q, self.decoder))          # (the route of _decode_latents)
+        y = self.decoder.forward_nhwc(q.to(dt).contiguous(), raw=True)
+        out = ops.nhwc8_to_frames_u8(y.detach(), self.decoder.decoder_stack[-1].out_channels, channels_last)
+        return out.view(*lead, *out.shape[1:])
