@@ -96,6 +96,27 @@ int wmz_local3d_attn_bwd_general(const void* q, const void* k, const void* v, co
                                  long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv,
                                  int dtype, void* stream);
 
+/* The time window as a pair (the reference's open item `# todo: add causal masking`, local_3d_attention.py above
+ * Local3dAttention.forward): query plane s sees the key planes max(0, s - eS_back) .. min(S - 1, s + eS_fwd); the window inside a
+ * plane (eH, eW) is as above.  (eS, eS) is the symmetric window of the entry points above and gives their results bit for bit;
+ * (eS, 0) is the causal one: nothing of a plane <= s depends on a plane > s.  A key plane p is seen by the query planes p - eS_fwd
+ * .. p + eS_back, which is what the backward's dk | dv pass gathers.
+ *   _fwd_window: the contract of wmz_local3d_attn_fwd and of its trailing-planes form wmz_local3d_attn_fwd_planes (q_plane0,
+ *     q_planes: out / lse compact over those planes; the full grid is 0, S).  logits_dbg (full grid only) has
+ *     (eS_back + eS_fwd + 1)(2eH+1)(2eW+1) slots per query, plane slot ds + eS_back.
+ *   _bwd_window: the contract of wmz_local3d_attn_bwd.
+ * general != 0 keeps the launch on the general kernels (wmz_local3d_attn_*_general).  Same dtypes and refusals as the entry points
+ * they extend; a negative extent is refused. */
+int wmz_local3d_attn_fwd_window(const void* q, const void* k, const void* v, void* out, float* lse, float* logits_dbg,
+                                int B, int S, int H, int W, int heads, int dh, int eS_back, int eS_fwd, int eH, int eW,
+                                long ldq, long ldk, long ldv, long ldo, int q_plane0, int q_planes, int general, int dtype,
+                                void* stream);
+int wmz_local3d_attn_bwd_window(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                const void* dout, void* dq, void* dk, void* dv, float* delta_ws,
+                                int B, int S, int H, int W, int heads, int dh, int eS_back, int eS_fwd, int eH, int eW,
+                                long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv,
+                                int general, int dtype, void* stream);
+
 /* ---- nn.Linear family (local_3d_attention.py:46-53 to_q/to_k/to_v/to_out, :23-29 FeedForward, main.py:31
  * logit_proj), optionally fused with the PreNorm LayerNorm in front (:14-17) and the residual add behind
  * (:160-161):   C[M,N] = act( LN?(A)[M,K] @ Wt[N,K]^T + bias[N] ) + residual[M,N]

@@ -116,7 +116,8 @@ def _attention_block_backward(ctx, dy):
     else:
         do = dy
     # ---- attention core
-    dq, dkv = ops.local3d_attention_bwd(q, kv[..., :I], kv[..., I:], o, lse, do, ctx.extents, ctx.heads)
+    dq, dkv = ops.local3d_attention_bwd(q, kv[..., :I], kv[..., I:], o, lse, do, ctx.extents, ctx.heads,
+                                        time_window=getattr(ctx, 'time_window', None))
     # ---- to_q on the raw input
     g_wq = _emit(wq, lambda w: ops.linear_wgrad(dq, x_q, w))
     dxq = ops.linear_dgrad(dq, _wt(wq, dt, 'wqT'))

@@ -47,7 +47,8 @@ def build_denoiser(data, num_embeddings, use_ema=False):
     extents = [int(e) for e in str(o.extents).split(',')]
     assert len(extents) == 3
     model = VqVideoDiffusionModel(data_shape=data_shape, dim=o.dim, num_classes=num_embeddings, extents=extents,
-                                  depth=o.depth, mlp_dim=o.mlp_dim, dim_head=o.dim_head, heads=o.heads, dropout=o.dropout)
+                                  depth=o.depth, mlp_dim=o.mlp_dim, dim_head=o.dim_head, heads=o.heads, dropout=o.dropout,
+                                  causal=bool(getattr(o, 'causal', False)))      # (a reference checkpoint has no such field)
     model.load_state_dict(sd, strict=True)
     return model
 

@@ -7,7 +7,9 @@
 //   MODE 1 (owner = keys)     dK_j = scale * sum_i dS_ij Q_i ,  dV_j = sum_i P_ij dO_i
 // with P_ij = exp(scale*s_ij - lse_i), dS_ij = P_ij (dO_i.V_j - delta_i).  "Owner" tiles (16 positions) live in
 // registers as MFMA B operands (X1 = Q|K, X2 = dO|V); "visitor" tiles of the neighbouring planes are staged in LDS
-// (Y1 = K|Q, Y2 = V|dO) exactly like the forward's K/V slabs:
+// (Y1 = K|Q, Y2 = V|dO) exactly like the forward's K/V slabs.  (Inside a plane the relation is symmetric; along the time axis a query
+// plane s sees the key planes s - eS .. s + eSf, so a key plane p is seen by the query planes p - eSf .. p + eS: MODE 1 is launched
+// with the swapped pair, attn_swap_window, and the kernel itself reads "eS before, eSf after the owner plane" in both roles.)
 //   S^T [32 visitors x 16 owners] = Y1 . X1^T          dP^T = Y2 . X2^T          (row fragments, MFMA 16x16x32)
 //   acc1^T[dh x 16 owners] += Y1^T . dS^T               (MODE 1 also: acc2^T += Y2^T . P^T)   (transposed LDS reads)
 #include "attn_common.h"
@@ -142,7 +144,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void attn_bwd_kernel(BwdPtrs P, AttnGe
   const int t_lo = (max(wg_hlo - G.eH, 0) * G.W) >> 4;
   const int t_hi = (min(wg_hhi + G.eH, G.H - 1) * G.W + G.W - 1) >> 4;
 
-  for (int ds = -G.eS; ds <= G.eS; ++ds) {
+  for (int ds = -G.eS; ds <= G.eSf; ++ds) {
     const int sv = s + ds;
     if (sv < 0 || sv >= G.S) continue;
     const long plane_v = ((long)b * G.S + sv) * HW;
@@ -294,7 +296,7 @@ int launch_both(const BwdPtrs& PQ, const BwdPtrs& PK, const AttnGeom& G, hipStre
   constexpr int OPW0 = sizeof(T) == 2 ? 2 : 1;
   int rc = launch<T, DH, OPW0, KC, 0>(PQ, G, st);
   if (rc != WMZ_OK) return rc;
-  return launch<T, DH, 1, KC, 1>(PK, G, st);
+  return launch<T, DH, 1, KC, 1>(PK, attn_swap_window(G), st);      // owners are keys: the swapped time window
 }
 
 }  // namespace
@@ -311,14 +313,14 @@ int wmz_attn_bwd_row32_dispatch(const void* q, const void* k, const void* v, con
 
 static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* out, const float* lse,
                          const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
-                         int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
+                         int W, int heads, int dh, int eS, int eSf, int eH, int eW, long ldq, long ldk, long ldv,
                          long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream, bool general);
 
 extern "C" int wmz_local3d_attn_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse,
                                     const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
                                     int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
                                     long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream) {
-  return attn_bwd_impl(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, B, S, H, W, heads, dh, eS, eH, eW, ldq, ldk, ldv, ldo, lddo,
+  return attn_bwd_impl(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, B, S, H, W, heads, dh, eS, eS, eH, eW, ldq, ldk, ldv, ldo, lddo,
                        lddq, lddk, lddv, dtype, stream, false);
 }
 
@@ -327,24 +329,35 @@ extern "C" int wmz_local3d_attn_bwd_general(const void* q, const void* k, const 
                                             const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
                                             int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
                                             long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream) {
-  return attn_bwd_impl(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, B, S, H, W, heads, dh, eS, eH, eW, ldq, ldk, ldv, ldo, lddo,
+  return attn_bwd_impl(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, B, S, H, W, heads, dh, eS, eS, eH, eW, ldq, ldk, ldv, ldo, lddo,
                        lddq, lddk, lddv, dtype, stream, true);
+}
+
+// The time window stated as a pair (wmz_local3d_attn_fwd_window): dq of plane s gathers the key planes s - eS_back .. s + eS_fwd,
+// dk | dv of plane p the query planes p - eS_fwd .. p + eS_back.  Every other argument as above; general != 0: the general kernels.
+extern "C" int wmz_local3d_attn_bwd_window(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                           const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
+                                           int W, int heads, int dh, int eS_back, int eS_fwd, int eH, int eW, long ldq, long ldk,
+                                           long ldv, long ldo, long lddo, long lddq, long lddk, long lddv, int general, int dtype,
+                                           void* stream) {
+  return attn_bwd_impl(q, k, v, out, lse, dout, dq, dk, dv, delta_ws, B, S, H, W, heads, dh, eS_back, eS_fwd, eH, eW, ldq, ldk, ldv,
+                       ldo, lddo, lddq, lddk, lddv, dtype, stream, general != 0);
 }
 
 static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* out, const float* lse,
                          const void* dout, void* dq, void* dk, void* dv, float* delta_ws, int B, int S, int H,
-                         int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv,
+                         int W, int heads, int dh, int eS, int eSf, int eH, int eW, long ldq, long ldk, long ldv,
                          long ldo, long lddo, long lddq, long lddk, long lddv, int dtype, void* stream, bool general) {
   WMZ_REQUIRE(q && k && v && out && lse && dout && dq && dk && dv && delta_ws, "wmz_local3d_attn_bwd: null tensor");
   WMZ_REQUIRE(B > 0 && S > 0 && H > 0 && W > 0 && heads > 0 && dh > 0, "wmz_local3d_attn_bwd: bad shape");
-  WMZ_REQUIRE(eS >= 0 && eH >= 0 && eW >= 0, "wmz_local3d_attn_bwd: negative extent");
+  WMZ_REQUIRE(eS >= 0 && eSf >= 0 && eH >= 0 && eW >= 0, "wmz_local3d_attn_bwd: negative extent");
   WMZ_REQUIRE(H <= 16384 && W <= 16384, "wmz_local3d_attn_bwd: H, W must be <= 16384");
   WMZ_REQUIRE(dh % 8 == 0, "wmz_local3d_attn_bwd: dim_head must be a multiple of 8 (got %d)", dh);
   WMZ_REQUIRE((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) % 8 == 0, "wmz_local3d_attn_bwd: row strides must be multiples of 8");
   WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_local3d_attn_bwd: bad dtype %d", dtype);
   if (dh > 128) { wmz_set_error("wmz_local3d_attn_bwd: dim_head %d > 128 not built", dh); return WMZ_ERR_UNSUPPORTED; }
   AttnGeom G;
-  G.B = B; G.S = S; G.H = H; G.W = W; G.heads = heads; G.dh = dh; G.eS = eS; G.eH = eH; G.eW = eW;
+  G.B = B; G.S = S; G.H = H; G.W = W; G.heads = heads; G.dh = dh; G.eS = eS; G.eSf = eSf; G.eH = eH; G.eW = eW;
   G.ldq = ldq; G.ldk = ldk; G.ldv = ldv; G.ldo = ldo;
   G.HW = H * W; G.tiles = (G.HW + 15) / 16; G.qgroups = 0;
   G.scale = 1.0f / sqrtf((float)dh);

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
   // ---- slab geometry and walk (as in attn_fwd_row16.hip; stated once and pinned on the host: attn_slab_walk.h)
   const int my_lo = max(W32 ? w32_row_lo(h, G.eH) : h - eHv, 0), my_hi = min(W32 ? w32_row_hi(h, G.eH) : h + eHv, H - 1);
   const int t_lo = max(h0 - eHv, 0), t_hi = min(min(h0 + NW - 1, H - 1) + eHv, H - 1);
-  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
+  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eSf);
   const int c_first = t_lo >> LOG_CH, c_last = t_hi >> LOG_CH;
   const int nch = (c_last - c_first + 1) * 2;               // slabs per visiting plane: (chunk) x (row parity)
   const int nslab = (sk_hi - sk_lo + 1) * nch;
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? (MODE == 0 && !W8 ? 4 : 2) : 1)
   }
   const unsigned rs1 = 16u * ld1_b, rs2 = 16u * ld2_b;
   const long ps1 = (long)HW * (long)ld1_b, ps2 = (long)HW * (long)ld2_b;
-  const int nwin = 2 * G.eS + 1;
+  const int nwin = G.eS + G.eSf + 1;
   int p_first = s - G.eS;
   { const int a = (((G.S - 1 - p_first) % nwin) + nwin) % nwin; p_first += a; }
   if (p_first > sk_hi || p_first < sk_lo) p_first = sk_lo;
@@ -506,14 +506,14 @@ __global__ __launch_bounds__(1024) void attn_bwd_kvplane_kernel(RBwdPtrs P, Attn
   // ---- slab geometry and walk (as above, without the clamps: attn_slab_walk.h, CLAMP = false)
   const int my_lo = max(h - G.eH, 0), my_hi = min(h + G.eH, H - 1);
   const int t_lo = max(h0 - G.eH, 0), t_hi = min(h0 + NW - 1 + G.eH, H - 1);
-  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
+  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eSf);
   const int c_first = t_lo >> 4, c_last = t_hi >> 4;
   const int nch = (c_last - c_first + 1) * 2;
   const int nslab = (sk_hi - sk_lo + 1) * nch;
   const unsigned ld1_b = (unsigned)P.ldy1 * 2u, ld2_b = (unsigned)P.ldy2 * 2u;      // SAME_LD: equal
   const unsigned rs1 = 16u * ld1_b, rs2 = 16u * ld2_b;
   const long ps1 = (long)HW * (long)ld1_b, ps2 = (long)HW * (long)ld2_b;
-  const int nwin = 2 * G.eS + 1;
+  const int nwin = G.eS + G.eSf + 1;
   int p_first = s - G.eS;
   { const int a = (((G.S - 1 - p_first) % nwin) + nwin) % nwin; p_first += a; }
   if (p_first > sk_hi || p_first < sk_lo) p_first = sk_lo;
@@ -760,17 +760,19 @@ int launch_one(const RBwdPtrs& P, AttnGeom G, hipStream_t st, bool whole_chunks_
   return WMZ_OK;
 }
 
+// (GK: the geometry of the dk | dv role -- a key plane p is seen by the query planes p - eSf .. p + eS, the swapped time window.)
 template <int DH>
 int launch_both(const RBwdPtrs& PQ, const RBwdPtrs& PK, const AttnGeom& G, hipStream_t st) {
+  const AttnGeom GK = attn_swap_window(G);
   if (G.w8) {
     // 8-wide planes (G.H = H / 2 tile rows): up to 8 tile rows on 4-wave workgroups with 2-row slabs, larger planes on the big shapes
     if (G.H <= 8) {
       const int rc = launch_one<DH, 0, 4, 2, true>(PQ, G, st);
-      return rc != WMZ_OK ? rc : launch_one<DH, 1, 4, 2, true>(PK, G, st);
+      return rc != WMZ_OK ? rc : launch_one<DH, 1, 4, 2, true>(PK, GK, st);
     }
     // (the dq pass with its rim masks does not fit 128 registers: 8-wave workgroups, two per plane chunk, for it as well)
     const int rc = launch_one<DH, 0, 8, 8, true>(PQ, G, st);
-    return rc != WMZ_OK ? rc : launch_one<DH, 1, 8, 8, true>(PK, G, st);
+    return rc != WMZ_OK ? rc : launch_one<DH, 1, 8, 8, true>(PK, GK, st);
   }
   int rc = launch_one<DH, 0, 16, 8, false>(PQ, G, st);
   if (rc != WMZ_OK) return rc;
@@ -778,7 +780,7 @@ int launch_both(const RBwdPtrs& PQ, const RBwdPtrs& PK, const AttnGeom& G, hipSt
 #define WMZ_ABWD_PLANE 1    // 1: the whole-plane 16-wave dk | dv kernel where its preconditions hold; 0: always the 8-wave form
 #endif
   if (WMZ_ABWD_PLANE && (G.H & 15) == 0) {
-    AttnGeom Gp = G;
+    AttnGeom Gp = GK;
     Gp.qgroups = G.H / 16;
     const long nwg = (long)G.B * G.heads * G.S * Gp.qgroups;
     const float c2 = G.scale * 1.4426950408889634f;
@@ -789,7 +791,7 @@ int launch_both(const RBwdPtrs& PQ, const RBwdPtrs& PK, const AttnGeom& G, hipSt
     WMZ_LAUNCH_CHECK("wmz_local3d_attn_bwd(row16, dk|dv plane)");
     return WMZ_OK;
   }
-  return launch_one<DH, 1, 8, 8, false>(PK, G, st);
+  return launch_one<DH, 1, 8, 8, false>(PK, GK, st);
 }
 
 // 32-wide planes (G.H = 2H tile rows): the multi-workgroup forms in their W32 mode (MODE bit 1).  Up to 8 tile rows on the 4-wave
@@ -797,14 +799,15 @@ int launch_both(const RBwdPtrs& PQ, const RBwdPtrs& PK, const AttnGeom& G, hipSt
 // (the whole-plane dk | dv kernel is written for 16x16 planes and keeps its window law).
 template <int DH>
 int launch_both32(const RBwdPtrs& PQ, const RBwdPtrs& PK, const AttnGeom& G, hipStream_t st) {
+  const AttnGeom GK = attn_swap_window(G);
   if (G.H <= 8) {
     const int rc = launch_one<DH, 2, 4, 2, false>(PQ, G, st);
-    return rc != WMZ_OK ? rc : launch_one<DH, 3, 4, 2, false>(PK, G, st);
+    return rc != WMZ_OK ? rc : launch_one<DH, 3, 4, 2, false>(PK, GK, st);
   }
   // (at dim_head 128 the dq pass's whole-chunks form, which keeps its LDS-DMA offsets in registers, would spill 16 bytes at the
   //  128 registers of a 16-wave workgroup: the clamped form, valid for any H, holds 128 without scratch)
   const int rc = launch_one<DH, 2, 16, 8, false>(PQ, G, st, DH < 128);
-  return rc != WMZ_OK ? rc : launch_one<DH, 3, 8, 8, false>(PK, G, st);
+  return rc != WMZ_OK ? rc : launch_one<DH, 3, 8, 8, false>(PK, GK, st);
 }
 
 }  // namespace

@@ -27,7 +27,12 @@ struct AttnGeom {
   int dbg;       // ablation switches for timing experiments: 1 = skip the per-tile compute, 2 = skip the K/V staging
   int variant;   // development A/B switch between kernel instantiations (wmz_debug_attn_knobs); 0 = product default
   int w8;        // row kernels: the plane is 8 wide and handed over as H / 2 tile rows of 16 (attn_fwd_row16.hip)
+  int eSf;       // time window: the owner plane s sees the planes s - eS .. s + eSf (eS: planes before, eSf: planes after; symmetric:
+                 // eSf == eS, causal: eSf == 0).  The dk | dv role of the backward takes the swapped pair (attn_swap_window)
 };
+
+// A key plane p is seen by the query planes p - eSf .. p + eS: the geometry of the role whose owners are keys.
+inline AttnGeom attn_swap_window(AttnGeom G) { const int b = G.eS; G.eS = G.eSf; G.eSf = b; return G; }
 
 struct TileInfo { int hlo, hhi, wlo, whi; };
 

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void attn_fwd_kernel(const
   const int t_hi = (min(wg_hhi + G.eH, G.H - 1) * G.W + G.W - 1) >> 4;
 
   // slab schedule: planes sk_lo..sk_hi x nch slabs of KC tiles; slab j+1 is in flight while slab j is processed
-  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
+  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eSf);
   const int nch = (t_hi - t_lo + KC) / KC;
   const int nslab = (sk_hi - sk_lo + 1) * nch;
   auto issue = [&](int j) {
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void attn_fwd_kernel(const
             const bool ok0 = win_inside(d0, lim);
             const bool ok1 = has1 && win_inside(d1, lim);
             if (DBG != nullptr && qt0 * 16 + qi * 16 + li < HW) {
-              const long qrow = ((plane_q + qt0 * 16 + qi * 16 + li) * G.heads + head) * (long)((2 * G.eS + 1) * KHW);
+              const long qrow = ((plane_q + qt0 * 16 + qi * 16 + li) * G.heads + head) * (long)((G.eS + G.eSf + 1) * KHW);
               if (ok0) DBG[qrow + (ds + G.eS) * KHW + (int)(d0 >> 16) * KW + (int)(d0 & 0xFFFF)] = s0[r] * G.scale;
               if (ok1) DBG[qrow + (ds + G.eS) * KHW + (int)(d1 >> 16) * KW + (int)(d1 & 0xFFFF)] = s1[r] * G.scale;
             }
@@ -271,44 +271,55 @@ static int g_attn_dbg = 0, g_attn_variant = 0;
 extern "C" int wmz_debug_attn_knobs(int dbg, int variant) { g_attn_dbg = dbg; g_attn_variant = variant; return WMZ_OK; }
 
 static int attn_fwd_impl(const void* q, const void* k, const void* v, void* out, float* lse, float* logits_dbg, int B, int S,
-                         int H, int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv, long ldo,
+                         int H, int W, int heads, int dh, int eS, int eSf, int eH, int eW, long ldq, long ldk, long ldv, long ldo,
                          int q_plane0, int q_planes, int dtype, void* stream, bool general);
 
 extern "C" int wmz_local3d_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
                                     float* logits_dbg, int B, int S, int H, int W, int heads, int dh, int eS, int eH,
                                     int eW, long ldq, long ldk, long ldv, long ldo, int dtype, void* stream) {
-  return attn_fwd_impl(q, k, v, out, lse, logits_dbg, B, S, H, W, heads, dh, eS, eH, eW, ldq, ldk, ldv, ldo, 0, S, dtype, stream, false);
+  return attn_fwd_impl(q, k, v, out, lse, logits_dbg, B, S, H, W, heads, dh, eS, eS, eH, eW, ldq, ldk, ldv, ldo, 0, S, dtype, stream, false);
 }
 
 // Same contract, always on the general kernel (any W, fp32 or bf16): the parity tests compare the fast path with it.
 extern "C" int wmz_local3d_attn_fwd_general(const void* q, const void* k, const void* v, void* out, float* lse,
                                             float* logits_dbg, int B, int S, int H, int W, int heads, int dh, int eS, int eH,
                                             int eW, long ldq, long ldk, long ldv, long ldo, int dtype, void* stream) {
-  return attn_fwd_impl(q, k, v, out, lse, logits_dbg, B, S, H, W, heads, dh, eS, eH, eW, ldq, ldk, ldv, ldo, 0, S, dtype, stream, true);
+  return attn_fwd_impl(q, k, v, out, lse, logits_dbg, B, S, H, W, heads, dh, eS, eS, eH, eW, ldq, ldk, ldv, ldo, 0, S, dtype, stream, true);
 }
 
 extern "C" int wmz_local3d_attn_fwd_planes(const void* q, const void* k, const void* v, void* out, float* lse, int B, int S,
                                            int H, int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk,
                                            long ldv, long ldo, int q_plane0, int q_planes, int dtype, void* stream) {
-  return attn_fwd_impl(q, k, v, out, lse, nullptr, B, S, H, W, heads, dh, eS, eH, eW, ldq, ldk, ldv, ldo, q_plane0, q_planes,
+  return attn_fwd_impl(q, k, v, out, lse, nullptr, B, S, H, W, heads, dh, eS, eS, eH, eW, ldq, ldk, ldv, ldo, q_plane0, q_planes,
                        dtype, stream, false);
 }
 
+// The time window stated as a pair: query plane s sees the key planes max(0, s - eS_back) .. min(S - 1, s + eS_fwd); (eS, eS) is the
+// symmetric window of the entry points above, (eS, 0) the causal one.  Every other argument as above (query planes as in _planes, the
+// probe with (eS_back + eS_fwd + 1) plane slots per query); general != 0 keeps the launch on the general kernel.
+extern "C" int wmz_local3d_attn_fwd_window(const void* q, const void* k, const void* v, void* out, float* lse, float* logits_dbg,
+                                           int B, int S, int H, int W, int heads, int dh, int eS_back, int eS_fwd, int eH, int eW,
+                                           long ldq, long ldk, long ldv, long ldo, int q_plane0, int q_planes, int general, int dtype,
+                                           void* stream) {
+  return attn_fwd_impl(q, k, v, out, lse, logits_dbg, B, S, H, W, heads, dh, eS_back, eS_fwd, eH, eW, ldq, ldk, ldv, ldo, q_plane0,
+                       q_planes, dtype, stream, general != 0);
+}
+
 static int attn_fwd_impl(const void* q, const void* k, const void* v, void* out, float* lse, float* logits_dbg, int B, int S,
-                         int H, int W, int heads, int dh, int eS, int eH, int eW, long ldq, long ldk, long ldv, long ldo,
+                         int H, int W, int heads, int dh, int eS, int eSf, int eH, int eW, long ldq, long ldk, long ldv, long ldo,
                          int q_plane0, int q_planes, int dtype, void* stream, bool general) {
   WMZ_REQUIRE(q && k && v && out, "wmz_local3d_attn_fwd: null tensor");
   WMZ_REQUIRE(q_plane0 >= 0 && q_planes > 0 && q_plane0 + q_planes <= S, "wmz_local3d_attn_fwd: query planes [%d, %d) outside [0, %d)", q_plane0, q_plane0 + q_planes, S);
   WMZ_REQUIRE(logits_dbg == nullptr || q_planes == S, "wmz_local3d_attn_fwd: the logits probe needs the full grid");
   WMZ_REQUIRE(B > 0 && S > 0 && H > 0 && W > 0 && heads > 0 && dh > 0, "wmz_local3d_attn_fwd: bad shape");
-  WMZ_REQUIRE(eS >= 0 && eH >= 0 && eW >= 0, "wmz_local3d_attn_fwd: negative extent");
+  WMZ_REQUIRE(eS >= 0 && eSf >= 0 && eH >= 0 && eW >= 0, "wmz_local3d_attn_fwd: negative extent");
   WMZ_REQUIRE(H <= 16384 && W <= 16384, "wmz_local3d_attn_fwd: H, W must be <= 16384");
   WMZ_REQUIRE(dh % 8 == 0, "wmz_local3d_attn_fwd: dim_head must be a multiple of 8 (got %d)", dh);
   WMZ_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "wmz_local3d_attn_fwd: row strides must be multiples of 8");
   WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16 || dtype == WMZ_F16, "wmz_local3d_attn_fwd: bad dtype %d", dtype);
   if (dh > 128) { wmz_set_error("wmz_local3d_attn_fwd: dim_head %d > 128 not built", dh); return WMZ_ERR_UNSUPPORTED; }
   AttnGeom G;
-  G.B = B; G.S = S; G.H = H; G.W = W; G.heads = heads; G.dh = dh; G.eS = eS; G.eH = eH; G.eW = eW;
+  G.B = B; G.S = S; G.H = H; G.W = W; G.heads = heads; G.dh = dh; G.eS = eS; G.eSf = eSf; G.eH = eH; G.eW = eW;
   G.ldq = ldq; G.ldk = ldk; G.ldv = ldv; G.ldo = ldo;
   G.HW = H * W; G.tiles = (G.HW + 15) / 16; G.qgroups = 0;
   G.qs0 = q_plane0; G.Sq = q_planes;

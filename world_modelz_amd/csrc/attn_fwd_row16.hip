@@ -125,7 +125,7 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
   // key rows the workgroup stages (this geometry, the plane order and next_state() / advance() below: attn_slab_walk.h states them
   // once and tests/test_attn_slab_walk_cpu.py pins them -- keep the two in step)
   const int t_lo = max(h0 - eHv, 0), t_hi = min(min(h0 + NW - 1, H - 1) + eHv, H - 1);
-  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eS);
+  const int sk_lo = max(0, s - G.eS), sk_hi = min(G.S - 1, s + G.eSf);
   const int c_first = t_lo >> LOG_CH, c_last = t_hi >> LOG_CH;
   const int nch = (c_last - c_first + 1) * RS;              // slabs per key plane: (chunk) x (row phase)
   const int nslab = (WMZ_ATTN_ABL & 32) ? 0 : (WMZ_ATTN_ABL & 64) ? nch : (sk_hi - sk_lo + 1) * nch;   // ablations: no slab loop / one key plane
@@ -154,7 +154,8 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
   // between.  The softmax is order-independent (online), the logits probe records the plane it actually visits.
   // (The phase counts planes from the END of the clip: the trailing-planes entry point hands over only the last planes of a
   // clip, and its visiting order -- hence every rounding -- must be the full grid's.)
-  const int nwin = 2 * G.eS + 1;
+  // (An asymmetric time window s - eS .. s + eSf rotates the same way, by its own length.)
+  const int nwin = G.eS + G.eSf + 1;
   int p_first = s - G.eS;
   { const int a = (((G.S - 1 - p_first) % nwin) + nwin) % nwin; p_first += a; }          // first plane of the window with S-1-p = 0 (mod nwin)
   if (p_first > sk_hi || p_first < sk_lo) p_first = sk_lo;
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(SH::NW * 64, 4) void attn_fwd_row16_kernel(const bf
       auto probe_row = [&](int t, const f32x4& sc) {
         const int kw = (2 * G.eW + 1), kh = (2 * G.eH + 1);
         const long qn = plane_o + hq * 16 + li;
-        const int nk = (2 * G.eS + 1) * kh * kw;
+        const int nk = (G.eS + G.eSf + 1) * kh * kw;
         const int ds = (sk_lo + pl) - s;
         const int D = base + RS * t - hq;
         const int dh = W8 ? 2 * D + dp : (W32 ? w32_dh(hq, base + RS * t) : D);                  // in plane rows

@@ -19,6 +19,7 @@
 //   * block -> (batch, query plane) and the rotated order's phase by the host's multipliers (div_m31), token indices in 32 bits:
 //     wmz_attn_fwd_row16_infer_takes bounds the launch accordingly.
 // Left at run time: B, S, eS, the query planes (qs0, Sq: the cone and the sampler pass trailing planes) and the pointers.
+// The time window is the symmetric one: a launch with eSf != eS (a causal model) is not the unit's and runs the run-time row kernel.
 // Measurements, the listing's instruction counts and what was tried: profiles/attn_infer_unit/README.md.
 // bfloat16 only: no *_f16.hip unit includes this file.
 #include "attn_row16_step.h"
@@ -322,7 +323,7 @@ int launch_infer(const void* q, const void* k, const void* v, void* out, const A
 // Whether a launch is the unit's: what the kernels above fix at compile time (attn_fwd_impl adds what it alone knows: the dtype,
 // no LSE, no probe, no stamp buffer).
 bool wmz_attn_fwd_row16_infer_takes(const AttnGeom& G) {
-  return G.W == 16 && G.H == 16 && G.dh == 128 && G.heads == 1 && G.ldq == 128 && G.ldk == 128 && G.ldv == 128 && G.ldo == 128 &&
+  return G.eSf == G.eS && G.W == 16 && G.H == 16 && G.dh == 128 && G.heads == 1 && G.ldq == 128 && G.ldk == 128 && G.ldv == 128 && G.ldo == 128 &&
          ((G.eH == 3 && G.eW == 3) || (G.eH == 1 && G.eW == 1)) && G.dbg == 0 && G.variant == 0 && G.w8 == 0 &&
          (long)G.B * G.S * 256 <= (1l << 31) && (long)G.B * G.Sq * G.Sq <= (1l << 31) && ((long)G.S + G.eS) * (2l * G.eS + 1) <= (1l << 31);       // 32-bit tokens, div_m31's range
 }

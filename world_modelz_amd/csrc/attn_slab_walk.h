@@ -26,13 +26,16 @@ struct SlabGeom { int H, s_last, t_lo, t_hi, sk_lo, sk_hi, c_first, nch, nslab; 
 // between.  The softmax is order-independent (online), the logits probe records the plane it actually visits.
 // (The phase counts planes from the END of the clip: the trailing-planes entry point hands over only the last planes of a
 // clip, and its visiting order -- hence every rounding -- must be the full grid's.)
-WMZ_HD int slab_first_plane(const SlabGeom& g, int eS, int s) {
-  const int nwin = 2 * eS + 1;
-  int p_first = s - eS;
+// The time window is a pair: the owner plane s sees the planes s - eSb .. s + eSf (symmetric: eSb == eSf == eS; causal: eSf == 0;
+// the dk | dv role, whose owners are keys, takes the swapped pair).  Its eSb + eSf + 1 planes rotate as above, by that length.
+WMZ_HD int slab_first_plane(const SlabGeom& g, int eSb, int eSf, int s) {
+  const int nwin = eSb + eSf + 1;
+  int p_first = s - eSb;
   { const int a = (((g.s_last - p_first) % nwin) + nwin) % nwin; p_first += a; }         // first plane of the window with S-1-p = 0 (mod nwin)
   if (p_first > g.sk_hi || p_first < g.sk_lo) p_first = g.sk_lo;
   return p_first;
 }
+WMZ_HD int slab_first_plane(const SlabGeom& g, int eS, int s) { return slab_first_plane(g, eS, eS, s); }
 
 // A plane is cut into chunks of CH rows, a slab holds every RS-th row of a chunk (KC = CH / RS rows: plane row = base + RS * slab
 // row).  eHv: the window's row extent in tile rows.  CLAMP = false is the whole-plane form (H % CH == 0 and NW == CH: no owner row
@@ -40,19 +43,21 @@ WMZ_HD int slab_first_plane(const SlabGeom& g, int eS, int s) {
 // give min(h0 + NW - 1 + eHv, H - 1) -- and dlim stays CH - RS without CLAMP: they are the kernels' own expressions, kept so that
 // this code and theirs can be held side by side.)
 template <int CH, int KC, bool CLAMP = true>
-WMZ_HD SlabGeom slab_geom(int H, int S, int eS, int eHv, int h0, int NW, int s) {
+WMZ_HD SlabGeom slab_geom(int H, int S, int eSb, int eSf, int eHv, int h0, int NW, int s) {
   constexpr int RS = CH / KC, LOG_CH = slab_log2(CH);
   static_assert(KC * RS == CH && (1 << LOG_CH) == CH && (1 << slab_log2(RS)) == RS, "a slab is one phase of a chunk of 2^n rows");
   SlabGeom g;
   g.H = H;
   g.t_lo = slab_max(h0 - eHv, 0);
   g.t_hi = slab_min((CLAMP ? slab_min(h0 + NW - 1, H - 1) : h0 + NW - 1) + eHv, H - 1);
-  g.sk_lo = slab_max(0, s - eS); g.s_last = S - 1; g.sk_hi = slab_min(g.s_last, s + eS);
+  g.sk_lo = slab_max(0, s - eSb); g.s_last = S - 1; g.sk_hi = slab_min(g.s_last, s + eSf);
   g.c_first = g.t_lo >> LOG_CH;
   g.nch = ((g.t_hi >> LOG_CH) - g.c_first + 1) * RS;        // slabs per plane: (chunk) x (row phase)
   g.nslab = (g.sk_hi - g.sk_lo + 1) * g.nch;
   return g;
 }
+template <int CH, int KC, bool CLAMP = true>
+WMZ_HD SlabGeom slab_geom(int H, int S, int eS, int eHv, int h0, int NW, int s) { return slab_geom<CH, KC, CLAMP>(H, S, eS, eS, eHv, h0, NW, s); }
 
 // The slab being prefetched: plane (from sk_lo), slab in the plane, first row, index; and where its DMA may read: bsafe, the
 // row the fetch starts from, and dlim, the last row offset piece_voff may add to it.

@@ -20,7 +20,7 @@ LN_EPS = 1e-5
 class _AttentionBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_kv, x_q, ln_g, ln_b, wq, wk, wv, bv, wout, bout, residual, extents, heads, grad_on, same_src,
-                res_is_xkv, out_f32=False):
+                res_is_xkv, out_f32=False, time_window=None):
         dt = x_kv.dtype
         I = wq.shape[0]
         ln = None if ln_g is None else (ln_g.detach(), ln_b.detach())
@@ -37,7 +37,7 @@ class _AttentionBlock(torch.autograd.Function):
             kv, _, xn = ops.linear_fwd_train(x_kv, wkv_c, bkv, ln, LN_EPS, stats, want_norm=True)     # (+ LN(x) for the weight gradient)
         else:
             kv = ops.linear_fwd(x_kv, wkv_c, bias=bkv, ln=ln, ln_eps=LN_EPS, ln_stats=stats)   # to_k | to_v on LN(x)
-        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I], kv[..., I:], extents, heads, need_lse=need_bwd)
+        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I], kv[..., I:], extents, heads, need_lse=need_bwd, time_window=time_window)
         if wout is not None:
             # (inference at a module boundary that wants fp32 back -- Local3dAttention.forward on fp32 inputs: the to_out GEMM's
             #  epilogue writes it, instead of a cast launch behind the block)
@@ -47,6 +47,7 @@ class _AttentionBlock(torch.autograd.Function):
         if need_bwd:
             ctx.save_for_backward(x_kv, x_q, ln_g, ln_b, wq, wk, wv, bv, wout, bout, q, kv, o, lse)
             ctx.extents, ctx.heads, ctx.has_res = extents, heads, residual is not None
+            ctx.time_window = time_window
             ctx.ln_stats = stats
             ctx.xn = xn                    # LN(x_kv) as the k | v GEMM consumed it (None: the weight gradient re-normalises)
             # gradient folding is decided by autograd identity of the caller's tensors (attention_block), never by
@@ -57,7 +58,7 @@ class _AttentionBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         from . import backward as B
-        return B.attention_block_backward(ctx, dy) + (None,)
+        return B.attention_block_backward(ctx, dy) + (None, None)
 
 
 class _FeedForwardBlock(torch.autograd.Function):
@@ -135,10 +136,10 @@ def _as_compute(x):
     return x if x.dtype == dt else x.to(dt)
 
 
-def attention_block(x_kv, x_q, ln, wq, wk, wv, bv, wout, bout, residual, extents, heads, out_f32=False):
+def attention_block(x_kv, x_q, ln, wq, wk, wv, bv, wout, bout, residual, extents, heads, out_f32=False, time_window=None):
     g, b = (None, None) if ln is None else ln
     return _AttentionBlock.apply(x_kv, x_q, g, b, wq, wk, wv, bv, wout, bout, residual, tuple(int(e) for e in extents),
-                                 int(heads), torch.is_grad_enabled(), x_q is x_kv, residual is x_kv, bool(out_f32))
+                                 int(heads), torch.is_grad_enabled(), x_q is x_kv, residual is x_kv, bool(out_f32), time_window)
 
 
 def feed_forward_block(x, ln, w1, b1, w2, b2, residual):

@@ -237,7 +237,7 @@ def transformer_forward_chain(tr, z):
     _, q, kv = launch(None, x, None, layers[0])
     for l, (attn, ff) in enumerate(layers):
         heads, ext = attn.fn.heads, attn.fn.extents
-        o, _, _ = ops.local3d_attention_fwd(q, kv[0], kv[1], ext, heads)
+        o, _, _ = ops.local3d_attention_fwd(q, kv[0], kv[1], ext, heads, time_window=attn.fn.time_window)
         x, q, kv = launch(o, x, (attn, ff), layers[l + 1] if l + 1 < len(layers) else None)
     return x
 
@@ -408,7 +408,8 @@ def _chain_stack_train(tr, packs, z, kernel_bwd):
     empty = x0.new_empty(0)
     for l, (attn, ff) in enumerate(layers):
         q, kv = cur['q'].view(B, S, H, W, I), cur['kv'].view(B, S, H, W, 2 * I)
-        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I], kv[..., I:], attn.fn.extents, attn.fn.heads, need_lse=True)
+        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I], kv[..., I:], attn.fn.extents, attn.fn.heads, need_lse=True,
+                                              time_window=attn.fn.time_window)
         nxt = _chain_layer_train(packs, l + 1, o, x_in, True, l + 1 < len(layers), not kernel_bwd)
         saved += [x_in, q, kv, o, lse, nxt.get('x1', empty), cur['st_attn'], nxt['st_ff'], nxt['z'], nxt['h'], cur['xh_attn'],
                   nxt['xh_ff']]
@@ -429,7 +430,8 @@ def _chain_layer_backward(packs, l, attn, ff, dy, x_in, q, kv, o, lse, x1, st_at
     do = torch.empty(o.shape, dtype=bf, device=dev)
     L.call('wmz_chain_ff_bwd', L.ptr(dy2), L.ptr(z), L.ptr(xh_ff), L.ptr(st_ff[1]), L.ptr(dz), L.ptr(dx1), L.ptr(do),
            L.ptr(packs.stream('ff_bwd', l)), ntok, D, I, M, L.stream())
-    dq, dkv = ops.local3d_attention_bwd(q, kv[..., :I], kv[..., I:], o, lse, do, attn.fn.extents, attn.fn.heads)
+    dq, dkv = ops.local3d_attention_bwd(q, kv[..., :I], kv[..., I:], o, lse, do, attn.fn.extents, attn.fn.heads,
+                                        time_window=attn.fn.time_window)
     dx = torch.empty(dy.shape, dtype=bf, device=dev)
     L.call('wmz_chain_qkv_bwd', L.ptr(dq), L.ptr(dkv), L.ptr(xh_attn), L.ptr(st_attn[1]), L.ptr(dx1), L.ptr(dx),
            L.ptr(packs.stream('qkv_bwd', l)), ntok, D, I, L.stream())
@@ -671,9 +673,15 @@ def _run_chain(tr, z, cone, out):
         n_in, n_q = src[l], need[l]
         heads, ext = attn.fn.heads, attn.fn.extents
         o = torch.empty((B, n_q, H, W, I_), dtype=bf, device=dev)
-        L.call('wmz_local3d_attn_fwd_planes', L.ptr(q), L.ptr(kv[0]), L.ptr(kv[1]), L.ptr(o), None,
-               B, n_in, H, W, heads, I_ // heads, int(ext[0]), int(ext[1]), int(ext[2]), I_, I_, I_, I_,
-               n_in - n_q, n_q, L.dtype_code(bf), L.stream())
+        win = attn.fn.time_window
+        if win is None:
+            L.call('wmz_local3d_attn_fwd_planes', L.ptr(q), L.ptr(kv[0]), L.ptr(kv[1]), L.ptr(o), None,
+                   B, n_in, H, W, heads, I_ // heads, int(ext[0]), int(ext[1]), int(ext[2]), I_, I_, I_, I_,
+                   n_in - n_q, n_q, L.dtype_code(bf), L.stream())
+        else:                                  # a causal model: the same trailing planes, the one-sided time window
+            L.call('wmz_local3d_attn_fwd_window', L.ptr(q), L.ptr(kv[0]), L.ptr(kv[1]), L.ptr(o), None, None,
+                   B, n_in, H, W, heads, I_ // heads, win[0], win[1], int(ext[1]), int(ext[2]), I_, I_, I_, I_,
+                   n_in - n_q, n_q, 0, L.dtype_code(bf), L.stream())
         tail = layers[l + 1] if l + 1 < depth else None
         wpack, vec = _layer_pack((attn, ff), tail, bf)
         xo = out if (tail is None and out is not None) else torch.empty((B, n_q, H, W, D_), dtype=bf, device=dev)
@@ -863,7 +871,8 @@ def _fused_stack_train(tr, z, kernel_bwd):
     x_cur, x_rm, q, kv, st_attn = _embed_train(tr, z, tiled, xhat_rm)
     saved = []
     for l, (attn, ff) in enumerate(layers):
-        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I_], kv[..., I_:], attn.fn.extents, attn.fn.heads, need_lse=True)
+        o, lse, _ = ops.local3d_attention_fwd(q, kv[..., :I_], kv[..., I_:], attn.fn.extents, attn.fn.heads, need_lse=True,
+                                              time_window=attn.fn.time_window)
         x_in_rm, x_in_t = x_rm, (x_cur if xhat_rm else lse.new_empty(0))
         x_cur, x_rm, x1, q_n, kv_n, st_ff, st_attn_n, zt = _layer_train(o, x_cur, (attn, ff),
                                                                        layers[l + 1] if l + 1 < len(layers) else None,
@@ -896,7 +905,8 @@ def _layer_backward_fused(attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff,
     else:                               # dW2 = dy^T GELU(z) only has the last planes' rows to sum over
         dy2, g2 = dy.reshape(-1, D_), g.view(-1, S_, HW_, M_)[:, -1].reshape(-1, M_)
     # ---- attention core
-    dq, dkv = ops.local3d_attention_bwd(q, kv[..., :I_], kv[..., I_:], o, lse, do, attn.fn.extents, attn.fn.heads)
+    dq, dkv = ops.local3d_attention_bwd(q, kv[..., :I_], kv[..., I_:], o, lse, do, attn.fn.extents, attn.fn.heads,
+                                        time_window=attn.fn.time_window)
     # ---- to_q / to_k / to_v inputs
     dx = torch.empty(lead + (D_,), dtype=bf, device=dev)
     tiled = x_in_t.numel() > 0
@@ -936,7 +946,8 @@ def _layer_backward_ops(attn, ff, dy, x_in, q, kv, o, lse, x1, st_attn, st_ff, z
     dx1, g_fg, g_fb, g_w1, g_b1, g_w2, g_b2 = Bk.feed_forward_block_backward(cf, dy)[:7]
     # attention block: x1 = to_out(attn(LN(x), q = x)) + x
     ca = _Ctx((x_in, x_in, an_g, an_b, wq, wk, wv, bv, wout, bout, q, kv, o, lse), extents=attn.fn.extents,
-              heads=attn.fn.heads, has_res=True, res_is_xkv=True, same_src=True, ln_stats=(st_attn[0], st_attn[1]))
+              heads=attn.fn.heads, has_res=True, res_is_xkv=True, same_src=True, ln_stats=(st_attn[0], st_attn[1]),
+              time_window=attn.fn.time_window)
     r = Bk.attention_block_backward(ca, dx1)
     return r[0], [r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], g_fg, g_fb, g_w1, g_b1, g_w2, g_b2]
 

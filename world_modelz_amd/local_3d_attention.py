@@ -88,11 +88,14 @@ class Local3dAttention(nn.Module):
 
     `forward(x, q)`: keys/values are projected from x, queries from q; every token attends to its
     (2eS+1)(2eH+1)(2eW+1) neighbourhood clipped to the grid.  `use_checkpointing` is accepted for signature
-    compatibility: the HIP forward keeps only the per-row log-sum-exp, so there is nothing to checkpoint."""
+    compatibility: the HIP forward keeps only the per-row log-sum-exp, so there is nothing to checkpoint.
+    `causal` (the reference's open item `# todo: add causal masking`): plane s attends to the planes s - eS .. s only, so no
+    activation of a frame depends on a later frame; the window inside a plane is unchanged."""
 
-    def __init__(self, extents, dim, heads=8, dim_head=64, dropout=.0, use_checkpointing=True):
+    def __init__(self, extents, dim, heads=8, dim_head=64, dropout=.0, use_checkpointing=True, causal=False):
         super().__init__()
         self.extents = extents
+        self.causal = bool(causal)
         inner = dim_head * heads
         self.heads = heads
         self.scale = dim_head ** -0.5
@@ -106,6 +109,13 @@ class Local3dAttention(nn.Module):
             self.to_out = nn.Sequential(nn.Linear(inner, dim), nn.Dropout(dropout))
         self.use_checkpointing = use_checkpointing
         self.dropout = dropout
+
+    @property
+    def time_window(self):
+        """What every attention launch of this module passes as time_window: (eS, 0) when causal, else None (the symmetric entry
+        points)."""
+        from . import ops
+        return ops.causal_window(self.extents, self.causal)
 
     def _run(self, x, q, ln, residual, out_f32=False):
         same, res_same = q is x, residual is x            # attn(x, q=x) + x: keep ONE tensor so the backward folds the paths
@@ -123,11 +133,12 @@ class Local3dAttention(nn.Module):
         if self.dropout > 0 and self.training and wo is not None:
             # to_out = Linear -> Dropout (local_3d_attention.py:50-53): the fused block without its residual, the mask and the
             # residual add as torch device ops behind it (not a fused path: the reference default and every published run use 0)
-            y = Fw.attention_block(x, q, ln, wq, wk, wv, bv, wo, bo, None, self.extents, self.heads)
+            y = Fw.attention_block(x, q, ln, wq, wk, wv, bv, wo, bo, None, self.extents, self.heads, time_window=self.time_window)
             y = torch.nn.functional.dropout(y, self.dropout, True)
             y = y if residual is None else y + residual
             return y.reshape(q.shape[:-1] + (y.shape[-1],))
-        y = Fw.attention_block(x, q, ln, wq, wk, wv, bv, wo, bo, residual, self.extents, self.heads, out_f32=out_f32)
+        y = Fw.attention_block(x, q, ln, wq, wk, wv, bv, wo, bo, residual, self.extents, self.heads, out_f32=out_f32,
+                               time_window=self.time_window)
         return y.reshape(q.shape[:-1] + (y.shape[-1],))
 
     def _head_padded(self):
@@ -168,7 +179,7 @@ class Local3dAttention(nn.Module):
                 return F.pad(t.reshape(t.shape[:-1] + (self.heads, dh)) * scale, (0, pad)).reshape(t.shape[:-1] + (-1,))
             q, k, v = heads_padded(q, ((dh + pad) / dh) ** 0.5), heads_padded(k), heads_padded(v)
         k, v, q = Fw._as_compute(k), Fw._as_compute(v), Fw._as_compute(q)
-        out, _, _ = ops.local3d_attention_fwd(q, k, v, self.extents, self.heads)
+        out, _, _ = ops.local3d_attention_fwd(q, k, v, self.extents, self.heads, time_window=self.time_window)
         out = out.reshape(-1, self.heads, 1, out.shape[-1] // self.heads)
         return (out[..., :dh] if pad else out).to(dt_in)
 
@@ -177,9 +188,10 @@ class Local3dAttentionTransformer(nn.Module):
     """Token + 3-axis position embedding followed by depth x [attention, feed-forward] with residuals and no
     final LayerNorm (reference :121-163)."""
 
-    def __init__(self, *, data_shape, dim, num_classes, extents, depth, heads, dim_head, mlp_dim, dropout=.0):
+    def __init__(self, *, data_shape, dim, num_classes, extents, depth, heads, dim_head, mlp_dim, dropout=.0, causal=False):
         super().__init__()
         self.num_classes = num_classes
+        self.causal = bool(causal)
         self.embedding = nn.Embedding(num_classes, dim)
         self.pos_emb_s = nn.Embedding(data_shape[0], dim)
         self.pos_emb_h = nn.Embedding(data_shape[1], dim)
@@ -187,7 +199,7 @@ class Local3dAttentionTransformer(nn.Module):
         self.layers = nn.ModuleList([])
         for _ in range(depth):
             self.layers.append(nn.ModuleList([
-                PreNorm(dim, Local3dAttention(extents, dim, heads=heads, dim_head=dim_head, dropout=dropout)),
+                PreNorm(dim, Local3dAttention(extents, dim, heads=heads, dim_head=dim_head, dropout=dropout, causal=causal)),
                 PreNorm(dim, FeedForward(dim, mlp_dim, dropout=dropout)),
             ]))
 

@@ -8,13 +8,15 @@ from .local_3d_attention import Local3dAttentionTransformer
 
 class VqVideoDiffusionModel(nn.Module):
     """Denoiser: tokens [B,S,H,W] (vocabulary num_classes + 1, the extra id is the mask token) ->
-    fp32 logits [B,H,W,num_classes] of the LAST frame only (reference :33-36; quirk Q5)."""
+    fp32 logits [B,H,W,num_classes] of the LAST frame only (reference :33-36; quirk Q5).  causal: every attention layer's time
+    window is one-sided (Local3dAttention), so no context frame's activation depends on the frame being generated."""
 
-    def __init__(self, *, data_shape, dim, num_classes, extents, depth, dim_head, mlp_dim, heads=1, dropout=.0):
+    def __init__(self, *, data_shape, dim, num_classes, extents, depth, dim_head, mlp_dim, heads=1, dropout=.0, causal=False):
         super().__init__()
+        self.causal = bool(causal)
         self.transformer = Local3dAttentionTransformer(data_shape=data_shape, dim=dim, num_classes=num_classes + 1,
                                                        extents=extents, depth=depth, heads=heads, dim_head=dim_head,
-                                                       mlp_dim=mlp_dim, dropout=dropout)
+                                                       mlp_dim=mlp_dim, dropout=dropout, causal=causal)
         self.logit_proj = nn.Linear(dim, num_classes)
 
     def forward(self, x):

@@ -30,9 +30,16 @@ def _out_rows(out, M, dtype):
     return out, ld
 
 
-def local3d_attention_fwd(q, k, v, extents, heads, need_lse=False, logits_dbg=False, general=False):
+def causal_window(extents, causal):
+    """The time_window of a model's attention launches: None (the symmetric entry points) unless the model is causal."""
+    return (int(extents[0]), 0) if causal else None
+
+
+def local3d_attention_fwd(q, k, v, extents, heads, need_lse=False, logits_dbg=False, general=False, time_window=None):
     """q, k, v: [B,S,H,W,heads*dh] (last dim contiguous, uniform row stride).  Returns (out, lse, logits).
-    general: take the general kernel even where the 16-wide-plane fast path applies (parity tests)."""
+    general: take the general kernel even where the 16-wide-plane fast path applies (parity tests).
+    time_window = (back, fwd): query plane s sees the key planes s - back .. s + fwd instead of s -+ extents[0] (wmz_local3d_attn_fwd_
+    window; the probe then has back + fwd + 1 plane slots); None: the symmetric entry points."""
     B, S, H, W, I = q.shape
     dh = I // heads
     dt = L.dtype_code(q.dtype)
@@ -44,8 +51,14 @@ def local3d_attention_fwd(q, k, v, extents, heads, need_lse=False, logits_dbg=Fa
     lse = torch.empty((N, heads), dtype=torch.float32, device=q.device) if need_lse else None
     dbg = None
     if logits_dbg:
-        K = (2 * extents[0] + 1) * (2 * extents[1] + 1) * (2 * extents[2] + 1)
+        planes = 2 * extents[0] + 1 if time_window is None else int(time_window[0]) + int(time_window[1]) + 1
+        K = planes * (2 * extents[1] + 1) * (2 * extents[2] + 1)
         dbg = torch.full((N, heads, K), -1e9, dtype=torch.float32, device=q.device)
+    if time_window is not None:
+        L.call('wmz_local3d_attn_fwd_window', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(dbg), B, S, H, W, heads, dh,
+               int(time_window[0]), int(time_window[1]), int(extents[1]), int(extents[2]), ldq, ldk, ldv, I, 0, S, int(general), dt,
+               L.stream())
+        return out, lse, dbg
     L.call('wmz_local3d_attn_fwd_general' if general else 'wmz_local3d_attn_fwd', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out),
            L.ptr(lse), L.ptr(dbg),
            B, S, H, W, heads, dh, int(extents[0]), int(extents[1]), int(extents[2]), ldq, ldk, ldv, I, dt, L.stream())
@@ -416,10 +429,11 @@ def vq_ema_update(embedding, cluster_size, activation_count, counts, dw, decay, 
 
 # ------------------------------------------------------------------------------------------------ backward
 
-def local3d_attention_bwd(q, k, v, out, lse, dout, extents, heads, dqkv=None, general=False):
+def local3d_attention_bwd(q, k, v, out, lse, dout, extents, heads, dqkv=None, general=False, time_window=None):
     """Returns (dq, dkv) with dkv = [..., 2I] holding dk | dv (the layout the fused k|v projection wants).
     dqkv (optional, [..., 3I]): write dq | dk | dv into its column thirds instead (fused to_qkv of config 5).
-    general: take the general kernels even where the row kernels apply (parity tests, A/B timings)."""
+    general: take the general kernels even where the row kernels apply (parity tests, A/B timings).
+    time_window = (back, fwd): the forward's (wmz_local3d_attn_bwd_window); None: the symmetric entry points."""
     B, S, H, W, I = q.shape
     dh = I // heads
     dt = L.dtype_code(q.dtype)
@@ -439,6 +453,11 @@ def local3d_attention_bwd(q, k, v, out, lse, dout, extents, heads, dqkv=None, ge
         dq, dk, dv = dqkv[..., :I], dqkv[..., I:2 * I], dqkv[..., 2 * I:]
         dkv = dqkv[..., I:]
         lddq = lddkv = 3 * I
+    if time_window is not None:
+        L.call('wmz_local3d_attn_bwd_window', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(dout), L.ptr(dq), L.ptr(dk),
+               L.ptr(dv), L.ptr(delta), B, S, H, W, heads, dh, int(time_window[0]), int(time_window[1]), int(extents[1]),
+               int(extents[2]), ldq, ldk, ldv, ldo, lddo, lddq, lddkv, lddkv, int(general), dt, L.stream())
+        return dq, dkv
     L.call('wmz_local3d_attn_bwd_general' if general else 'wmz_local3d_attn_bwd', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(dout), L.ptr(dq),
            L.ptr(dk), L.ptr(dv), L.ptr(delta), B, S, H, W, heads, dh, int(extents[0]), int(extents[1]),
            int(extents[2]), ldq, ldk, ldv, ldo, lddo, lddq, lddkv, lddkv, dt, L.stream())
