@@ -379,6 +379,24 @@ int wmz_embed_qkv_fused_fwd_planes(const int64_t* z, const float* emb, const flo
                                    const float* vec, int B, int S, int H, int W, int planes_out, int D, int I, int M,
                                    int num_classes, int xflags, float eps, void* stream);
 
+/* ---- the context cache's forms of the two trailing-planes launches above (causal models: a context plane's q / k / v do not
+ * depend on the frame being generated, so a sampler computes them once per frame and only the generated plane per denoise
+ * iteration; world_modelz_amd/fused.py ContextCache).  Same arguments, same arithmetic per token and the same x_out (compact,
+ * tiled or row-major as asked); q_out and kv_out hold dst_planes plane SLOTS per clip -- q [B, dst_planes, HW, I],
+ * kv [2, B, dst_planes, HW, I] -- and the launch writes the slots dst_plane0 .. dst_plane0 + planes_out - 1 of each clip and no
+ * other byte: row t of the compact grid goes to row (t / rows_out) rows_dst + row0_dst + t % rows_out with rows_out =
+ * planes_out HW, rows_dst = dst_planes HW, row0_dst = dst_plane0 HW (csrc/fused_row_maps.h states this map and the source map
+ * of the trailing planes), the v rows B dst_planes HW rows behind the k rows.  dst_planes = planes_out, dst_plane0 = 0 is the
+ * compact layout.  The attention entry points read the slots in place (S = dst_planes).  Refused: dst_plane0 < 0,
+ * dst_plane0 + planes_out > dst_planes.  has_tail == 0 (the last layer) places nothing: the trailing-planes launch as it is. */
+int wmz_layer_fused_fwd_slots(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                              const float* vec, int B, int planes_out, int planes_in, int HW, int D, int I, int M,
+                              int has_head, int has_tail, int xflags, float eps, int dst_planes, int dst_plane0, void* stream);
+int wmz_embed_qkv_fused_fwd_slots(const int64_t* z, const float* emb, const float* pos_s, const float* pos_h,
+                                  const float* pos_w, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                                  const float* vec, int B, int S, int H, int W, int planes_out, int D, int I, int M,
+                                  int num_classes, int xflags, float eps, int dst_planes, int dst_plane0, void* stream);
+
 /* ---- the PRECISE fused inference mode: the same kernels with IEEE-half MFMA operands and a half residual stream between the
  * layers (same matrix rate as bf16, 11 significand bits instead of 8).  The reference computes in fp32
  * (local_3d_attention.py:78-118); BASELINE.json asks for attention logits within 1e-3 relative of it, which bf16 operands miss
@@ -401,6 +419,14 @@ int wmz_embed_qkv_fused_fwd_planes_f16(const int64_t* z, const float* emb, const
                                        const float* pos_w, void* x_out, void* q_out, void* kv_out, const void* wpack,
                                        const float* vec, int B, int S, int H, int W, int planes_out, int D, int I, int M,
                                        int num_classes, int xflags, float eps, void* stream);
+/* (the half forms of the context cache's launches: `_f16_slots`, the slots form of the `_f16` entry point) */
+int wmz_layer_fused_fwd_f16_slots(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                                  const float* vec, int B, int planes_out, int planes_in, int HW, int D, int I, int M,
+                                  int has_head, int has_tail, int xflags, float eps, int dst_planes, int dst_plane0, void* stream);
+int wmz_embed_qkv_fused_fwd_f16_slots(const int64_t* z, const float* emb, const float* pos_s, const float* pos_h,
+                                      const float* pos_w, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                                      const float* vec, int B, int S, int H, int W, int planes_out, int D, int I, int M,
+                                      int num_classes, int xflags, float eps, int dst_planes, int dst_plane0, void* stream);
 int wmz_layer_fused_pack_f16(const float* wout, const float* bout, const float* g2, const float* be2, const float* w1,
                              const float* b1, const float* w2, const float* b2, const float* g1, const float* be1,
                              const float* wq, const float* wk, const float* wv, const float* bv, void* wpack, float* vec,

@@ -166,6 +166,35 @@ def last_frame_cone(on):
         set_last_frame_cone(prev)
 
 
+# Inference only, causal models on the fused widths: under the causal window no context plane depends on the frame being generated,
+# so the sampler can compute the context planes' K / V once per frame (fused.context_prefill) and only the generated plane per
+# denoise iteration (VqVideoDiffusionModel.forward_last) -- same logits bit for bit, about a seventh of the tokens per iteration.
+# Off by default: the decode launches are small and latency-bound, what they gain is a measurement
+# (profiles/context_cache/README.md).  sample.sample_frames reads this when its context_cache argument is None; a model that is
+# not eligible (VqVideoDiffusionModel.context_cache_eligible) keeps the uncached path.  The cached passes run as one chain of
+# launches: clip_streams below does not apply to them.
+_context_cache = os.environ.get('WMZ_CONTEXT_CACHE', '0') != '0'
+
+
+def get_context_cache():
+    return _context_cache
+
+
+def set_context_cache(on):
+    global _context_cache
+    _context_cache = bool(on)
+
+
+@contextlib.contextmanager
+def context_cache(on):
+    prev = get_context_cache()
+    set_context_cache(on)
+    try:
+        yield
+    finally:
+        set_context_cache(prev)
+
+
 # Training forward of the denoiser on the fused or chain kernels (bf16): one attention launch + one per-token launch per layer
 # instead of six.  Off: the op-by-op forward.
 _fused_training = os.environ.get('WMZ_FUSED_TRAINING', '1') != '0'

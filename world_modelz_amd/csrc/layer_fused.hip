@@ -23,6 +23,7 @@
 //     exists in full and the chunk's accumulator (16 registers) is converted in place to the next operand.
 #include "fused_common.h"
 #include "fused_pack_rows.h"
+#include "fused_row_maps.h"
 #include "wmz_debug.h"
 #include <atomic>
 
@@ -60,6 +61,9 @@ struct FusedParams {
   // (hidden units 32c + 16h + 8j ..) at ((2c + j) * 64 + lane) * 16 bytes: every store instruction is one contiguous KB
   bf16_t* zt;
   long long* ts;        // timing probe (wmz_debug_fused_timestamps): workgroup 0 writes s_memtime at stage boundaries
+  // destination map of q and k | v (the _slots forms, OptSlots; fused_row_maps.h): row t of the compact grid is written to row
+  // (t / rows_out) * rows_dst + row0_dst + t % rows_out, the v rows dst_total rows behind the k rows
+  int rows_dst, row0_dst; long dst_total;
 };
 // stage-boundary probe: wave w of workgroup 0 stores the shader clock into ts[w * 64 + slot]
 #define WMZ_TS(slot)                                                                                      \
@@ -71,6 +75,7 @@ struct FusedParams {
 // OptRuntime: from the kernel arguments, all of them -- layer_fused_kernel, every caller's kernel.
 struct OptRuntime {
   static constexpr bool kFixed = false;
+  static constexpr bool kDstMap = false;     // q and k | v rows go where the compact grid puts them
   static constexpr int kXflags = 0;          // (unused: the layout is an argument)
   typedef WStreamT<false> Stream;
   // cache policy of the stores by class (mem_policy.h) -- the tiled stream, q, k | v: plain
@@ -81,11 +86,18 @@ struct OptRuntime {
   __device__ static __forceinline__ int kv_combined(const FusedParams& P) { return P.kv_combined; }
   __device__ static __forceinline__ int dbg(const FusedParams& P) { return P.dbg; }
   __device__ static __forceinline__ long long* ts(const FusedParams& P) { return P.ts; }
-  __device__ static __forceinline__ long src_row(const FusedParams& P, long t) {
-    if (P.rows_out == 0) return t;
-    const int c = (int)t / P.rows_out;
-    return (long)c * P.rows_in + P.row0 + ((int)t - c * P.rows_out);
-  }
+  __device__ static __forceinline__ long src_row(const FusedParams& P, long t) { return fused_src_row(P.rows_out, P.rows_in, P.row0, t); }
+};
+// OptSlots: OptRuntime for the context cache's launches (wmz_*_fwd_slots) -- inference only (no training outputs, k rows then v
+// rows, no ablation switches, no probes), and q and k | v leave through the destination map: into plane slots of buffers that hold
+// more planes than the launch computes.  Instantiated for those entry points alone.
+struct OptSlots : OptRuntime {
+  static constexpr bool kDstMap = true;
+  template <typename T> __device__ static __forceinline__ T* train(T*) { return nullptr; }
+  __device__ static __forceinline__ int kv_combined(const FusedParams&) { return 0; }
+  __device__ static __forceinline__ int dbg(const FusedParams&) { return 0; }
+  __device__ static __forceinline__ long long* ts(const FusedParams&) { return nullptr; }
+  __device__ static __forceinline__ long dst_row(const FusedParams& P, long t) { return fused_dst_row(P.rows_out, P.rows_dst, P.row0_dst, t); }
 };
 // OptInfer: at compile time -- the plain inference launch of the full grid (layer_fused_infer_kernel; fused_launch checks what
 // is assumed here).  Whole 256-token workgroups (no row guards, no clamps, wave-uniform bases with 32-bit lane offsets), the
@@ -95,6 +107,7 @@ struct OptRuntime {
 template <int XFLAGS>
 struct OptInfer {
   static constexpr bool kFixed = true;
+  static constexpr bool kDstMap = false;
   static constexpr int kXflags = XFLAGS;
   typedef WStreamT<true> Stream;
   // the tiled stream, q and k | v are read once, by the next launch, almost always on another XCD: written through (sc1).  The last
@@ -108,6 +121,30 @@ struct OptInfer {
   __device__ static __forceinline__ long long* ts(const FusedParams&) { return nullptr; }
   __device__ static __forceinline__ long src_row(const FusedParams&, long t) { return t; }
 };
+
+// store_tile128 through the destination map (OptSlots): the same LDS image, each of its 32 rows flushed to the row the map names --
+// a wave's rows may lie in more than one clip, i.e. in more than one slot range.  Rows past ntok are not stored.
+template <typename O>
+__device__ __forceinline__ void store_tile128_rows(char* stg, bf16_t* dst, const FusedParams& P, long tok0, const Frag8<bf16_t> (&b)[8],
+                                                   int lane, HalfGuard& hg) {
+  const int t = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) stage_put(stg, b[s].v, t, h * 8 + s);
+  asm volatile("" : "+s"(tok0), "+v"(lane));   // the map's index arithmetic HERE (as stage_flush: hoisted into the prologue it is
+                                               // carried across every GEMM, and spilled)
+  // one KB at a time, read -> map -> store (stage_flush keeps all eight KB in registers; here the map's index arithmetic needs
+  // the room, and these launches are small)
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    const s16x8 v = *reinterpret_cast<const s16x8*>(stg + p * 1024 + lane * 16);
+    if (hg.on()) hg.see(v);
+    const int r = p * 4 + (lane >> 4), pc = lane & 15;
+    const int c = pc ^ (r & 15);
+    if (tok0 + r < P.ntok) *reinterpret_cast<s16x8*>(dst + O::dst_row(P, tok0 + r) * 128 + c * 8) = v;
+    WMZ_FENCE();
+  }
+  if (hg.on()) hg.fold(WMZ_HG_QKV);
+}
 
 // token + 3-axis position embedding of the lane's half row, rounded to bf16 (the value the stream carries)
 template <int F, typename O>
@@ -439,12 +476,16 @@ __device__ __forceinline__ void layer_fused_body(const FusedParams& P) {
     f32x16 ka[I / 32];
     Frag8<bf16_t> kb[I / 16];
     init_vec<I / 32>(ka, v_bk);
+    if constexpr (O::kDstMap) store_tile128_rows<O>(stg, P.q, P, tok0, qkvb, lane, hg);   // q rows, into their plane slots
+    else
     store_tile128<WH, O::kStQ>(stg, P.q, I, tok0, P.ntok, 0, qkvb, lane, hg);     // q rows (as side work under the to_k MFMAs: slower)
     ws_extra(ws, 8);
     WMZ_TS(33);
     gemm_stage<I / 32, D / 16>(ka, xb, ring0, ws, lane);               // to_k
     WMZ_TS(34);
     bop_from_acc<I / 32>(kb, ka);
+    if constexpr (O::kDstMap) store_tile128_rows<O>(stg, P.kv, P, tok0, kb, lane, hg);
+    else
     if (O::kv_combined(P)) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, 0, kb, lane, hg);   // k | v column halves of [ntok, 2I]
     else store_tile128<WH, O::kStKV>(stg, P.kv, I, tok0, P.ntok, 0, kb, lane, hg);   // k rows
     ws_extra(ws, 8);
@@ -453,6 +494,8 @@ __device__ __forceinline__ void layer_fused_body(const FusedParams& P) {
     gemm_stage<I / 32, D / 16>(ka, xb, ring0, ws, lane);               // to_v
     WMZ_TS(36);
     bop_from_acc<I / 32>(kb, ka);
+    if constexpr (O::kDstMap) store_tile128_rows<O>(stg, P.kv + P.dst_total * I, P, tok0, kb, lane, hg);   // v rows, behind every k slot
+    else
     if (O::kv_combined(P)) store_tile128(stg, P.kv, 2 * I, tok0, P.ntok, I, kb, lane, hg);
     else store_tile128<WH, O::kStKV>(stg, P.kv + (long)P.ntok * I, I, tok0, P.ntok, 0, kb, lane, hg);    // v rows, behind the k rows
   }
@@ -474,10 +517,14 @@ __global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_infer_kernel(FusedPa
   layer_fused_body<256, 128, 256, HEAD, TAIL, OptInfer<(HEAD ? WMZ_FUSED_X_IN_TILED : 0) | (TAIL ? WMZ_FUSED_X_OUT_TILED : 0)>>(P);
 }
 #endif
+// The context cache's launches (wmz_*_fwd_slots): embedding + tail, head + tail.
+template <bool HEAD>
+__global__ __launch_bounds__(NTHR, 8 / FW) void layer_fused_slots_kernel(FusedParams P) {
+  layer_fused_body<256, 128, 256, HEAD, true, OptSlots>(P);
+}
 
 }  // namespace
 
-static int fused_launch(FusedParams& P, int ntok, int D, int I, int M, int has_head, int has_tail, void* stream);
 // What every launch sets; everything optional off: no embedding (z NULL), identity rows (rows_out 0), row-major streams (xflags 0),
 // none of the training outputs (NULL; kv as k rows then v rows), no probes (fused_launch sets dbg / ts).
 static FusedParams fused_params(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
@@ -487,6 +534,8 @@ static FusedParams fused_params(const void* o, const void* x, void* x_out, void*
   P.wpack = (const char*)wpack; P.vec = vec; P.ntok = ntok; P.eps = eps;
   return P;
 }
+#ifndef WMZ_FUSED_SLOTS_UNIT     // (the unit of the context cache's forms -- layer_fused_slots.hip -- holds the entry points at the end of this file alone)
+static int fused_launch(FusedParams& P, int ntok, int D, int I, int M, int has_head, int has_tail, void* stream);
 static long long* g_fused_ts = nullptr;
 static int g_fused_dbg = 0;       // ablation switches (wmz_debug_fused_knobs): 1 = skip the MFMA loops, 2 = skip the weight DMA + waits,
                                   // 4 = no per-slab barrier, 8 = keep the run-time kernel where the inference unit would run (A/B)
@@ -749,6 +798,8 @@ extern "C" int WMZ_FN(wmz_embed_qkv_fused_fwd_planes)(const int64_t* z, const fl
   return fused_launch(P, P.ntok, D, I, M, 0, 1, stream);
 }
 
+#endif  // WMZ_FUSED_SLOTS_UNIT
+
 // One instantiation's launch.  Its dynamic LDS limit is raised once per device, not on every launch (the attribute belongs to
 // the device's copy of the function).
 template <void (*KERN)(FusedParams)>
@@ -762,6 +813,7 @@ static void fused_launch_kernel(const FusedParams& P, dim3 grid, hipStream_t st)
   hipLaunchKernelGGL(KERN, grid, dim3(NTHR), VECB + RING * SLAB + FW * 8192, st, P);
 }
 
+#ifndef WMZ_FUSED_SLOTS_UNIT
 static int fused_launch(FusedParams& P, int ntok, int D, int I, int M, int has_head, int has_tail, void* stream) {
   if (!(D == 256 && I == 128 && M == 256)) {
     wmz_set_error("wmz_layer_fused_fwd: built for dim 256 / inner 128 / mlp 256 (got %d/%d/%d); use the unfused path", D, I, M);
@@ -791,3 +843,105 @@ static int fused_launch(FusedParams& P, int ntok, int D, int I, int M, int has_h
   WMZ_LAUNCH_CHECK("wmz_layer_fused_fwd");
   return WMZ_OK;
 }
+#endif  // WMZ_FUSED_SLOTS_UNIT
+
+#if defined(WMZ_FUSED_SLOTS_UNIT) && WMZ_FUSED_FW != 8
+// ---- the small-workgroup form of the context cache's launches (layer_fused_slots_w4.hip: 4 waves = 128 tokens per workgroup, 16 KB
+// weight slabs; what a decode step runs): this unit holds the kernels and their launcher alone; the entry points are the 8-wave unit's, which hands over the
+// parameter block it has checked and filled.  Same arithmetic per token: bit-identical results.
+int WMZ_FN(wmz_fused_slots_small_launch)(const void* params, int has_head, void* stream) {
+  const FusedParams P = *static_cast<const FusedParams*>(params);     // (the same struct in both units: nothing of it depends on FW)
+  const dim3 grid((unsigned)wmz_cdiv(P.ntok, TW * FW));
+  if (has_head) fused_launch_kernel<layer_fused_slots_kernel<true>>(P, grid, (hipStream_t)stream);
+  else fused_launch_kernel<layer_fused_slots_kernel<false>>(P, grid, (hipStream_t)stream);
+  WMZ_LAUNCH_CHECK("wmz_layer_fused_fwd_slots (4 waves)");
+  return WMZ_OK;
+}
+#elif defined(WMZ_FUSED_SLOTS_UNIT)
+// ---- the context cache's forms: the trailing-planes launches above with q and k | v written into the plane slots
+// [dst_plane0, dst_plane0 + planes_out) of buffers that hold dst_planes planes per clip (fused_row_maps.h); x_out stays compact.
+static int fused_launch_slots(FusedParams& P, int B, int planes_out, int rows_plane, int dst_planes, int dst_plane0, int D, int I,
+                              int M, int has_head, void* stream);
+// (the half unit's entry points are the slots forms OF the _f16 entry points: wmz_layer_fused_fwd_f16_slots, wmz_embed_qkv_fused_fwd_f16_slots)
+#ifdef WMZ_OP16_F16
+#define WMZ_SLOTS_FN(base) base##_f16_slots
+#else
+#define WMZ_SLOTS_FN(base) base##_slots
+#endif
+// Waves per workgroup of these launches.  A decode launch is one plane: at 8 waves = 256 tokens per workgroup that is one workgroup
+// per clip of 16 x 16, each streaming the layer's weights alone.  The 4-wave build (layer_fused_slots_w4.hip: twice the workgroups,
+// 16 KB slabs) measured 23.7 against 34.1 us per launch at 8 clips, 23.3 against 33.8 at 1 and 24.7 against 35.2 at 32, spread
+// 0.03 us (profiles/context_cache/README.md): launches of up to 32 eight-wave workgroups -- the range measured -- take it, larger
+// ones (a context pass of many clips) keep 8 waves.  wmz_debug_fused_slots_waves forces either form (0 = this rule).
+constexpr int kSlotsSmallMaxTokens = 32 * 256;
+int WMZ_FN(wmz_fused_slots_small_launch)(const void* params, int has_head, void* stream);
+#ifndef WMZ_OP16_F16
+int g_wmz_fused_slots_waves = 0;
+extern "C" int wmz_debug_fused_slots_waves(int waves) {
+  WMZ_REQUIRE(waves == 0 || waves == 4 || waves == 8, "wmz_debug_fused_slots_waves: 0 (the product form), 4 or 8");
+  g_wmz_fused_slots_waves = waves;
+  return WMZ_OK;
+}
+#else
+extern int g_wmz_fused_slots_waves;
+#endif
+extern "C" int WMZ_SLOTS_FN(wmz_layer_fused_fwd)(const void* o, const void* x, void* x_out, void* q_out, void* kv_out,
+                                         const void* wpack, const float* vec, int B, int planes_out, int planes_in, int HW,
+                                         int D, int I, int M, int has_head, int has_tail, int xflags, float eps, int dst_planes,
+                                         int dst_plane0, void* stream) {
+  WMZ_REQUIRE((xflags & ~3) == 0, "wmz_layer_fused_fwd_slots: bad layout flags");
+  WMZ_REQUIRE(xflags == 0 || ((long)planes_out * HW) % 32 == 0 && ((long)planes_in * HW) % 32 == 0,
+              "wmz_layer_fused_fwd_slots: the tiled stream layout needs whole 32-token tiles per clip");
+  WMZ_REQUIRE(B > 0 && HW > 0 && planes_out > 0 && planes_out <= planes_in, "wmz_layer_fused_fwd_slots: bad plane counts");
+  WMZ_REQUIRE(fused_slots_ok(planes_out, dst_planes, dst_plane0),
+              "wmz_layer_fused_fwd_slots: the planes written, dst_plane0 .. dst_plane0 + planes_out - 1, must lie inside the dst_planes slots");
+  WMZ_REQUIRE((long)B * planes_in * HW < (1L << 31) && (long)B * dst_planes * HW < (1L << 31), "wmz_layer_fused_fwd_slots: token count overflows int");
+  if (!has_tail)                       // the last layer: no q or k | v to place -- the trailing-planes launch as it is
+    return WMZ_FN(wmz_layer_fused_fwd_planes)(o, x, x_out, nullptr, nullptr, wpack, vec, B, planes_out, planes_in, HW, D, I, M, has_head, 0,
+                                      xflags, eps, stream);
+  WMZ_REQUIRE(x && wpack && vec && q_out && kv_out, "wmz_layer_fused_fwd_slots: bad arguments");
+  WMZ_REQUIRE(!has_head || (o && x_out), "wmz_layer_fused_fwd_slots: head needs o and x_out");
+  FusedParams P = fused_params(o, x, x_out, q_out, kv_out, wpack, vec, B * planes_out * HW, eps);
+  P.xflags = xflags;
+  P.rows_out = planes_out * HW; P.rows_in = planes_in * HW; P.row0 = (planes_in - planes_out) * HW;
+  return fused_launch_slots(P, B, planes_out, HW, dst_planes, dst_plane0, D, I, M, has_head, stream);
+}
+
+extern "C" int WMZ_SLOTS_FN(wmz_embed_qkv_fused_fwd)(const int64_t* z, const float* emb, const float* pos_s, const float* pos_h,
+                                             const float* pos_w, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                                             const float* vec, int B, int S, int H, int W, int planes_out, int D, int I, int M,
+                                             int num_classes, int xflags, float eps, int dst_planes, int dst_plane0,
+                                             void* stream) {
+  WMZ_REQUIRE((xflags & ~WMZ_FUSED_X_OUT_TILED) == 0, "wmz_embed_qkv_fused_fwd_slots: bad layout flags");
+  WMZ_REQUIRE(B > 0 && S > 0 && H > 0 && W > 0 && num_classes > 0, "wmz_embed_qkv_fused_fwd_slots: bad shape");
+  WMZ_REQUIRE(xflags == 0 || ((long)planes_out * H * W) % 32 == 0, "wmz_embed_qkv_fused_fwd_slots: the tiled stream layout needs whole 32-token tiles per clip");
+  WMZ_REQUIRE(planes_out > 0 && planes_out <= S, "wmz_embed_qkv_fused_fwd_slots: bad plane count");
+  WMZ_REQUIRE(fused_slots_ok(planes_out, dst_planes, dst_plane0),
+              "wmz_embed_qkv_fused_fwd_slots: the planes written, dst_plane0 .. dst_plane0 + planes_out - 1, must lie inside the dst_planes slots");
+  WMZ_REQUIRE((long)B * S * H * W < (1L << 31) && (long)B * dst_planes * H * W < (1L << 31), "wmz_embed_qkv_fused_fwd_slots: token count overflows int");
+  WMZ_REQUIRE(z && emb && pos_s && pos_h && pos_w && x_out && q_out && kv_out && wpack && vec, "wmz_embed_qkv_fused_fwd_slots: null tensor");
+  FusedParams P = fused_params(nullptr, nullptr, x_out, q_out, kv_out, wpack, vec, B * planes_out * H * W, eps);
+  P.rows_out = planes_out * H * W; P.rows_in = S * H * W; P.row0 = (S - planes_out) * H * W;
+  P.z = z; P.emb = emb; P.pos_s = pos_s; P.pos_h = pos_h; P.pos_w = pos_w; P.S = S; P.H = H; P.W = W; P.num_classes = num_classes;
+  P.xflags = xflags;
+  return fused_launch_slots(P, B, planes_out, H * W, dst_planes, dst_plane0, D, I, M, 0, stream);
+}
+
+static int fused_launch_slots(FusedParams& P, int B, int planes_out, int rows_plane, int dst_planes, int dst_plane0, int D, int I,
+                              int M, int has_head, void* stream) {
+  if (!(D == 256 && I == 128 && M == 256)) {
+    wmz_set_error("wmz_layer_fused_fwd_slots: built for dim 256 / inner 128 / mlp 256 (got %d/%d/%d)", D, I, M);
+    return WMZ_ERR_UNSUPPORTED;
+  }
+  P.rows_dst = dst_planes * rows_plane;
+  P.row0_dst = dst_plane0 * rows_plane;
+  P.dst_total = fused_dst_total(B, P.rows_dst);
+  const int waves = g_wmz_fused_slots_waves != 0 ? g_wmz_fused_slots_waves : (P.ntok <= kSlotsSmallMaxTokens ? 4 : 8);
+  if (waves == 4) return WMZ_FN(wmz_fused_slots_small_launch)(&P, has_head, stream);
+  const dim3 grid((unsigned)wmz_cdiv(P.ntok, TW * FW));
+  if (has_head) fused_launch_kernel<layer_fused_slots_kernel<true>>(P, grid, (hipStream_t)stream);
+  else fused_launch_kernel<layer_fused_slots_kernel<false>>(P, grid, (hipStream_t)stream);
+  WMZ_LAUNCH_CHECK("wmz_layer_fused_fwd_slots");
+  return WMZ_OK;
+}
+#endif  // WMZ_FUSED_SLOTS_UNIT

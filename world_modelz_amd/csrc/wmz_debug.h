@@ -13,6 +13,11 @@ int wmz_debug_fused_timestamps(void* buf);
  * 2 = skip the weight DMA and its waits, 4 = skip the per-slab workgroup barrier (bits combine); 8 = keep the run-time kernel where
  * the inference unit (layer_fused_infer_kernel) would run -- same results, A/B timing and tests; 0 = product behaviour. */
 int wmz_debug_fused_knobs(int dbg);
+/* Waves per workgroup of the context cache's per-token launches (wmz_layer_fused_fwd_slots, wmz_embed_qkv_fused_fwd_slots and
+ * their half forms): 4 = the small-workgroup build (csrc/layer_fused_slots_w4.hip: 128 tokens per workgroup), 8 = the 256-token
+ * build, whatever the launch's size; 0 = the product rule (4 waves up to 8192 tokens per launch, else 8).  Same results bit for
+ * bit; A/B timing and tests. */
+int wmz_debug_fused_slots_waves(int waves);
 /* Same for the 16-wide-plane attention forward kernel (16 waves x 64 int64). */
 int wmz_debug_attn_timestamps(void* buf);
 /* development knobs of the attention forward: dbg = ablation switches (1 skip the per-tile compute, 2 skip the K/V

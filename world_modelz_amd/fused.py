@@ -707,6 +707,136 @@ def transformer_forward_last(tr, z):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the context cache (causal models): the context planes' K / V once per frame, the generated plane once per denoise iteration
+
+def context_planes(S, eS, depth):
+    """a[l] = trailing CONTEXT planes (of the Sc = S - 1 planes in front of the generated one) on which layer l's input stream --
+    hence its q and k | v -- has to exist so that every layer's K / V exist on the last min(eS, Sc) context planes, which is what
+    the generated plane's queries see under the causal window: a[depth-1] = min(Sc, eS), a[l] = min(Sc, a[l+1] + eS).  Layer
+    l < depth-1 runs attention and its head on a[l+1] query planes over a[l] key planes; the last layer runs nothing for the
+    context (its K / V are the tail of launch depth-2, or of the embedding launch when depth = 1)."""
+    Sc = S - 1
+    a = [0] * depth
+    a[depth - 1] = min(Sc, eS)
+    for l in range(depth - 2, -1, -1):
+        a[l] = min(Sc, a[l + 1] + eS)
+    return a
+
+
+class ContextCache:
+    """The context pass's own q and k | v buffers, one spare plane slot per clip behind the context planes: layer l has
+    q [B, a[l]+1, H, W, I] and kv [2, B, a[l]+1, H, W, I] (a = context_planes).  context_prefill fills the slots 0 .. a[l]-1, each
+    decode step (transformer_forward_last_cached) writes the generated frame's rows into slot a[l], and the attention launches read
+    K / V in place: no copy, no second layout.  The addresses are fixed for the cache's lifetime (captured graphs bake them in).
+    Zero-filled at birth: a slot nobody wrote yet holds finite values."""
+
+    def __init__(self, tr, B, S, H, W, dtype, device):
+        layers = list(tr.layers)
+        self.eS = int(layers[0][0].fn.extents[0])
+        self.depth = len(layers)
+        self.geometry = (int(B), int(S), int(H), int(W))
+        self.dtype, self.device = dtype, torch.device(device)
+        self.a = context_planes(S, self.eS, self.depth)
+        self.q = [torch.zeros((B, n + 1, H, W, I_), dtype=dtype, device=device) for n in self.a]
+        self.kv = [torch.zeros((2, B, n + 1, H, W, I_), dtype=dtype, device=device) for n in self.a]
+
+    def check(self, tr, z, dtype):
+        if (tuple(z.shape) != self.geometry or dtype != self.dtype or z.device != self.device or len(tr.layers) != self.depth
+                or int(tr.layers[0][0].fn.extents[0]) != self.eS):
+            raise ValueError(f'this ContextCache was built for clips {self.geometry} in {self.dtype} on {self.device}, depth '
+                             f'{self.depth}, time extent {self.eS}; got {tuple(z.shape)} in {dtype} on {z.device}')
+
+
+def _slots_entry(base, dt):
+    """The context cache's form of the entry point `base` for tensors of dtype dt: base_slots, or for IEEE half the slots form of
+    its _f16 entry point, base_f16_slots."""
+    return base + ('_f16_slots' if dt == torch.float16 else '_slots')
+
+
+def _slots_attention(cache, l, attn, q_plane0, q_planes):
+    """Layer l's attention over its slot buffers, queries from the slots [q_plane0, q_plane0 + q_planes): the existing causal entry
+    point with S = a[l] + 1 -- no context query sees the spare slot behind it."""
+    B, _, H, W = cache.geometry
+    q, kv = cache.q[l], cache.kv[l]
+    heads, ext, win = attn.fn.heads, attn.fn.extents, attn.fn.time_window
+    o = torch.empty((B, q_planes, H, W, I_), dtype=cache.dtype, device=cache.device)
+    L.call('wmz_local3d_attn_fwd_window', L.ptr(q), L.ptr(kv[0]), L.ptr(kv[1]), L.ptr(o), None, None,
+           B, cache.a[l] + 1, H, W, heads, I_ // heads, win[0], win[1], int(ext[1]), int(ext[2]), I_, I_, I_, I_,
+           q_plane0, q_planes, 0, L.dtype_code(cache.dtype), L.stream())
+    return o
+
+
+def _slots_layer(cache, l, o, x, planes_out, planes_in, head, tail, dst_plane0, tiled):
+    """Launch l + 1 of a cached pass: head = layer l on planes_out of x's planes_in planes, tail = layer l + 1's q and k | v into the
+    slots dst_plane0 .. of its buffers (no tail: the last layer, row-major x_out, nothing to place)."""
+    B, _, H, W = cache.geometry
+    bf, dev = cache.dtype, cache.device
+    wpack, vec = _layer_pack(head, tail, bf)
+    xo = torch.empty((B, planes_out, H, W, D_), dtype=bf, device=dev)
+    q, kv, n_dst = (cache.q[l + 1], cache.kv[l + 1], cache.a[l + 1] + 1) if tail is not None else (None, None, planes_out)
+    xflags = (X_IN_TILED if tiled else 0) | (X_OUT_TILED if tiled and tail is not None else 0)
+    L.call(_slots_entry('wmz_layer_fused_fwd', bf), L.ptr(o), L.ptr(x), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
+           B, planes_out, planes_in, H * W, D_, I_, M_, 1, 1 if tail is not None else 0, xflags, 1e-5, n_dst, dst_plane0, L.stream())
+    return xo
+
+
+def _slots_embed(tr, cache, z, planes_out, dst_plane0, tiled):
+    """The embedding launch of a cached pass: the last planes_out planes of the grid z -> x (compact), layer 0's q and k | v into
+    the slots dst_plane0 .. of its buffers."""
+    B, S, H, W = z.shape
+    bf = cache.dtype
+    wpack, vec = _layer_pack(None, tr.layers[0], bf)
+    x = torch.empty((B, planes_out, H, W, D_), dtype=bf, device=cache.device)
+    L.call(_slots_entry('wmz_embed_qkv_fused_fwd', bf), L.ptr(z), L.ptr(tr.embedding.weight.detach()),
+           L.ptr(tr.pos_emb_s.weight.detach()), L.ptr(tr.pos_emb_h.weight.detach()), L.ptr(tr.pos_emb_w.weight.detach()),
+           L.ptr(x), L.ptr(cache.q[0]), L.ptr(cache.kv[0]), L.ptr(wpack), L.ptr(vec), B, S, H, W, planes_out, D_, I_, M_,
+           tr.embedding.num_embeddings, X_OUT_TILED if tiled else 0, 1e-5, cache.a[0] + 1, dst_plane0, L.stream())
+    return x
+
+
+def context_prefill(tr, z, cache=None):
+    """The context pass of a causal stack over the token grid z [B, S, H, W]: everything of z[:, :-1] that the generated plane
+    z[:, -1] can see, computed once and kept (ContextCache; a given cache is refilled in place).  z[:, :-1] is embedded as an
+    (S-1)-plane grid -- a plane's position index is its index in the clip either way --, then layer l < depth-1 runs attention
+    and its head on a[l+1] query planes over a[l] key planes (context_planes), every launch writing the next layer's q and k | v
+    into the slots 0 .. a[l+1]-1 of its buffers.  One chain of launches on the current stream (config.clip_streams does not apply).
+    The caller vouches for a causal stack with one time extent (VqVideoDiffusionModel.context_prefill checks)."""
+    B, S, H, W = z.shape
+    bf = config.get_fused_dtype()
+    if cache is None:
+        cache = ContextCache(tr, B, S, H, W, bf, z.device)
+    else:
+        cache.check(tr, z, bf)
+    a = cache.a
+    if a[0] == 0:                              # S = 1 or a time extent of 0: the generated plane sees no context
+        return cache
+    layers = list(tr.layers)
+    tiled = (H * W) % 32 == 0
+    x = _slots_embed(tr, cache, z[:, :-1].contiguous(), a[0], 0, tiled)
+    for l in range(len(layers) - 1):
+        o = _slots_attention(cache, l, layers[l][0], a[l] - a[l + 1], a[l + 1])
+        x = _slots_layer(cache, l, o, x, a[l + 1], a[l], layers[l], layers[l + 1], 0, tiled)
+    return cache
+
+
+def transformer_forward_last_cached(tr, z, cache):
+    """The last plane of transformer_forward(tr, z) ([B, H, W, D]) from z[:, -1] and the context kept in `cache`
+    (context_prefill of a grid with the same z[:, :-1]): one embedding launch plus, per layer, one attention launch -- the
+    generated plane's queries over the layer's slots -- and one per-token launch, all of one plane.  Per-token arithmetic is per
+    token and the query plane sees the same key planes in the same order: bit-identical to the uncached forward."""
+    cache.check(tr, z, config.get_fused_dtype())
+    layers = list(tr.layers)
+    a = cache.a
+    tiled = (z.shape[2] * z.shape[3]) % 32 == 0
+    x = _slots_embed(tr, cache, z.contiguous(), 1, a[0], tiled)
+    for l, (attn, ff) in enumerate(layers):
+        o = _slots_attention(cache, l, attn, a[l], 1)
+        tail = layers[l + 1] if l + 1 < len(layers) else None
+        x = _slots_layer(cache, l, o, x, 1, 1, (attn, ff), tail, a[l + 1] if tail is not None else 0, tiled)
+    return x[:, 0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # training: the stack as one autograd node (_StackTrain) on the fused kernels (wmz_*_train) or the chain kernels
 # (_chain_stack_train), backward on that family's backward kernels or op by op (backward.py), as training_route decides
 

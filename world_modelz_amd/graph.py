@@ -50,11 +50,12 @@ class GraphedForward:
     runner built with pre / post work is NOT guarded on its own -- its caller has to be (sample.sample_frames is): the fallback
     would have to repeat that work too."""
 
-    def __init__(self, model, example, warmup=3, pre=None, post=None):
+    def __init__(self, model, example, warmup=3, pre=None, post=None, static_in=None):
         """pre(static_in) / post(static_out): optional device-only work captured in front of / behind the forward (the
-        sampler's draw + re-mask step and its logits hand-over: sample.py), replayed with it."""
+        sampler's draw + re-mask step and its logits hand-over: sample.py), replayed with it.  static_in: another runner's input
+        buffer to capture on instead of a copy of `example` (the sampler's prefill and decode graphs read one token grid)."""
         self.model = model
-        self.static_in = example.clone()
+        self.static_in = example.clone() if static_in is None else static_in
         self.warmup = warmup
         self.pre, self.post = pre, post
         self.recaptures = 0
@@ -66,6 +67,7 @@ class GraphedForward:
         # being rebuilt whenever anything else in the stamp changes -- and by load_state_dict / .to() / optimizers, which
         # all write the existing objects)
         return (_cast.epoch_of(self._tensors), config.get_mode_dtype(), config.get_last_frame_cone(), config.get_clip_streams(),
+                config.get_context_cache(),
                 tuple((t._version, t.data_ptr()) for t in self._tensors))
 
     @gc_quiet

@@ -41,6 +41,56 @@ class VqVideoDiffusionModel(nn.Module):
         h = self.transformer.forward_compute(x)
         return self._logits(h[:, -1])         # [B,H,W,D] view: uniform row stride, no copy
 
+    # ---- the context cache (config.context_cache; fused.ContextCache): a causal model's context K / V once per frame
+
+    def _context_cache_refusal(self, z):
+        """Why context_prefill / forward_last cannot run on the token grid z now (None: they can)."""
+        from . import config, fused
+        tr = self.transformer
+        if not self.causal:
+            return 'the model is not causal: its context planes depend on the frame being generated'
+        if len({int(a.fn.extents[0]) for a, _ in tr.layers}) != 1:
+            return 'the layers do not share one time extent'
+        if torch.is_grad_enabled() or not z.is_cuda:
+            return 'the context cache is an inference path on the GPU (call it under torch.no_grad())'
+        if z.dim() != 4:
+            return f'the token grid is [B, S, H, W], not {tuple(z.shape)}'
+        _, S, H, W = z.shape
+        dt = config.get_fused_dtype()
+        if dt not in (torch.bfloat16, torch.float16) or fused.inference_route(tr, dt, H, W, z.numel()) != 'fused':
+            return 'only the fused widths in bf16 or in the precise mode keep a context cache (other widths and fp32 run the uncached forward)'
+        if S > tr.pos_emb_s.num_embeddings or H > tr.pos_emb_h.num_embeddings or W > tr.pos_emb_w.num_embeddings:
+            return 'token grid larger than the position-embedding tables'
+        return None
+
+    def context_cache_eligible(self, z):
+        """Whether context_prefill(z) / forward_last(z, cache) would run: a causal model with one time extent, without grad on
+        the GPU, on the fused inference route in bf16 or in the precise mode."""
+        return self._context_cache_refusal(z) is None
+
+    def _context_cache_check(self, z):
+        why = self._context_cache_refusal(z)
+        if why is not None:
+            raise ValueError(f'VqVideoDiffusionModel: no context cache here -- {why}')
+
+    def context_prefill(self, z, cache=None):
+        """The context pass over z [B, S, H, W] -- everything of z[:, :-1] the last frame can see -- kept as a fused.ContextCache
+        (a given cache is refilled in place).  ValueError where context_cache_eligible(z) is False.
+        config.half_guard: neither this call nor forward_last is a guarded call of its own -- an overflow of the prefill would have
+        to fail every later forward_last on the cache.  Their caller is: sample.sample_frames guards the whole call and repeats
+        it uncached on the fp32 route."""
+        from . import fused
+        self._context_cache_check(z)
+        return fused.context_prefill(self.transformer, z, cache)
+
+    def forward_last(self, z, cache):
+        """forward(z) -- fp32 logits [B, H, W, C] of the last frame, bit for bit -- reading z[:, -1] only: everything of the
+        context comes from `cache`, the context_prefill of a grid with the same z[:, :-1].  One plane per launch.  ValueError
+        where context_cache_eligible(z) is False."""
+        from . import fused
+        self._context_cache_check(z)
+        return self._logits(fused.transformer_forward_last_cached(self.transformer, z, cache))
+
     def _logits(self, last):
         # (a half stream -- the precise mode -- takes the half unit of the same GEMM: fp32 accumulation, fp32 logits)
         return Fw.linear(last, self.logit_proj.weight, self.logit_proj.bias, out_f32=True)

@@ -107,10 +107,26 @@ def lowest_scores_mask(scores, alpha, candidates=None, count=None):
 REMASK_MODES = ('random', 'confidence')
 
 
+def _use_context_cache(model, batch_z, context_cache):
+    """sample_frames' context_cache argument resolved: None reads config.context_cache and keeps the uncached path on a model that
+    is not eligible (VqVideoDiffusionModel.context_cache_eligible); True on such a model is a ValueError."""
+    from . import config
+    if not (config.get_context_cache() if context_cache is None else bool(context_cache)):
+        return False
+    eligible = getattr(model, 'context_cache_eligible', None)
+    if eligible is not None and eligible(batch_z):
+        return True
+    if context_cache is None:
+        return False
+    if eligible is None:
+        raise ValueError(f'context_cache=True: {type(model).__name__} has no context cache (VqVideoDiffusionModel.context_prefill)')
+    model._context_cache_check(batch_z)                           # raises, naming what is missing
+
+
 @torch.no_grad()
 def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iterations=30, sample_topk=-1, noise_schedule=None,
                   consistent_masking=False, generator=None, use_graph=True, uniforms=None, trace=None, temperature=1.0,
-                  sample_topp=1.0, *, remask='random', remask_noise=0.0):
+                  sample_topp=1.0, *, remask='random', remask_noise=0.0, context_cache=None):
     """batch_z: int64 [B,S,H,W] context tokens on the GPU (the last frame is overwritten).  Returns the list of generated
     latent frames [B,H,W] (decode them with VqAutoEncoder.decode) and the final batch_z.
 
@@ -126,7 +142,11 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     masked-token decoders (MaskGIT).  remask_noise >= 0 (finite) scales the Gumbel noise added to the scores, annealed by
     (1 - alpha); its uniform is u_mask[f, i] when injected.  ValueError for anything else.  (Config 5's sampler,
     sparse_diffusion.sample_clips, takes all of these too: it masks when it gathers a context, so its 'confidence' orders that
-    masking by a score kept per clip position between sub-steps.)"""
+    masking by a score kept per clip position between sub-steps.)
+    context_cache: True -- a causal model on the fused widths computes the context planes' K / V once per frame
+    (model.context_prefill) and the generated plane alone per iteration (model.forward_last): the same logits bit for bit, hence
+    the same tokens; ValueError on a model that is not eligible.  None (default) reads config.context_cache and keeps the
+    uncached path where the model is not eligible; False: the uncached path."""
     assert batch_z.is_cuda
     if remask not in REMASK_MODES:
         raise ValueError(f'remask must be one of {REMASK_MODES} (got {remask!r})')
@@ -137,6 +157,7 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     if not 0 < sample_topp <= 1:
         raise ValueError(f'sample_topp must lie in (0, 1] (got {sample_topp})')
     from . import half_guard
+    use_cache = _use_context_cache(model, batch_z, context_cache)
     if half_guard.wanted():
         # config.half_guard: the whole call is one guarded call (its forwards only accumulate into the word); a fallback repeats
         # it on the fp32 route with the random state it started from, so the tokens are the fp32 mode's
@@ -150,9 +171,10 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
                 g.set_state(st)
             if trace is not None:
                 del trace[:]
-            return sample_frames(*args, **kwargs)
+            return sample_frames(*args, context_cache=False, **kwargs)     # (the fp32 route keeps no context cache)
         kwargs = dict(trace=trace, temperature=temperature, sample_topp=sample_topp, remask=remask, remask_noise=remask_noise)
-        return half_guard.guarded('sample.sample_frames', model, batch_z.device, lambda: sample_frames(*args, **kwargs), again)
+        return half_guard.guarded('sample.sample_frames', model, batch_z.device,
+                                  lambda: sample_frames(*args, context_cache=use_cache, **kwargs), again)
     B, S, H, W = batch_z.shape
     mask_token = num_embeddings
     batch_z = batch_z.clone()
@@ -162,8 +184,9 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     if (use_graph and uniforms is None and trace is None and num_embeddings <= ops.sample_max_classes()
             and (not confidence or H * W <= ops.remask_max_rows())):
         return _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_iterations, sample_topk, noise_schedule,
-                                    consistent_masking, generator, temperature, sample_topp, remask, remask_noise)
-    fwd = GraphedForward(model, batch_z) if use_graph else None
+                                    consistent_masking, generator, temperature, sample_topp, remask, remask_noise, use_cache)
+    fwd = GraphedForward(model, batch_z) if use_graph and not use_cache else None     # (the cached steps run eagerly here)
+    cache = None
     if fwd is not None:
         batch_z = fwd.static_in                                   # the loop edits the graph's own input buffer: no staging copy
     dev = batch_z.device
@@ -175,6 +198,8 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     for f in range(num_frames):
         logits = torch.zeros(B * H * W, num_embeddings, device=dev)      # flat start (:71)
         last_mask = torch.ones(B, H * W, dtype=torch.bool, device=dev)
+        if use_cache:
+            cache = model.context_prefill(batch_z, cache)         # the frame's context: fixed until the shift below
         for i in range(num_eval_iterations):
             if temperature != 1.0:
                 logits = logits * inv_temperature
@@ -207,7 +232,8 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
                 trace.append(frame.view(B, H, W).clone())
             if i + 1 < num_eval_iterations:                       # (the reference runs the model behind a frame's last draw too, :111,
                 #                                                    and never reads those logits)
-                logits = (fwd(batch_z) if fwd is not None else model(batch_z)).reshape(B * H * W, num_embeddings).float()
+                y = model.forward_last(batch_z, cache) if use_cache else (fwd(batch_z) if fwd is not None else model(batch_z))
+                logits = y.reshape(B * H * W, num_embeddings).float()
         out.append(denoised.view(B, H, W).clone())
         batch_z[:, :-1] = batch_z[:, 1:].clone()                  # shift frames (:115)
     return out, (batch_z.clone() if fwd is not None else batch_z)   # (never hand out the graph's own buffer)
@@ -259,9 +285,11 @@ class _WeakModel:
     was a reference cycle -- a dropped model, its hipGraphs and their private pools were freed only by the cyclic collector,
     whenever that ran (possibly in the middle of another stream capture); now dropping the model frees them at once."""
 
-    def __init__(self, model):
+    def __init__(self, model, call=None):
+        """call(model, z): what the runner captures instead of model(z) (the cached sampler's prefill and decode step)."""
         import weakref
         self._ref = weakref.ref(model)
+        self._call = call
 
     def _model(self):
         m = self._ref()
@@ -276,7 +304,7 @@ class _WeakModel:
         return self._model().buffers()
 
     def __call__(self, z):
-        return self._model()(z)
+        return self._model()(z) if self._call is None else self._call(self._model(), z)
 
 
 def release_sampler_sessions(model):
@@ -295,11 +323,13 @@ _SEED_KEY = 0x9E3779B97F4A7C15                   # the captured kernels' Philox 
 class _Session:
     """One captured sampler step (forward + draw of the next iteration + counter) and the device state it works on, kept with the
     model across sample_frames calls: capturing costs ~4 ms, a frame of 30 iterations ~11 (GraphedForward re-captures by itself
-    when the weights, the compute dtype or the run-time configuration changed)."""
+    when the weights, the compute dtype or the run-time configuration changed).  context_cache: the session owns a
+    fused.ContextCache and TWO graphs on one token grid -- the prefill (once per frame) and the decode step (model.forward_last
+    between today's pre / post work)."""
 
     def __init__(self, model, batch_z, C, n_iter, sample_topk, consistent_masking, temperature=1.0, sample_topp=1.0, remask='random',
-                 remask_noise=0.0):
-        from . import ops
+                 remask_noise=0.0, context_cache=False):
+        from . import config, fused, ops
         B, S, H, W = batch_z.shape
         dev = batch_z.device
         R = B * H * W
@@ -332,11 +362,19 @@ class _Session:
                 src = self.logits
             draw(src, holder['z'])
         self.draw = draw
-        self.fwd = GraphedForward(_WeakModel(model), batch_z, pre=pre, post=post)
+        self.prefill = None
+        if not context_cache:
+            self.fwd = GraphedForward(_WeakModel(model), batch_z, pre=pre, post=post)
+            return
+        cache = self.cache = fused.ContextCache(model.transformer, B, S, H, W, config.get_fused_dtype(), dev)
+        self.fwd = GraphedForward(_WeakModel(model, lambda m, z: m.forward_last(z, cache)), batch_z, pre=pre, post=post)
+        self.prefill = GraphedForward(_WeakModel(model, lambda m, z: m.context_prefill(z, cache).q[0]), batch_z,
+                                      static_in=self.fwd.static_in)
 
 
 def _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_iterations, sample_topk, noise_schedule,
-                         consistent_masking, generator, temperature=1.0, sample_topp=1.0, remask='random', remask_noise=0.0):
+                         consistent_masking, generator, temperature=1.0, sample_topp=1.0, remask='random', remask_noise=0.0,
+                         context_cache=False):
     """The same loop with NO host work inside a frame but one graph launch per iteration: the draw + re-mask step is one
     kernel (wmz_sample_tokens_dev, or wmz_sample_tokens_filtered_dev with a temperature, a nucleus filter or more than 2048 classes
     -- up to ops.sample_max_classes(): temperature, top-k, softmax, top-p, inverse-CDF draw and re-mask per row, uniforms from in-kernel Philox indexed
@@ -348,14 +386,19 @@ def _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_it
     The captured step stays with the model between calls (_Session).  Same distribution as the torch path (which stays for
     injected uniforms: the parity fixtures), different random stream.
     remask = 'confidence': the step is TWO kernels -- the scored draw (wmz_sample_tokens_scored_dev) and the per-clip selection of the
-    lowest scores (wmz_remask_lowest_dev) -- captured in the same place."""
+    lowest scores (wmz_remask_lowest_dev) -- captured in the same place.
+    context_cache: a frame is one replay of the prefill graph, then n - 1 replays of the decode graph (forward_last + draw + counter):
+    still no host sync inside a frame, one graph launch per iteration plus one per frame."""
+    from . import config
     B, S, H, W = batch_z.shape
     n = num_eval_iterations
-    key = (B, S, H, W, num_embeddings, n, int(sample_topk), bool(consistent_masking), batch_z.device, str(remask), float(remask_noise),
+    # (the cached session's buffers are in the fused dtype: another mode is another session, not a re-capture)
+    key = (B, S, H, W, num_embeddings, n, int(sample_topk), bool(consistent_masking), batch_z.device,
+           bool(context_cache), config.get_fused_dtype() if context_cache else None, str(remask), float(remask_noise),
            float(temperature), float(sample_topp))
     per_model = model.__dict__.setdefault('_wmz_sampler_sessions', _Sessions())
     ses = per_model.touch(key, lambda: _Session(model, batch_z, num_embeddings, n, sample_topk, consistent_masking,
-                                                     temperature, sample_topp, remask, remask_noise))
+                                                     temperature, sample_topp, remask, remask_noise, context_cache))
     ses.alphas.copy_(torch.tensor([min(max(noise_schedule((i + 1) / n) if noise_schedule is not None else (i + 1) / n, 0.0), 1.0)
                                    for i in range(n)], dtype=torch.float32))
     # The Philox stream is indexed by the counter; a call starts it at a 62-bit draw from the caller's generator (the global CPU
@@ -366,11 +409,15 @@ def _sample_frames_fused(model, batch_z, num_embeddings, num_frames, num_eval_it
                              device=generator.device if generator is not None else 'cpu').item()) // n * n
     fwd = ses.fwd
     fwd.refresh()                                                 # (a re-capture draws: before the call's state is set up, not inside it)
+    if ses.prefill is not None:
+        ses.prefill.refresh()
     z = fwd.static_in
     z.copy_(batch_z)                                              # (the capture / the previous call drew into the last frame)
     ses.counter.fill_(base)
     out = []
     for f in range(num_frames):
+        if ses.prefill is not None:
+            ses.prefill(z)                                        # the frame's context K / V: fixed until the shift below
         ses.logits.zero_()                                        # flat start (:71)
         if ses.last_mask is not None:
             ses.last_mask.fill_(1)
