@@ -198,6 +198,12 @@ int wmz_layernorm_bwd(const void* x, long ldx, const void* dyhat, long lddy, con
 int wmz_embed_pos3d_fwd(const int64_t* z, const float* emb, const float* pos_s, const float* pos_h,
                         const float* pos_w, void* x, int B, int S, int H, int W, int D, int num_classes,
                         int dtype, void* stream);
+/* The trailing planes_out planes of every clip of the same embedding: x [B, planes_out, H, W, D], z and the tables as above
+ * (z is the whole [B, S, H, W] grid; a plane keeps its own position index).  Same expression, same order: bit-identical to those
+ * planes of wmz_embed_pos3d_fwd.  What a context cache's decode step embeds (planes_out = 1). */
+int wmz_embed_pos3d_fwd_planes(const int64_t* z, const float* emb, const float* pos_s, const float* pos_h,
+                               const float* pos_w, void* x, int B, int S, int H, int W, int planes_out, int D,
+                               int num_classes, int dtype, void* stream);
 /* its backward: scatter-add dx into the four fp32 tables (accumulated; zero them first).  H + W <= 64.  W == 16 takes a kernel
  * that keeps the column sums in registers when D % 64 is 0 or at least 16 (every wave that works has lanes 0..15 active: they
  * carry the plane row's token ids); any other width, and any other W, takes the general kernel.  Same sums either way. */
@@ -396,6 +402,13 @@ int wmz_embed_qkv_fused_fwd_slots(const int64_t* z, const float* emb, const floa
                                   const float* pos_w, void* x_out, void* q_out, void* kv_out, const void* wpack,
                                   const float* vec, int B, int S, int H, int W, int planes_out, int D, int I, int M,
                                   int num_classes, int xflags, float eps, int dst_planes, int dst_plane0, void* stream);
+/* ... and of the chain kernels' inference launch (csrc/layer_chain_slots_g<n>.hip): the contract of wmz_layer_chain_fwd_planes with
+ * q_out [B, dst_planes, HW, I] and kv_out [2, B, dst_planes, HW, I] holding plane slots as above -- the map is applied per token, a
+ * wave's 16 tokens may lie in two clips --, x_out compact [B, n_q, HW, D].  Refused before anything is launched: what
+ * fused_slots_ok refuses.  tail == 0 places nothing: the trailing-planes launch as it is. */
+int wmz_layer_chain_fwd_slots(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                              const float* vec, int B, int n_q, int n_in, int HW, int D, int I, int M, int head, int tail,
+                              float eps, int dst_planes, int dst_plane0, void* stream);
 
 /* ---- the PRECISE fused inference mode: the same kernels with IEEE-half MFMA operands and a half residual stream between the
  * layers (same matrix rate as bf16, 11 significand bits instead of 8).  The reference computes in fp32
@@ -438,6 +451,9 @@ int wmz_fused_pack_table_f16(const void* block_rows, int nblk, long total8, cons
 int wmz_layer_chain_fwd_planes_f16(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
                                    const float* vec, int B, int n_q, int n_in, int HW, int D, int I, int M, int head, int tail,
                                    float eps, void* stream);
+int wmz_layer_chain_fwd_f16_slots(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                                  const float* vec, int B, int n_q, int n_in, int HW, int D, int I, int M, int head, int tail,
+                                  float eps, int dst_planes, int dst_plane0, void* stream);
 /* ... and the linear behind it (VqVideoDiffusionModel.logit_proj on the last frame, main.py:33-36): wmz_linear_fwd /
  * wmz_linear_fwd_stats / wmz_linear_fwd_blocked with dtype = WMZ_F16 (A and Wt half, bias / LayerNorm parameters fp32, C half or,
  * with out_f32, fp32). */

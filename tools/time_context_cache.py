@@ -3,6 +3,7 @@
 alternated in groups, warm-up discarded, min / median / max over the groups reported; one JSON line per (mode, batch).
 
     python tools/time_context_cache.py [--iters 20] [--groups 5] [--batches 1,8,32] [--modes bf16,precise]
+                                       [--widths dim,heads,dim_head,mlp] [--depth N] [--clip S,H,W] [--arms uncached,cached]
 
 The benchmark geometry with causal=True (clips of 32 x 16 x 16, codebook 1024, dim 256, one head of 128, window 7 x 7 x 7, depth 4):
   iteration/uncached   one replay of the captured sampler step as it is today: last-frame cone forward + draw + counter
@@ -16,6 +17,11 @@ The benchmark geometry with causal=True (clips of 32 x 16 x 16, codebook 1024, d
   launch/*_w4          the same two on the small-workgroup build (csrc/layer_fused_slots_w4.hip: 4 waves, two workgroups per clip --
                        what the entry points choose for a decode step), captured in the same process, alternated with the 8-wave arms
 The iteration, prefill and frame figures run the product rule.
+--widths / --depth / --clip time another causal model on the same codebook and window -- a chain-width one
+(profiles/context_cache_chain/README.md: --widths 96,1,128,256 --depth 12 --clip 6,16,16): its per-token launches are the chain
+kernels' (launch/embed = the embedding launch of one plane plus the chain launch without a head; one workgroup size, no *_w4 arms),
+and the line carries the model.  --arms uncached times the uncached arm alone (iteration/uncached, frame/uncached): it runs on a
+tree without the cached passes for these widths too.
 The launch figures are replays of a graph that holds 20 copies of the launch, divided by 20.  At most 16 host threads."""
 import argparse
 import json
@@ -81,18 +87,43 @@ def _copies(fn, config):
     return g.replay
 
 
+def model_config(args):
+    """CFG with --widths / --depth / --clip applied (the defaults: CFG itself)."""
+    c = dict(CFG)
+    if args.widths:
+        c['dim'], c['heads'], c['dim_head'], c['mlp_dim'] = (int(v) for v in args.widths.split(','))
+    if args.depth:
+        c['depth'] = args.depth
+    if args.clip:
+        c['S'], c['H'], c['W'] = (int(v) for v in args.clip.split(','))
+    return c
+
+
 def measure(mode, B, args):
     from world_modelz_amd import config, fused, sample
     from world_modelz_amd.main import VqVideoDiffusionModel
     torch.manual_seed(0)
-    c = CFG
+    c = model_config(args)
+    arms = args.arms.split(',')
     m = VqVideoDiffusionModel(data_shape=(c['S'], c['H'], c['W']), dim=c['dim'], num_classes=c['C'], extents=c['extents'],
                               depth=c['depth'], dim_head=c['dim_head'], mlp_dim=c['mlp_dim'], heads=c['heads'], causal=True).cuda()
     z = torch.randint(0, c['C'], (B, c['S'], c['H'], c['W'])).cuda()
     out = {'mode': mode, 'B': B, 'iters': args.iters, 'groups': args.groups, 'device': torch.cuda.get_device_name(0)}
+    if c != CFG:
+        out['model'] = {k: c[k] for k in ('dim', 'heads', 'dim_head', 'mlp_dim', 'depth', 'S', 'H', 'W')}
     with config.compute_dtype(mode), torch.no_grad():
         def frame(cache):
             return sample.sample_frames(m, z, c['C'], 1, N_ITER, generator=torch.Generator().manual_seed(1), context_cache=cache)
+        if arms == ['uncached']:
+            frame(False)
+            plain = [s for s in m._wmz_sampler_sessions.values() if s.prefill is None][0]
+            out['route'] = fused.inference_route(m.transformer, config.get_fused_dtype(), c['H'], c['W'], z.numel())
+            out.update({f'iteration/{k}': v for k, v in alternate({'uncached': lambda: plain.fwd(plain.fwd.static_in)},
+                                                                  args.iters, args.groups).items()})
+            out.update({f'frame/{k}': v for k, v in alternate({'uncached': lambda: frame(False)}, max(2, args.iters // 5),
+                                                              args.groups).items()})
+            sample.release_sampler_sessions(m)
+            return out
         same = all(torch.equal(a, b) for a, b in zip(frame(True)[0], frame(False)[0]))
         out['same_tokens'] = bool(same)
         ses = {bool(s.prefill is not None): s for s in m._wmz_sampler_sessions.values()}
@@ -112,6 +143,11 @@ def measure(mode, B, args):
         a = cache.a
         bf = cache.dtype
         zc = z.contiguous()
+        if cache.family == 'chain':
+            out.update(alternate(chain_launches(fused, tr, layers, cache, zc), max(2, args.iters // 2), args.groups, scale=1.0 / COPIES))
+            out['family'], out['dtype'] = 'chain', str(bf)
+            sample.release_sampler_sessions(m)
+            return out
         arms = {'launch/embed': copies(lambda: fused._slots_embed(tr, cache, zc, 1, a[0], True), 8),
                 'launch/embed_w4': copies(lambda: fused._slots_embed(tr, cache, zc, 1, a[0], True), 4)}
         x = fused._slots_embed(tr, cache, zc, 1, a[0], True)
@@ -132,12 +168,31 @@ def measure(mode, B, args):
     return out
 
 
+def chain_launches(fused, tr, layers, cache, zc):
+    """The decode step's launches of a chain-width model, one by one (one workgroup size: no small form)."""
+    a = cache.a
+    arms = {'launch/embed': copies(lambda: fused._slots_embed_chain(tr, cache, zc, 1, a[0]))}
+    x = fused._slots_embed_chain(tr, cache, zc, 1, a[0])
+    for l, (attn, ff) in enumerate(layers):
+        o = fused._slots_attention(cache, l, attn, a[l], 1)
+        tail = layers[l + 1] if l + 1 < len(layers) else None
+        arms[f'launch/attention/{l}'] = copies(lambda l=l, attn=attn: fused._slots_attention(cache, l, attn, a[l], 1))
+        arms[f'launch/per_token/{l}'] = copies(lambda l=l, o=o, x=x, attn=attn, ff=ff, tail=tail: fused._slots_layer_chain(
+            cache, l, o, x, 1, 1, (attn, ff), tail, a[l + 1] if tail is not None else 0))
+        x = fused._slots_layer_chain(cache, l, o, x, 1, 1, (attn, ff), tail, a[l + 1] if tail is not None else 0)
+    return arms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--groups', type=int, default=5)
     ap.add_argument('--batches', default='1,8,32')
     ap.add_argument('--modes', default='bf16,precise')
+    ap.add_argument('--widths', default=None, help='dim,heads,dim_head,mlp of the model (default: the benchmark widths)')
+    ap.add_argument('--depth', type=int, default=0, help='layers (default: the benchmark depth)')
+    ap.add_argument('--clip', default=None, help='S,H,W of a clip (default: the benchmark clip)')
+    ap.add_argument('--arms', default='uncached,cached', choices=['uncached,cached', 'uncached'])
     ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'timings need the GPU'

@@ -166,11 +166,13 @@ def last_frame_cone(on):
         set_last_frame_cone(prev)
 
 
-# Inference only, causal models on the fused widths: under the causal window no context plane depends on the frame being generated,
-# so the sampler can compute the context planes' K / V once per frame (fused.context_prefill) and only the generated plane per
-# denoise iteration (VqVideoDiffusionModel.forward_last) -- same logits bit for bit, about a seventh of the tokens per iteration.
-# Off by default: the decode launches are small and latency-bound, what they gain is a measurement
-# (profiles/context_cache/README.md).  sample.sample_frames reads this when its context_cache argument is None; a model that is
+# Inference only, causal models whose uncached forward runs the fused kernels (the default widths) or the chain kernels (the widths
+# of csrc/chain_widths.h, at a grid that chain_policy below lets them take): under the causal window no context plane depends on the
+# frame being generated, so the sampler can compute the context planes' K / V once per frame (fused.context_prefill) and only the
+# generated plane per denoise iteration (VqVideoDiffusionModel.forward_last) -- same logits bit for bit, about a seventh of the
+# tokens per iteration at the benchmark clip.  Off by default: the decode launches are small and latency-bound, what they gain is a
+# measurement (profiles/context_cache/README.md; the chain widths: profiles/context_cache_chain/README.md).  sample.sample_frames
+# reads this when its context_cache argument is None; a model that is
 # not eligible (VqVideoDiffusionModel.context_cache_eligible) keeps the uncached path.  The cached passes run as one chain of
 # launches: clip_streams below does not apply to them.
 _context_cache = os.environ.get('WMZ_CONTEXT_CACHE', '0') != '0'

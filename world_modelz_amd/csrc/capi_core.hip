@@ -1,5 +1,6 @@
 // Error plumbing and version of libwmz_hip.so, plus the token/position embedding kernel.
 #include "wmz_common.h"
+#include "fused_row_maps.h"
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -51,16 +52,20 @@ namespace {
 
 // x[b,s,h,w,:] = emb[z] + ((pos_s[s] + pos_h[h]) + pos_w[w])   (local_3d_attention.py:140-157)
 // one 16-byte-wide lane per 4 channels; tables are fp32 and tiny (L2-resident), x is written once.
-template <typename T>
-__global__ __launch_bounds__(256) void embed_pos3d_kernel(const int64_t* __restrict__ z, const float* __restrict__ emb,
-                                                          const float* __restrict__ ps, const float* __restrict__ ph,
-                                                          const float* __restrict__ pw, T* __restrict__ x, long ntok,
-                                                          int S, int H, int W, int D, int num_classes) {
+// The body of both kernels below.  PLANES: the launch computes the trailing rows_out rows of every clip's rows_in (whole planes):
+// row `to` of x is the token grid's row t = fused_src_row(...) (fused_row_maps.h), whose token id and position indices it takes.
+// The expression and its order are the whole grid's, so the planes produced are bit-identical to the whole grid's.
+template <typename T, bool PLANES>
+__device__ __forceinline__ void embed_pos3d_body(const int64_t* __restrict__ z, const float* __restrict__ emb,
+                                                 const float* __restrict__ ps, const float* __restrict__ ph,
+                                                 const float* __restrict__ pw, T* __restrict__ x, long ntok, int S, int H,
+                                                 int W, int D, int num_classes, int rows_out, int rows_in, int row0) {
   const int d4 = D >> 2;
   const long total = ntok * d4;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long t = i / d4;
-    const int c = (int)(i - t * d4) * 4;
+    const long to = i / d4;
+    const int c = (int)(i - to * d4) * 4;
+    const long t = PLANES ? fused_src_row(rows_out, rows_in, row0, to) : to;
     const int w = (int)(t % W);
     const int h = (int)((t / W) % H);
     const int s = (int)((t / ((long)W * H)) % S);
@@ -72,14 +77,32 @@ __global__ __launch_bounds__(256) void embed_pos3d_kernel(const int64_t* __restr
     const f32x4 cw = *reinterpret_cast<const f32x4*>(pw + (long)w * D + c);
     const f32x4 v = e + ((a + bq) + cw);
     if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<f32x4*>(x + t * D + c) = v;
+      *reinterpret_cast<f32x4*>(x + to * D + c) = v;
     } else {
       s16x4 o;
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[k] = (short)f32_to_bf16_bits(v[k]);
-      *reinterpret_cast<s16x4*>(x + t * D + c) = o;
+      *reinterpret_cast<s16x4*>(x + to * D + c) = o;
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void embed_pos3d_kernel(const int64_t* __restrict__ z, const float* __restrict__ emb,
+                                                          const float* __restrict__ ps, const float* __restrict__ ph,
+                                                          const float* __restrict__ pw, T* __restrict__ x, long ntok,
+                                                          int S, int H, int W, int D, int num_classes) {
+  embed_pos3d_body<T, false>(z, emb, ps, ph, pw, x, ntok, S, H, W, D, num_classes, 0, 0, 0);
+}
+
+// the trailing planes of every clip (wmz_embed_pos3d_fwd_planes): ntok = B planes_out H W rows of x
+template <typename T>
+__global__ __launch_bounds__(256) void embed_pos3d_planes_kernel(const int64_t* __restrict__ z, const float* __restrict__ emb,
+                                                                 const float* __restrict__ ps, const float* __restrict__ ph,
+                                                                 const float* __restrict__ pw, T* __restrict__ x, long ntok,
+                                                                 int S, int H, int W, int D, int num_classes, int rows_out,
+                                                                 int rows_in, int row0) {
+  embed_pos3d_body<T, true>(z, emb, ps, ph, pw, x, ntok, S, H, W, D, num_classes, rows_out, rows_in, row0);
 }
 
 // Backward: one workgroup per (b, s) plane, thread = channel.  pos_s gets one row add per plane, pos_h / pos_w are
@@ -375,6 +398,32 @@ extern "C" int wmz_embed_pos3d_fwd(const int64_t* z, const float* emb, const flo
     hipLaunchKernelGGL(embed_pos3d_kernel<float>, dim3(grid), dim3(256), 0, st, z, emb, pos_s, pos_h, pos_w,
                        (float*)x, ntok, S, H, W, D, num_classes);
   WMZ_LAUNCH_CHECK("wmz_embed_pos3d_fwd");
+  return WMZ_OK;
+}
+
+// The trailing planes_out planes of the same embedding: x [B, planes_out, H, W, D], every element by the expression above
+// (embed_pos3d_body), bit-identical to those planes of wmz_embed_pos3d_fwd.  planes_out == S is that launch's result.
+extern "C" int wmz_embed_pos3d_fwd_planes(const int64_t* z, const float* emb, const float* pos_s, const float* pos_h,
+                                          const float* pos_w, void* x, int B, int S, int H, int W, int planes_out, int D,
+                                          int num_classes, int dtype, void* stream) {
+  WMZ_REQUIRE(z && emb && pos_s && pos_h && pos_w && x, "wmz_embed_pos3d_fwd_planes: null tensor");
+  WMZ_REQUIRE(B > 0 && S > 0 && H > 0 && W > 0 && D > 0 && num_classes > 0, "wmz_embed_pos3d_fwd_planes: bad shape");
+  WMZ_REQUIRE(planes_out > 0 && planes_out <= S, "wmz_embed_pos3d_fwd_planes: bad plane count");
+  WMZ_REQUIRE(D % 4 == 0, "wmz_embed_pos3d_fwd_planes: D must be a multiple of 4 (got %d)", D);
+  WMZ_REQUIRE(dtype == WMZ_F32 || dtype == WMZ_BF16, "wmz_embed_pos3d_fwd_planes: bad dtype %d", dtype);
+  WMZ_REQUIRE((long)B * S * H * W < (1L << 31), "wmz_embed_pos3d_fwd_planes: token count overflows int");
+  const int HW = H * W;
+  const long ntok = (long)B * planes_out * HW;
+  const long total = ntok * (D / 4);
+  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == WMZ_BF16)
+    hipLaunchKernelGGL(embed_pos3d_planes_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, z, emb, pos_s, pos_h, pos_w,
+                       (bf16_t*)x, ntok, S, H, W, D, num_classes, planes_out * HW, S * HW, (S - planes_out) * HW);
+  else
+    hipLaunchKernelGGL(embed_pos3d_planes_kernel<float>, dim3(grid), dim3(256), 0, st, z, emb, pos_s, pos_h, pos_w,
+                       (float*)x, ntok, S, H, W, D, num_classes, planes_out * HW, S * HW, (S - planes_out) * HW);
+  WMZ_LAUNCH_CHECK("wmz_embed_pos3d_fwd_planes");
   return WMZ_OK;
 }
 

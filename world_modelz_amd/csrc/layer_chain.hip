@@ -27,11 +27,23 @@
 #ifndef WMZ_CHAIN_GROUP
 #define WMZ_CHAIN_GROUP 0         // this unit's group of width triples (chain_widths.h); group 0 also holds the entry points
 #endif
+// WMZ_CHAIN_SLOTS_UNIT: the context cache's form of the inference launch (layer_chain_slots_g<n>.hip, include/wmz.h:
+// wmz_layer_chain_fwd_slots) -- the same kernel with q and k | v leaving through the destination row map of fused_row_maps.h,
+// per lane, into plane slots of buffers that hold more planes than the launch computes.  Units of their own (launches with a
+// tail, inference only), so that the units without the option hold the kernels they held, unchanged.
+#ifdef WMZ_CHAIN_SLOTS_UNIT
+#include "fused_row_maps.h"
+#define CHAIN_KERNEL layer_chain_slots_kernel
+#define CHAIN_GROUP_BASE wmz_chain_fwd_slots_group
+#else
+#define CHAIN_KERNEL layer_chain_kernel
+#define CHAIN_GROUP_BASE wmz_chain_fwd_group
+#endif
 // a group's launcher: WMZ_OK / an error code, or -1 when the widths are not this group's
 #ifdef WMZ_OP16_F16
-#define CHAIN_GROUP_FN(g) WMZ_CHAIN_CAT(WMZ_CHAIN_CAT(wmz_chain_fwd_group, g), _f16)
+#define CHAIN_GROUP_FN(g) WMZ_CHAIN_CAT(WMZ_CHAIN_CAT(CHAIN_GROUP_BASE, g), _f16)
 #else
-#define CHAIN_GROUP_FN(g) WMZ_CHAIN_CAT(wmz_chain_fwd_group, g)
+#define CHAIN_GROUP_FN(g) WMZ_CHAIN_CAT(CHAIN_GROUP_BASE, g)
 #endif
 #define CHAIN_DECLARE_GROUP(g) \
   int CHAIN_GROUP_FN(g)(const void* params, int D, int I, int M, int head, int tail, int train, hipStream_t st);
@@ -74,6 +86,11 @@ struct ChainParams {
   float* st_ff;         // [2, N]  mean | rstd of x1
   bf16_t* xn_attn;      // [N, D]  the normalised rows of x2 (what the next layer's folded to_k / to_v consume)
   float* st_attn;       // [2, N]  mean | rstd of x2
+#ifdef WMZ_CHAIN_SLOTS_UNIT
+  // the destination map of q and k | v (fused_row_maps.h): row t of the compact grid goes to fused_dst_row(rows_out, rows_dst,
+  // row0_dst, t); voff already counts the slots (fused_dst_total rows)
+  int rows_out, rows_dst, row0_dst;
+#endif
 };
 
 constexpr int pad16(int n) { return (n + CSP - 1) / CSP * CSP; }
@@ -91,7 +108,7 @@ struct ChainShape {
 // (they ARE the packed B operands of the GEMMs behind the norms: no extra arithmetic), the feed-forward pre-activation, GELU of it,
 // both LayerNorm statistics pairs and, on request, the raw feed-forward input.
 template <int D, int I, int M, int MC, bool HEAD, bool TAIL, bool TRAIN>
-__global__ __launch_bounds__(CW * 64, 2) void layer_chain_kernel(ChainParams P) {
+__global__ __launch_bounds__(CW * 64, 2) void CHAIN_KERNEL(ChainParams P) {
   using S = ChainShape<D, I, M, MC, HEAD, TAIL>;
   constexpr int NBD = D / 16, NBI = I / 16, KSD = D / 32, KSI = I / 32, NBC = MC / 16, KSC = MC / 32;
   constexpr int VEC = 2 * D + M + 2 * I;
@@ -321,13 +338,18 @@ __global__ __launch_bounds__(CW * 64, 2) void layer_chain_kernel(ChainParams P) 
 #pragma unroll
     for (int b = 0; b < NBI; ++b) a[b] = (f32x4)(0.f);
     gemm(CNBI{}, CKSD{}, a, xq);
-    store_rows(CNBI{}, P.q + tok * I + g * (I / 4), a, WMZ_HG_QKV);
+#ifdef WMZ_CHAIN_SLOTS_UNIT                                 // this LANE's row in the slot buffers (a wave's 16 tokens can lie in two clips)
+    const long tokd = fused_dst_row(P.rows_out, P.rows_dst, P.row0_dst, tok);
+#else
+    const long tokd = tok;
+#endif
+    store_rows(CNBI{}, P.q + tokd * I + g * (I / 4), a, WMZ_HG_QKV);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
       for (int b = 0; b < NBI; ++b) a[b] = *reinterpret_cast<const f32x4*>(vec + 2 * D + M + t * I + g * (I / 4) + 4 * b);
       gemm(CNBI{}, CKSD{}, a, xn);
-      store_rows(CNBI{}, P.kv + (long)t * P.voff + tok * P.ldkv + g * (I / 4), a, WMZ_HG_QKV);
+      store_rows(CNBI{}, P.kv + (long)t * P.voff + tokd * P.ldkv + g * (I / 4), a, WMZ_HG_QKV);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the ring's run-ahead requests land before the LDS is handed back
@@ -340,10 +362,18 @@ template <int D, int I, int M, int MC, bool TRAIN>
 int launch_chain(const ChainParams& P, int head, int tail, hipStream_t st) {
   const long ntok = (long)P.B * P.n_q * P.HW;
   const dim3 grid((unsigned)((ntok + CW * CT - 1) / (CW * CT))), block(CW * 64);
+#ifdef WMZ_CHAIN_SLOTS_UNIT       // (only the launches that place something: a tail, inference)
+  static_assert(!TRAIN, "the slots form is inference only");
+  if (!tail) return WMZ_ERR_ARG;
+  if (head) hipLaunchKernelGGL((CHAIN_KERNEL<D, I, M, MC, true, true, false>), grid, block, 0, st, P);
+  else hipLaunchKernelGGL((CHAIN_KERNEL<D, I, M, MC, false, true, false>), grid, block, 0, st, P);
+  WMZ_LAUNCH_CHECK("wmz_layer_chain_fwd_slots");
+#else
   if (head && tail) hipLaunchKernelGGL((layer_chain_kernel<D, I, M, MC, true, true, TRAIN>), grid, block, 0, st, P);
   else if (head) hipLaunchKernelGGL((layer_chain_kernel<D, I, M, MC, true, false, TRAIN>), grid, block, 0, st, P);
   else hipLaunchKernelGGL((layer_chain_kernel<D, I, M, MC, false, true, TRAIN>), grid, block, 0, st, P);
   WMZ_LAUNCH_CHECK("wmz_layer_chain_fwd");
+#endif
   return WMZ_OK;
 }
 
@@ -351,7 +381,10 @@ int launch_chain(const ChainParams& P, int head, int tail, hipStream_t st) {
 
 int CHAIN_GROUP_FN(WMZ_CHAIN_GROUP)(const void* params, int D, int I, int M, int head, int tail, int train, hipStream_t st) {
   const ChainParams& P = *static_cast<const ChainParams*>(params);
-#ifdef WMZ_OP16_F16
+#if defined(WMZ_CHAIN_SLOTS_UNIT)
+#define CHAIN_TRY(d, i, m, mc) \
+  if (D == d && I == i && M == m) return launch_chain<d, i, m, mc, false>(P, head, tail, st);
+#elif defined(WMZ_OP16_F16)
 #define CHAIN_TRY(d, i, m, mc)                                                                            \
   if (D == d && I == i && M == m) {                                                                       \
     if (train) {                                                                                          \
@@ -385,6 +418,37 @@ int chain_dispatch(const ChainParams& P, int D, int I, int M, int head, int tail
 }
 }  // namespace
 
+#ifdef WMZ_CHAIN_SLOTS_UNIT
+// ---- the context cache's form (include/wmz.h): wmz_layer_chain_fwd_planes with q_out [B, dst_planes, HW, I] and kv_out
+// [2, B, dst_planes, HW, I] holding plane SLOTS, of which the launch writes dst_plane0 .. dst_plane0 + n_q - 1 of every clip and no
+// other byte; x_out stays compact.  (The half unit's entry point is the slots form OF the _f16 entry point, as in layer_fused.hip.)
+#ifdef WMZ_OP16_F16
+#define WMZ_CHAIN_SLOTS_FN wmz_layer_chain_fwd_f16_slots
+#define WMZ_CHAIN_SLOTS_NAME "wmz_layer_chain_fwd_f16_slots"
+#else
+#define WMZ_CHAIN_SLOTS_FN wmz_layer_chain_fwd_slots
+#define WMZ_CHAIN_SLOTS_NAME "wmz_layer_chain_fwd_slots"
+#endif
+extern "C" int WMZ_CHAIN_SLOTS_FN(const void* o, const void* x, void* x_out, void* q_out, void* kv_out, const void* wpack,
+                                  const float* vec, int B, int n_q, int n_in, int HW, int D, int I, int M, int head, int tail,
+                                  float eps, int dst_planes, int dst_plane0, void* stream) {
+  WMZ_REQUIRE(B > 0 && n_q > 0 && n_in >= n_q && HW > 0, WMZ_CHAIN_SLOTS_NAME ": bad shape");
+  WMZ_REQUIRE(fused_slots_ok(n_q, dst_planes, dst_plane0),
+              WMZ_CHAIN_SLOTS_NAME ": the planes written, dst_plane0 .. dst_plane0 + n_q - 1, must lie inside the dst_planes slots");
+  WMZ_REQUIRE((long)B * n_in * HW < (1L << 31) && (long)B * dst_planes * HW < (1L << 31), WMZ_CHAIN_SLOTS_NAME ": token count overflows int");
+  if (!tail)                           // the last layer: no q or k | v to place -- the trailing-planes launch as it is
+    return WMZ_FN(wmz_layer_chain_fwd_planes)(o, x, x_out, nullptr, nullptr, wpack, vec, B, n_q, n_in, HW, D, I, M, head, 0, eps, stream);
+  WMZ_REQUIRE(x && wpack && vec && q_out && kv_out, WMZ_CHAIN_SLOTS_NAME ": null tensor");
+  WMZ_REQUIRE(!head || (o && x_out), WMZ_CHAIN_SLOTS_NAME ": head needs o and x_out");
+  ChainParams P;
+  P.o = (const bf16_t*)o; P.x = (const bf16_t*)x; P.xo = (bf16_t*)x_out; P.q = (bf16_t*)q_out; P.kv = (bf16_t*)kv_out;
+  P.wpack = (const char*)wpack; P.vec = vec; P.B = B; P.n_q = n_q; P.n_in = n_in; P.HW = HW; P.eps = eps;
+  P.rows_out = n_q * HW; P.rows_dst = dst_planes * HW; P.row0_dst = dst_plane0 * HW;
+  P.ldkv = I; P.voff = fused_dst_total(B, P.rows_dst) * I;
+  P.x1 = P.xn_ff = P.z = P.h = P.xn_attn = nullptr; P.st_ff = P.st_attn = nullptr;
+  return chain_dispatch(P, D, I, M, head, tail, 0, (hipStream_t)stream, WMZ_CHAIN_SLOTS_NAME);
+}
+#else  // WMZ_CHAIN_SLOTS_UNIT
 // pieces (KB) per weight slab: every GEMM stage of the packed stream is padded to a multiple of it
 #ifndef WMZ_OP16_F16
 extern "C" int wmz_layer_chain_slab_pieces(void) { return CSP; }
@@ -448,4 +512,5 @@ extern "C" int wmz_layer_chain_fwd_train(const void* o, const void* x, void* x_o
   return chain_dispatch(P, D, I, M, head, tail, 1, st, "wmz_layer_chain_fwd_train");
 }
 #endif  // WMZ_OP16_F16
+#endif  // WMZ_CHAIN_SLOTS_UNIT
 #endif  // WMZ_CHAIN_GROUP == 0

@@ -728,7 +728,14 @@ class ContextCache:
     q [B, a[l]+1, H, W, I] and kv [2, B, a[l]+1, H, W, I] (a = context_planes).  context_prefill fills the slots 0 .. a[l]-1, each
     decode step (transformer_forward_last_cached) writes the generated frame's rows into slot a[l], and the attention launches read
     K / V in place: no copy, no second layout.  The addresses are fixed for the cache's lifetime (captured graphs bake them in).
-    Zero-filled at birth: a slot nobody wrote yet holds finite values."""
+    Zero-filled at birth: a slot nobody wrote yet holds finite values.
+    The widths are the stack's: family 'chain' with (D, I, M) of chain_widths(tr) (the passes below named *_chain, on
+    csrc/layer_chain_slots_g<n>.hip), or family 'fused' with the default widths (layer_fused_slots.hip)."""
+
+    @staticmethod
+    def _family(tr):
+        cw = chain_widths(tr)
+        return ('fused', (D_, I_, M_), 0) if cw is None else ('chain', tuple(cw[:3]), cw[3])
 
     def __init__(self, tr, B, S, H, W, dtype, device):
         layers = list(tr.layers)
@@ -736,11 +743,18 @@ class ContextCache:
         self.depth = len(layers)
         self.geometry = (int(B), int(S), int(H), int(W))
         self.dtype, self.device = dtype, torch.device(device)
+        self.family, self.widths, self.mc = self._family(tr)
         self.a = context_planes(S, self.eS, self.depth)
-        self.q = [torch.zeros((B, n + 1, H, W, I_), dtype=dtype, device=device) for n in self.a]
-        self.kv = [torch.zeros((2, B, n + 1, H, W, I_), dtype=dtype, device=device) for n in self.a]
+        I = self.widths[1]
+        self.q = [torch.zeros((B, n + 1, H, W, I), dtype=dtype, device=device) for n in self.a]
+        self.kv = [torch.zeros((2, B, n + 1, H, W, I), dtype=dtype, device=device) for n in self.a]
 
-    def check(self, tr, z, dtype):
+    def check(self, tr, z, dtype, family=None):
+        """family: the kernel family of the pass that is about to run on this cache (None: the stack's own)."""
+        fam, widths, _ = self._family(tr)
+        if (fam, widths) != (self.family, self.widths) or (family is not None and family != self.family):
+            raise ValueError(f'this ContextCache was built for the {self.family} kernels at widths {self.widths}; got a stack of the '
+                             f'{fam} kernels at widths {widths}' + (f' in a {family} pass' if family is not None else ''))
         if (tuple(z.shape) != self.geometry or dtype != self.dtype or z.device != self.device or len(tr.layers) != self.depth
                 or int(tr.layers[0][0].fn.extents[0]) != self.eS):
             raise ValueError(f'this ContextCache was built for clips {self.geometry} in {self.dtype} on {self.device}, depth '
@@ -757,11 +771,12 @@ def _slots_attention(cache, l, attn, q_plane0, q_planes):
     """Layer l's attention over its slot buffers, queries from the slots [q_plane0, q_plane0 + q_planes): the existing causal entry
     point with S = a[l] + 1 -- no context query sees the spare slot behind it."""
     B, _, H, W = cache.geometry
+    I = cache.widths[1]
     q, kv = cache.q[l], cache.kv[l]
     heads, ext, win = attn.fn.heads, attn.fn.extents, attn.fn.time_window
-    o = torch.empty((B, q_planes, H, W, I_), dtype=cache.dtype, device=cache.device)
+    o = torch.empty((B, q_planes, H, W, I), dtype=cache.dtype, device=cache.device)
     L.call('wmz_local3d_attn_fwd_window', L.ptr(q), L.ptr(kv[0]), L.ptr(kv[1]), L.ptr(o), None, None,
-           B, cache.a[l] + 1, H, W, heads, I_ // heads, win[0], win[1], int(ext[1]), int(ext[2]), I_, I_, I_, I_,
+           B, cache.a[l] + 1, H, W, heads, I // heads, win[0], win[1], int(ext[1]), int(ext[2]), I, I, I, I,
            q_plane0, q_planes, 0, L.dtype_code(cache.dtype), L.stream())
     return o
 
@@ -794,46 +809,100 @@ def _slots_embed(tr, cache, z, planes_out, dst_plane0, tiled):
     return x
 
 
-def context_prefill(tr, z, cache=None):
+def _slots_layer_chain(cache, l, o, x, planes_out, planes_in, head, tail, dst_plane0, tiled=False):
+    """_slots_layer at the chain kernels' widths (wmz_layer_chain_fwd_slots; row-major streams only): the weight stream is
+    _chain_pack's, the one the uncached chain forward reads."""
+    B, _, H, W = cache.geometry
+    bf, dev = cache.dtype, cache.device
+    D, I, M = cache.widths
+    wpack, vec = _chain_pack(head, tail, D, I, M, cache.mc, bf)
+    xo = torch.empty((B, planes_out, H, W, D), dtype=bf, device=dev) if head is not None else None
+    q, kv, n_dst = (cache.q[l + 1], cache.kv[l + 1], cache.a[l + 1] + 1) if tail is not None else (None, None, planes_out)
+    L.call(_slots_entry('wmz_layer_chain_fwd', bf), L.ptr(o), L.ptr(x), L.ptr(xo), L.ptr(q), L.ptr(kv), L.ptr(wpack), L.ptr(vec),
+           B, planes_out, planes_in, H * W, D, I, M, 1 if head is not None else 0, 1 if tail is not None else 0, 1e-5, n_dst,
+           dst_plane0, L.stream())
+    return xo
+
+
+def _slots_embed_chain(tr, cache, z, planes_out, dst_plane0, tiled=False):
+    """_slots_embed at the chain kernels' widths, as transformer_forward_chain embeds: the embedding launch in the compute dtype
+    (the precise mode: the sum in fp32, rounded once to half) -- here of the last planes_out planes alone --, then the chain
+    launch without a head that writes layer 0's q and k | v into the slots dst_plane0 .. of its buffers."""
+    from .functional import get_compute_dtype
+    B, S, H, W = z.shape
+    bf, D = cache.dtype, cache.widths[0]
+    dt = get_compute_dtype()
+    x = torch.empty((B, planes_out, H, W, D), dtype=dt, device=cache.device)
+    L.call('wmz_embed_pos3d_fwd_planes', L.ptr(z), L.ptr(tr.embedding.weight.detach()), L.ptr(tr.pos_emb_s.weight.detach()),
+           L.ptr(tr.pos_emb_h.weight.detach()), L.ptr(tr.pos_emb_w.weight.detach()), L.ptr(x), B, S, H, W, planes_out, D,
+           tr.embedding.num_embeddings, L.dtype_code(dt), L.stream())
+    if x.dtype != bf:
+        x = x.to(bf)
+    _slots_layer_chain(cache, -1, None, x, planes_out, planes_out, None, tr.layers[0], dst_plane0)
+    return x
+
+
+# the launches of a cached pass per kernel family: (embedding launch, per-token launch); the passes below are the same for both
+_SLOTS_FORMS = {'fused': (_slots_embed, _slots_layer), 'chain': (_slots_embed_chain, _slots_layer_chain)}
+
+
+def context_prefill(tr, z, cache=None, family='fused'):
     """The context pass of a causal stack over the token grid z [B, S, H, W]: everything of z[:, :-1] that the generated plane
     z[:, -1] can see, computed once and kept (ContextCache; a given cache is refilled in place).  z[:, :-1] is embedded as an
     (S-1)-plane grid -- a plane's position index is its index in the clip either way --, then layer l < depth-1 runs attention
     and its head on a[l+1] query planes over a[l] key planes (context_planes), every launch writing the next layer's q and k | v
     into the slots 0 .. a[l+1]-1 of its buffers.  One chain of launches on the current stream (config.clip_streams does not apply).
+    family: 'fused' (the default widths) or 'chain' (context_prefill_chain).
     The caller vouches for a causal stack with one time extent (VqVideoDiffusionModel.context_prefill checks)."""
     B, S, H, W = z.shape
     bf = config.get_fused_dtype()
     if cache is None:
         cache = ContextCache(tr, B, S, H, W, bf, z.device)
-    else:
-        cache.check(tr, z, bf)
+    cache.check(tr, z, bf, family)
+    embed, layer = _SLOTS_FORMS[family]
     a = cache.a
     if a[0] == 0:                              # S = 1 or a time extent of 0: the generated plane sees no context
         return cache
     layers = list(tr.layers)
-    tiled = (H * W) % 32 == 0
-    x = _slots_embed(tr, cache, z[:, :-1].contiguous(), a[0], 0, tiled)
+    tiled = family == 'fused' and (H * W) % 32 == 0
+    x = embed(tr, cache, z[:, :-1].contiguous(), a[0], 0, tiled)
     for l in range(len(layers) - 1):
         o = _slots_attention(cache, l, layers[l][0], a[l] - a[l + 1], a[l + 1])
-        x = _slots_layer(cache, l, o, x, a[l + 1], a[l], layers[l], layers[l + 1], 0, tiled)
+        x = layer(cache, l, o, x, a[l + 1], a[l], layers[l], layers[l + 1], 0, tiled)
     return cache
 
 
-def transformer_forward_last_cached(tr, z, cache):
+def transformer_forward_last_cached(tr, z, cache, family='fused'):
     """The last plane of transformer_forward(tr, z) ([B, H, W, D]) from z[:, -1] and the context kept in `cache`
     (context_prefill of a grid with the same z[:, :-1]): one embedding launch plus, per layer, one attention launch -- the
     generated plane's queries over the layer's slots -- and one per-token launch, all of one plane.  Per-token arithmetic is per
-    token and the query plane sees the same key planes in the same order: bit-identical to the uncached forward."""
-    cache.check(tr, z, config.get_fused_dtype())
+    token and the query plane sees the same key planes in the same order: bit-identical to the uncached forward.
+    family: 'fused' or 'chain' (transformer_forward_last_cached_chain)."""
+    cache.check(tr, z, config.get_fused_dtype(), family)
+    embed, layer = _SLOTS_FORMS[family]
     layers = list(tr.layers)
     a = cache.a
-    tiled = (z.shape[2] * z.shape[3]) % 32 == 0
-    x = _slots_embed(tr, cache, z.contiguous(), 1, a[0], tiled)
+    tiled = family == 'fused' and (z.shape[2] * z.shape[3]) % 32 == 0
+    x = embed(tr, cache, z.contiguous(), 1, a[0], tiled)
     for l, (attn, ff) in enumerate(layers):
         o = _slots_attention(cache, l, attn, a[l], 1)
         tail = layers[l + 1] if l + 1 < len(layers) else None
-        x = _slots_layer(cache, l, o, x, 1, 1, (attn, ff), tail, a[l + 1] if tail is not None else 0, tiled)
+        x = layer(cache, l, o, x, 1, 1, (attn, ff), tail, a[l + 1] if tail is not None else 0, tiled)
     return x[:, 0]
+
+
+def context_prefill_chain(tr, z, cache=None):
+    """context_prefill at the widths of csrc/chain_widths.h: the same passes and the same context_planes law on the chain kernels
+    -- an embedding launch plus a chain launch without a head where the fused form has its embedding launch.  The cached passes
+    ALWAYS run the chain kernels, whatever chain_pays would say about their smaller token count: they are bit-identical to the
+    uncached chain forward (transformer_forward_chain), which is the route the caller found the whole grid on."""
+    return context_prefill(tr, z, cache, 'chain')
+
+
+def transformer_forward_last_cached_chain(tr, z, cache):
+    """transformer_forward_last_cached at the chain kernels' widths: the last plane of transformer_forward_chain(tr, z), bit for
+    bit, one plane per launch."""
+    return transformer_forward_last_cached(tr, z, cache, 'chain')
 
 
 # ---------------------------------------------------------------------------------------------------------------------

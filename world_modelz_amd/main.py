@@ -57,15 +57,24 @@ class VqVideoDiffusionModel(nn.Module):
             return f'the token grid is [B, S, H, W], not {tuple(z.shape)}'
         _, S, H, W = z.shape
         dt = config.get_fused_dtype()
-        if dt not in (torch.bfloat16, torch.float16) or fused.inference_route(tr, dt, H, W, z.numel()) != 'fused':
-            return 'only the fused widths in bf16 or in the precise mode keep a context cache (other widths and fp32 run the uncached forward)'
+        if dt not in (torch.bfloat16, torch.float16) or self._context_cache_family(z) is None:
+            return ('only a model whose uncached forward runs the fused or the chain kernels at this grid, in bf16 or in the precise '
+                    'mode, keeps a context cache (op-by-op widths, grids the chain kernels do not take, and fp32 run the uncached forward)')
         if S > tr.pos_emb_s.num_embeddings or H > tr.pos_emb_h.num_embeddings or W > tr.pos_emb_w.num_embeddings:
             return 'token grid larger than the position-embedding tables'
         return None
 
+    def _context_cache_family(self, z):
+        """The kernel family of the cached passes on the token grid z: that of the UNCACHED forward at this grid -- 'fused', 'chain'
+        (the widths of csrc/chain_widths.h where the chain kernels take the grid: always in the precise mode, by config.chain_policy
+        in bf16) -- or None."""
+        from . import config, fused
+        route = fused.inference_route(self.transformer, config.get_fused_dtype(), z.shape[2], z.shape[3], z.numel())
+        return route if route in ('fused', 'chain') else None
+
     def context_cache_eligible(self, z):
         """Whether context_prefill(z) / forward_last(z, cache) would run: a causal model with one time extent, without grad on
-        the GPU, on the fused inference route in bf16 or in the precise mode."""
+        the GPU, on the fused or the chain inference route in bf16 or in the precise mode."""
         return self._context_cache_refusal(z) is None
 
     def _context_cache_check(self, z):
@@ -81,7 +90,7 @@ class VqVideoDiffusionModel(nn.Module):
         it uncached on the fp32 route."""
         from . import fused
         self._context_cache_check(z)
-        return fused.context_prefill(self.transformer, z, cache)
+        return fused.context_prefill(self.transformer, z, cache, self._context_cache_family(z))
 
     def forward_last(self, z, cache):
         """forward(z) -- fp32 logits [B, H, W, C] of the last frame, bit for bit -- reading z[:, -1] only: everything of the
@@ -89,7 +98,7 @@ class VqVideoDiffusionModel(nn.Module):
         where context_cache_eligible(z) is False."""
         from . import fused
         self._context_cache_check(z)
-        return self._logits(fused.transformer_forward_last_cached(self.transformer, z, cache))
+        return self._logits(fused.transformer_forward_last_cached(self.transformer, z, cache, self._context_cache_family(z)))
 
     def _logits(self, last):
         # (a half stream -- the precise mode -- takes the half unit of the same GEMM: fp32 accumulation, fp32 logits)

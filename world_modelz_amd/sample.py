@@ -143,7 +143,7 @@ def sample_frames(model, batch_z, num_embeddings, num_frames, num_eval_iteration
     (1 - alpha); its uniform is u_mask[f, i] when injected.  ValueError for anything else.  (Config 5's sampler,
     sparse_diffusion.sample_clips, takes all of these too: it masks when it gathers a context, so its 'confidence' orders that
     masking by a score kept per clip position between sub-steps.)
-    context_cache: True -- a causal model on the fused widths computes the context planes' K / V once per frame
+    context_cache: True -- a causal model on the fused or the chain kernels' widths computes the context planes' K / V once per frame
     (model.context_prefill) and the generated plane alone per iteration (model.forward_last): the same logits bit for bit, hence
     the same tokens; ValueError on a model that is not eligible.  None (default) reads config.context_cache and keeps the
     uncached path where the model is not eligible; False: the uncached path."""
